@@ -18,7 +18,13 @@ rank 0 (--end-collective reduce: the full-frame sum-reduce instead; the same bit
       paths; their tails weigh N times more); BDPT band split with one splat
       reduce-scatter per call.
 
-Also reported (one JSON line on rank 0):
+A plain run sets up, warms up, times the steps and prints the headline line (one JSON line on rank
+0: metric, value, unit, ms_per_step, the configuration).  --dump-outputs DIR then also writes what the
+last timed step left in the frame buffer (dump_outputs below).  Everything else runs only with --full.
+
+With --full also reported in the line:
+  rays_per_path, shadow_hints, queues_per_frame   statistics of one untimed frame
+  kernels       per-kernel HIP-event times of an untimed one-slot pass
   roofline      dominant kernel (k_shadow_extend): compulsory bytes per launch (ray I/O + 64 B per
                 DISTINCT BVH node the launch visits, counted by the oracle) over its average HIP-event
                 duration in an untimed one-slot pass, vs the 8 TB/s HBM peak; traffic = rocprofv3
@@ -504,6 +510,30 @@ def timed_region(render, end_of_job, world, sync, device="cuda", trace=None):
     return el
 
 
+DUMP_LIMIT = 64 << 20   # bytes of all dumped arrays together
+
+
+def sample_rows(a, max_bytes):
+    """`a` itself if it fits in max_bytes, else a fixed sample of its rows (seeded, in row order):
+    the same rows for the same shape in every run."""
+    if a.nbytes <= max_bytes:
+        return a
+    n = max(1, int(max_bytes // (a.nbytes // a.shape[0])))
+    rows = np.sort(np.random.default_rng(0).choice(a.shape[0], n, replace=False))
+    return np.ascontiguousarray(a[rows])
+
+
+def dump_outputs(path, fb, last_call_frames):
+    """--dump-outputs: what a caller of the timed path holds after its last step, as float32 .npy:
+      image.npy           the accumulated, resolved image (mcrt_framebuffer_read 2; --save-image's array)
+      last_radiance.npy   the radiance of the last frame of the last mcrt_render_frames call
+    each whole when it fits its share of DUMP_LIMIT (image 5/8, radiance 1/4), else sample_rows of it."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "image.npy"), sample_rows(fb.read(2), DUMP_LIMIT * 5 // 8))
+    np.save(os.path.join(path, "last_radiance.npy"),
+            sample_rows(fb.read_frame(last_call_frames - 1), DUMP_LIMIT // 4))
+
+
 def launch_ranks(n):
     """Runs this script under `python -m torch.distributed.run --nproc-per-node n` (one process
     per GPU, rendezvous on 127.0.0.1 at a free port) as a child process with the same arguments,
@@ -535,6 +565,11 @@ def main():
     ap.add_argument("--band-rows", type=int, default=8)
     ap.add_argument("--end-collective", default="gather", choices=["gather", "reduce"],
                     help="tile split: gather each rank's band rows to rank 0, or sum-reduce the full frames")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the other legs: one-frame path statistics, per-kernel "
+                         "timing pass, BDPT object, CPU baseline, reference parity, roofline (each has its --no-* switch)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 writes what the last timed step left in the frame buffer as DIR/<name>.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-reference-parity", action="store_true",
                     help="skip the reference-kernel render of the first timed frame (parity_vs_reference)")
@@ -595,6 +630,11 @@ def main():
     env_world = os.environ.get("WORLD_SIZE")
     if args.gpus < 1:
         sys.exit(f"bench.py: --gpus must be >= 1 (got {args.gpus})")
+    if args.steps < 1:
+        sys.exit(f"bench.py: --steps must be >= 1 (got {args.steps})")
+    if not args.full:   # a plain run: the headline's timed steps only
+        args.no_kernel_timing = args.no_bdpt = args.no_cpu_baseline = True
+        args.no_reference_parity = args.no_roofline_model = True
     if env_world is None and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus))
     if env_world is not None and int(env_world) != args.gpus:
@@ -679,6 +719,7 @@ def main():
     else:
         band = dict(band_rows=args.band_rows, num_bands=world, band_index=rank)
     first = [True]
+    last_call = [1]   # frames of the latest call
     # auto: 32 frames per launch (MCRT_MAX_BATCH_FRAMES) up to 1080p, 16 above (slot memory).  The
     # camera and first-shading waves then hold 2 pixels x 32 jittered frames (packed waves); the
     # sweep tools/r2_gpu27.sh measured 1297 / 1315 Mpaths/s at 16 / 32 frames per launch, and a
@@ -708,6 +749,7 @@ def main():
             mdist.exchange_splats(fb, splat_full, splat_own)
         fb.accumulate(filt, 0 if first[0] else frame)   # 0: the first accumulation overwrites
         first[0] = False
+        last_call[0] = n
 
     def run(i0, count, per=None):
         # calls of min(batch, remaining) frames: the camera and first-shading waves pack 64 consecutive
@@ -731,16 +773,20 @@ def main():
     warm = max(args.warmup, 4 * batch)
     run(0, warm)
     ctx.sync()
-    warm_frames = warm + 1   # + the untimed statistics frame below (the driver's W is a minimum)
-    # per-frame path statistics (device queue sizes, occluder-hint counts) from one untimed frame
-    ctx.set_profiling(2)
+    warm_frames = warm + 1   # + the untimed single frame below (the driver's W is a minimum)
+    # one more untimed frame, rendered alone; --full: with the per-frame path statistics (device queue
+    # sizes, occluder-hint counts) switched on for it
+    fstats = qcounts = hcounts = rcounts = None
+    if args.full:
+        ctx.set_profiling(2)
     step(warm)
     ctx.sync()
-    ctx.set_profiling(False)
-    fstats = fb.stats()
-    qcounts = fb.queue_counts(max(D, 8)) if not bdpt else None
-    hcounts = fb.hint_counts(max(D, 8)) if not bdpt else None   # shadow rays answered by their occluder hint
-    rcounts = fb.retrace_counts(max(D, 8)) if not bdpt else None   # compact walks repeated on exact records
+    if args.full:
+        ctx.set_profiling(False)
+        fstats = fb.stats()
+        qcounts = fb.queue_counts(max(D, 8)) if not bdpt else None
+        hcounts = fb.hint_counts(max(D, 8)) if not bdpt else None   # shadow rays answered by their occluder hint
+        rcounts = fb.retrace_counts(max(D, 8)) if not bdpt else None   # compact walks repeated on exact records
     frame0 = warm + 1
 
     ctx.reset_stats()
@@ -776,6 +822,8 @@ def main():
     elapsed = timed_region(lambda: run(frame0, args.steps * fps), end_of_job, world, sync)
     if args.save_image and rank == 0:
         np.save(args.save_image, fb.read(2))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, fb, last_call[0])
     kstats = {}
     if not args.no_kernel_timing:
         # per-kernel HIP-event durations in a separate, untimed pass: one frame slot (kernels do not
@@ -826,9 +874,10 @@ def main():
                    "frames_per_launch": stats_batch, "max_frames_per_call": batch},
     }
     if rank == 0:
-        rays = {"closest": fstats["closest_rays"] / (W * H / world), "any": fstats["any_rays"] / (W * H / world),
-                "shaded": fstats["shaded_paths"] / (W * H / world)}
-        out["rays_per_path"] = {k: round(v, 4) for k, v in rays.items()}
+        if fstats is not None:
+            rays = {"closest": fstats["closest_rays"] / (W * H / world), "any": fstats["any_rays"] / (W * H / world),
+                    "shaded": fstats["shaded_paths"] / (W * H / world)}
+            out["rays_per_path"] = {k: round(v, 4) for k, v in rays.items()}
         if hcounts is not None and qcounts is not None:   # occluder hints
             out["shadow_hints"] = {f"bounce{b}": round(hcounts[b] / max(qcounts[0][b], 1), 4) for b in range(D)}
             # the wavefront's queues per bounce (one untimed frame): compaction keeps only live paths,

@@ -10,13 +10,17 @@ own C++ (oracle/_ref/librrref.so, built from /root/reference by oracle/refbuild)
                         radeon_rays_conformance_test_cl.h:160,552-556) + brute-force golden hits
                         from the reference's UnitTest/utils.cpp TestIntersections/TestOcclusions
   bunny.npz             assets/meshes/bunny.obj
+  meshes.zip            assets/meshes/bunny.obj and cornell-box/*.{obj,mtl} as they are (mesh data, with
+                        the set's copyright.txt), unpacked by tests/test_objload_capi_cpu.py
   sobol_1024x52.npy     the Joe-Kuo Sobol generator matrices uploaded as scene data (written to
                         monte-carlo-raytracer_amd/mcrt/data/, the product's package data)
                         (source/application/PathTracer/raytracing/sampling/sobol.h:34)
   rr_bvh_mixed.npz      node array of the reference Bvh2 (bvh2.cpp) over mcrt.scenes.test_scene()
 
 Generated on the GPU box instead (the reference's OpenCL kernels need the MI355X):
-  clref_{ieee,fast}.npz       python tests/clref_job.py OUT VARIANT
+  clref_{ieee,fast}.npz       python tests/clref_job.py OUT VARIANT; its {bunny,mixed}_{rays,closest}
+                              arrays (the same in both variants) are kept once, in
+                              clref_queries_{bunny,mixed}.npz, so that each file stays under 1 MiB
   clref_bdpt_{ieee,fast}.npz  python tests/clref_job.py OUT VARIANT bdpt, then
                               tests/clref_job.py:strip_bdpt_golden(OUT, FIXTURE) keeps the
                               radiance frames and vertex counts

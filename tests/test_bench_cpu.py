@@ -41,3 +41,16 @@ def test_plain_command_launches_ranks():
     assert "launching 2 ranks" in r.stderr and "torch.distributed.run" in r.stderr
     assert r.returncode != 0
     assert "2 ranks over nccl need 2 GPUs" in r.stderr, r.stderr[-3000:]
+
+
+def test_sample_rows_is_fixed_and_bounded():
+    sys.path.insert(0, ROOT)
+    import numpy as np
+    import bench
+    a = np.arange(100 * 8 * 4, dtype=np.float32).reshape(100, 8, 4)
+    assert bench.sample_rows(a, a.nbytes) is a
+    s = bench.sample_rows(a, a.nbytes // 3)
+    assert s.shape == (33, 8, 4) and s.nbytes <= a.nbytes // 3
+    np.testing.assert_array_equal(s, bench.sample_rows(a.copy(), a.nbytes // 3))
+    rows = s[:, 0, 0].astype(int) // 32
+    assert (np.diff(rows) > 0).all() and np.array_equal(s, a[rows])

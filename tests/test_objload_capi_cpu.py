@@ -1,15 +1,15 @@
 """Scene ingestion through the C ABI (mcrt_obj_load, csrc/mcrt_objload.cpp) for C/C++ hosts,
 against the package's Python loader (mcrt/objload.py, the same restatement of the reference's
 assimp preset + RTScene conversion) on a synthetic OBJ/MTL/PNG scene and on the reference's own
-assets (assets/meshes: the Cornell-box family and bunny.obj, read in place when /root/reference
-is present), and against the committed CornellBox-Original fixture (tests/golden, data only).
+mesh assets (assets/meshes: the Cornell-box family and bunny.obj, committed as data in
+tests/golden/meshes.zip and unpacked into a temporary directory), and against the committed CornellBox-Original fixture (tests/golden, data only).
 
 Integer data, texel data and everything the loaders compute in a single IEEE operation are
 compared bit for bit; values the Python side reduces with numpy/BLAS (generated face normals,
 tangent frames, shape areas, the directional light's bounding sphere) to within 2 ulp / 1e-6.
 Parity with assimp itself is unpinned (assimp is not in the image)."""
-import glob
 import os
+import zipfile
 
 import numpy as np
 import pytest
@@ -17,8 +17,18 @@ import pytest
 from mcrt import lib, objload
 from test_objload_cpu import _write_scene
 
-REF = "/root/reference/assets/meshes"
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+MESHES = os.path.join(GOLD, "meshes.zip")
+with zipfile.ZipFile(MESHES) as _z:
+    CORNELL = sorted(os.path.basename(n) for n in _z.namelist() if n.startswith("cornell-box/") and n.endswith(".obj"))
+
+
+@pytest.fixture(scope="module")
+def meshes(tmp_path_factory):
+    d = tmp_path_factory.mktemp("meshes")
+    with zipfile.ZipFile(MESHES) as z:
+        z.extractall(d)
+    return str(d)
 
 
 def _compare(a, b):
@@ -70,22 +80,19 @@ def test_missing_texture_and_mtl_warn(tmp_path):
     _compare(a, b)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference assets not present")
-@pytest.mark.parametrize("name", sorted(os.path.basename(p) for p in glob.glob(f"{REF}/cornell-box/*.obj")) + ["bunny.obj"])
-def test_reference_assets_match_python_loader(name):
-    path = f"{REF}/bunny.obj" if name == "bunny.obj" else f"{REF}/cornell-box/{name}"
+@pytest.mark.parametrize("name", CORNELL + ["bunny.obj"])
+def test_reference_assets_match_python_loader(meshes, name):
+    path = f"{meshes}/bunny.obj" if name == "bunny.obj" else f"{meshes}/cornell-box/{name}"
     sun = ((-0.5, -1.0, 0.3), (40.0, 40.0, 40.0))
     _compare(lib.load_obj(path, directional_lights=[sun]), _python(path, sun))
 
 
-def test_cornell_fixture():
+def test_cornell_fixture(meshes):
     """CornellBox-Original as the C++ loader sees it, against the committed fixture (the file's
     vertices and faces, data only): the same set of triangles (z negated, winding reversed), and
     the 'light' group (Ke 17 12 4) as the one mesh light.  The loader splits a group at each
     usemtl (assimp makes one mesh per material); the fixture groups by g, so triangles are
     compared as a set."""
-    if not os.path.isdir(REF):
-        pytest.skip("reference assets not present")
     z = np.load(f"{GOLD}/cornell_original.npz", allow_pickle=False)
     names = [str(n) for n in z["names"]]
     flip = np.array([1, 1, -1], np.float32)
@@ -97,7 +104,7 @@ def test_cornell_fixture():
             out.append(tuple(np.roll(t, -k, axis=0).reshape(-1)))
         return sorted(out)
     want = np.concatenate([(z[f"P{i}"] * flip)[z[f"T{i}"][:, [0, 2, 1]]] for i in range(len(names))])
-    a = lib.load_obj(f"{REF}/cornell-box/CornellBox-Original.obj")
+    a = lib.load_obj(f"{meshes}/cornell-box/CornellBox-Original.obj")
     got = np.concatenate([a.positions[s["startVertex"] + a.indices[s["startIdx"]:s["startIdx"] + 3 * s["numTriangles"]], :3]
                           .reshape(-1, 3, 3) for s in a.shapes])
     assert canon(got) == canon(want)

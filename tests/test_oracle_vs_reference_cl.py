@@ -58,6 +58,8 @@ def test_rr_queries_match_reference_opencl():
     np.testing.assert_array_equal(h["primid"], ref["primid"])
     np.testing.assert_array_equal(o.any(g["rays_any"]), z["rr_cornell_any"])
     for nm, s in (("bunny", bunny_scene()), ("mixed", scenes.test_scene())):
+        # the same job's ray queries, one file per scene (the same in both variants)
+        z = np.load(os.path.join(GOLD, f"clref_queries_{nm}.npz"), allow_pickle=False)
         o = po.OracleScene(s)
         o.build()
         h = o.closest(z[f"{nm}_rays"])

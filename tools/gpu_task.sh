@@ -3,7 +3,7 @@
 # root).  Every GPU step has its own time limit; the first failing step ends the task.
 #
 #   tools/gpu_task.sh suite     [DIR]                     full GPU suite + smoke()
-#   tools/gpu_task.sh bench     [DIR] [bench args...]     the driver's default bench (+ extra args)
+#   tools/gpu_task.sh bench     [DIR] [bench args...]     the whole bench line: bench.py --full (+ extra args)
 #   tools/gpu_task.sh ab        LIB_A [RUNS] [bench args] alternating bench runs: in-tree library (B)
 #                                                         vs LIB_A (MCRT_LIB_PATH), per-kernel times
 #   tools/gpu_task.sh sweep     R "bench args" V...       R rounds of the in-tree library, then each
@@ -60,12 +60,12 @@ suite)
   ;;
 bench)
   P=gpurun_out/${1:-bench}; shift; mkdir -p $P
-  timeout -k 10 600 python3 bench.py "$@" > $P/bench.json 2> $P/bench.err || fail bench $P/bench.err
+  timeout -k 10 600 python3 bench.py --full "$@" > $P/bench.json 2> $P/bench.err || fail bench $P/bench.err
   summary $P/bench.json
   ;;
 ab)
   LIB=$1; R=${2:-2}; shift 2; P=gpurun_out/ab; mkdir -p $P
-  B="python3 bench.py --no-cpu-baseline --no-roofline-model $*"
+  B="python3 bench.py --full --no-cpu-baseline --no-roofline-model $*"
   for r in $(seq 1 $R); do
     MCRT_LIB_PATH=$LIB timeout -k 10 400 $B > $P/A$r.json 2> $P/A$r.err || fail A$r $P/A$r.err 4
     timeout -k 10 400 $B > $P/B$r.json 2> $P/B$r.err || fail B$r $P/B$r.err 4
@@ -75,7 +75,7 @@ ab)
 sweep)
   # rounds of: the in-tree library, then each variant libmcrt_<V>.so (tools/build_variant.sh)
   R=$1; ARGS=$2; shift 2; P=gpurun_out/sweep; mkdir -p $P
-  B="python3 bench.py --no-cpu-baseline --no-roofline-model $ARGS"
+  B="python3 bench.py --full --no-cpu-baseline --no-roofline-model $ARGS"
   for r in $(seq 1 $R); do
     timeout -k 10 400 $B > $P/base_$r.json 2> $P/base_$r.err || fail base$r $P/base_$r.err 4
     for v in "$@"; do
@@ -109,7 +109,7 @@ bdpt-prof)
   ;;
 configs)
   P=gpurun_out/${1:-configs}; mkdir -p $P
-  F="--no-cpu-baseline --no-roofline-model --no-bdpt"
+  F="--full --no-cpu-baseline --no-roofline-model --no-bdpt"
   run() { n=$1; shift; timeout -k 10 400 python3 bench.py $F "$@" > $P/$n.json 2> $P/$n.err || fail $n $P/$n.err 4; summary $P/$n.json; }
   run dragon_1080p --scene dragon_proxy --tris 871414 --steps 96
   run sponza_1080p --scene sponza_proxy --steps 96
