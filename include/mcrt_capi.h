@@ -206,7 +206,8 @@ typedef struct {
      * "bvh.force2level" (RR/src/device/calc_intersection_device.cpp:68-105, defaults off,
      * PathTracingSettings.h:239-240).  Shapes with equal (startIdx, startVertex, numTriangles)
      * are instances of the first one; each keeps its own transform, shape id and material.
-     * Host-built (device_build applies to the flat structure only). */
+     * Host-built (device_build applies to the flat structure only); after a transform change its top
+     * level alone is rebuilt, on the device or the host (mcrt_accel_update_transforms). */
     int   force_2level;
     int   force_flat;
     /* Per-shape world-to-local matrices (Shape::SetTransform's minv, RR/include/radeon_rays.h;
@@ -301,7 +302,8 @@ MCRT_API mcrt_status mcrt_ctx_gather_chase_compact(mcrt_ctx ctx, uint64_t record
 MCRT_API mcrt_status mcrt_scene_create(mcrt_ctx ctx, const mcrt_scene_desc* desc, mcrt_scene* out);
 MCRT_API mcrt_status mcrt_scene_destroy(mcrt_scene scene);
 /* Dynamic updates (RTScene::update, APP/raytracing/scene/RTScene.cpp:317-391). Shapes
- * whose transforms change require mcrt_accel_build again. */
+ * whose transforms change go through mcrt_accel_update_transforms (below), which replaces the
+ * shapes and brings the acceleration structure up to date in one call. */
 MCRT_API mcrt_status mcrt_scene_update_lights(mcrt_scene scene, const mcrt_light* lights, uint32_t n);
 MCRT_API mcrt_status mcrt_scene_update_materials(mcrt_scene scene, const mcrt_material* m, uint32_t n);
 MCRT_API mcrt_status mcrt_scene_update_shapes(mcrt_scene scene, const mcrt_shape* s, uint32_t n);
@@ -310,6 +312,31 @@ MCRT_API mcrt_status mcrt_scene_update_shapes(mcrt_scene scene, const mcrt_shape
  * Hit shapeid = index into the shapes array (RTScene assigns SetId(nextShapeId++)
  * in shape order, RTScene.cpp:592,668). opts may be NULL (defaults). */
 MCRT_API mcrt_status mcrt_accel_build(mcrt_scene scene, const mcrt_accel_opts* opts);
+/* Moved shapes: RTScene::updateDynamicEntities' SetTransform on each moved shape + Commit
+ * (APP/raytracing/scene/RTScene.cpp:317-391) in one call.  `shapes` replaces the scene's shape
+ * array as mcrt_scene_update_shapes does (same count, startIdx and numTriangles; surface records
+ * included) and the structure of the last mcrt_accel_build is brought up to date:
+ *  - two-level: RadeonRays' Refit branch (RR/src/intersector/intersector_2level.cpp:495-660):
+ *    every per-mesh tree stays, the world boxes are recomputed (transform_bbox) and a new
+ *    top-level Bvh (RR/src/accelerator/bvh.cpp:73-437) is built over them with the build's
+ *    traversal cost, bins and SAH switch.  Only records [0, top-level records) are rewritten, in
+ *    place; the result equals a fresh mcrt_accel_build of the moved shapes.  startVertex must be
+ *    unchanged too (the mesh key is (startIdx, startVertex, numTriangles)).  world_to_local: per
+ *    shape as in mcrt_accel_opts; NULL = the transpose of each toWorldInverseTranspose.
+ *    The top tree is built on the device (mcrt_topbuild.hip) from a threshold shape count upward
+ *    and on the host below it; the environment variable MCRT_TOP_BUILD=host / =device forces one
+ *    (=device fails with MCRT_ERROR_DEVICE where the device path cannot take the input, e.g. more
+ *    than 64 bins; the structure is then still brought up to date on the host).
+ *  - flat: RR's flat intersector rebuilds on every Commit: mcrt_scene_update_shapes +
+ *    mcrt_accel_build with the options of the last build.
+ * Ordered after every launch already enqueued on the context stream and on the frame-slot
+ * streams.  MCRT_ERROR_NOT_READY before the first mcrt_accel_build, MCRT_ERROR_INVALID_ARG on a
+ * topology change. */
+MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene scene, const mcrt_shape* shapes, uint32_t n,
+                                                  const mcrt_mat4* world_to_local /* may be NULL */);
+/* The last mcrt_accel_update_transforms: *path 0 none yet, 1 top level built on the device, 2 top
+ * level built on the host, 3 full rebuild (flat); *ms its wall time including its synchronisation. */
+MCRT_API mcrt_status mcrt_accel_update_info(mcrt_scene scene, int32_t* path, double* ms);
 /* Build statistics: node count, bytes on device, host build milliseconds. */
 MCRT_API mcrt_status mcrt_accel_info(mcrt_scene scene, uint64_t* num_nodes, uint64_t* device_bytes,
                                      double* build_ms, uint32_t* num_triangles);
@@ -353,6 +380,16 @@ MCRT_API mcrt_status mcrt_accel_builder(mcrt_scene scene, int32_t* builder);
  * NULL to query *num_records); info[4] = {two_level, top-level records, depth, meshes}.
  * For tools and tests (e.g. pinning the trees against the reference builders). */
 MCRT_API mcrt_status mcrt_accel_build_host_records(const mcrt_scene_desc* desc, const mcrt_accel_opts* opts,
+                                                   float* out_records, uint64_t max_records,
+                                                   uint64_t* num_records, int32_t* info);
+
+/* Host-only twin of mcrt_accel_update_transforms (no device needed): builds `desc` as it stands,
+ * applies the refit for moved_shapes (RR's Refit branch, intersector_2level.cpp:495-660) through
+ * the function the device scene's host path uses, and returns the records and info as above.  For
+ * a flat structure: the fresh build of the moved shapes. */
+MCRT_API mcrt_status mcrt_accel_refit_host_records(const mcrt_scene_desc* desc, const mcrt_accel_opts* opts,
+                                                   const mcrt_shape* moved_shapes,
+                                                   const mcrt_mat4* moved_world_to_local,
                                                    float* out_records, uint64_t max_records,
                                                    uint64_t* num_records, int32_t* info);
 

@@ -301,6 +301,53 @@ bool shapes_are_instanced(const mcrt_shape* shapes, size_t n) {
     return false;
 }
 
+void build_bvh2l_top(const Bvh2lTop& st, const mcrt_shape* shapes, const mcrt_mat4* worldToLocal, float* rec,
+                     int* depth, float* topBox) {
+    const int numShapesTop = (int)st.world.size();
+    std::vector<Box> ob(numShapesTop);
+    for (int i = 0; i < numShapesTop; ++i) {
+        Box mb;
+        for (int a = 0; a < 3; ++a) {
+            mb.lo[a] = st.meshBox[6 * st.meshOf[i] + a];
+            mb.hi[a] = st.meshBox[6 * st.meshOf[i] + 3 + a];
+        }
+        ob[i] = transformBox(mb, shapes[st.world[i]].toWorldTransform);
+    }
+    ObjBvh top(ob.data(), numShapesTop, st.cost, st.bins, st.sah, 1);
+    const size_t topN = 2 * (size_t)numShapesTop - 1;
+    for (size_t p = 0; p < topN; ++p) {
+        const int nl = top.nodeLeft[p];
+        float* r = &rec[16 * p];
+        if (nl >= 0) {
+            const int c0 = (int)p + 1, c1 = (int)p + 2 * nl;
+            putBox2(r, top.nodeBox[c0], top.nodeBox[c1]);
+            putInts(r, c0, c1, 0, 0);
+            continue;
+        }
+        const int wi = top.indices[-1 - nl];
+        const int si = st.world[wi];
+        mcrt_mat4 minv;
+        if (worldToLocal) {
+            minv = worldToLocal[si];
+        } else {   // inverse = transpose(inverse transpose)
+            const mcrt_mat4& t = shapes[si].toWorldInverseTranspose;
+            minv.m0 = {t.m0.x, t.m1.x, t.m2.x, t.m3.x};
+            minv.m1 = {t.m0.y, t.m1.y, t.m2.y, t.m3.y};
+            minv.m2 = {t.m0.z, t.m1.z, t.m2.z, t.m3.z};
+            minv.m3 = {t.m0.w, t.m1.w, t.m2.w, t.m3.w};
+        }
+        std::memcpy(r + 0, &minv.m0, 16);
+        std::memcpy(r + 4, &minv.m1, 16);
+        std::memcpy(r + 8, &minv.m2, 16);
+        putInts(r, -2, (int)st.meshBase[st.meshOf[wi]], si, 0);
+    }
+    *depth = top.height.load() + st.maxBottom + 1;   // + the return marker
+    for (int a = 0; a < 3; ++a) {
+        topBox[a] = top.rootBox.lo[a];
+        topBox[3 + a] = top.rootBox.hi[a];
+    }
+}
+
 bool build_bvh2l(const mcrt_shape* shapes, size_t nshapes, const uint32_t* indices, const mcrt_float4* positions,
                  const mcrt_mat4* worldToLocal, float cost, int bins, bool sah, int threads, Bvh2lOut& out) {
     // meshes and instances (RTScene::attachMesh: the first shape with a mesh's data owns it)
@@ -378,52 +425,38 @@ bool build_bvh2l(const mcrt_shape* shapes, size_t nshapes, const uint32_t* indic
         work();
         for (auto& t : pool) t.join();
     }
-    // top level over the world-space boxes
-    std::vector<Box> ob(numShapesTop);
-    for (int i = 0; i < numShapesTop; ++i) {
-        const int si = world[i];
-        ob[i] = transformBox(trees[ent[si].mesh]->rootBox, shapes[si].toWorldTransform);
-    }
-    ObjBvh top(ob.data(), numShapesTop, cost, bins, sah, 1);
     // records: [top][mesh 0][mesh 1]...
     const size_t topN = 2 * (size_t)numShapesTop - 1;
-    std::vector<size_t> meshBase(numMeshes);
+    Bvh2lTop& st = out.top;
+    st = Bvh2lTop();
+    st.world.assign(world.begin(), world.end());
+    st.meshOf.resize(numShapesTop);
+    for (int i = 0; i < numShapesTop; ++i) st.meshOf[i] = ent[world[i]].mesh;
+    st.meshBase.resize(numMeshes);
+    st.meshBox.resize(6 * (size_t)numMeshes);
+    st.cost = cost;
+    st.bins = bins;
+    st.sah = sah;
     size_t total = topN;
-    int maxBottom = 0;
     for (int m = 0; m < numMeshes; ++m) {
-        meshBase[m] = total;
+        if (total <= (size_t)0x7fffffff) st.meshBase[m] = (uint32_t)total;
         total += trees[m]->nodeBox.size();
-        maxBottom = std::max(maxBottom, trees[m]->height.load());
+        st.maxBottom = std::max(st.maxBottom, trees[m]->height.load());
+        for (int a = 0; a < 3; ++a) {
+            st.meshBox[6 * m + a] = trees[m]->rootBox.lo[a];
+            st.meshBox[6 * m + 3 + a] = trees[m]->rootBox.hi[a];
+        }
     }
     if (total > (size_t)0x7fffffff) {
         for (auto* t : trees) delete t;
         return false;
     }
     std::vector<float> rec(16 * total);
-    emitInternal(top, 0, rec);
-    for (size_t p = 0; p < topN; ++p) {
-        const int nl = top.nodeLeft[p];
-        if (nl >= 0) continue;
-        const int si = world[top.indices[-1 - nl]];
-        mcrt_mat4 minv;
-        if (worldToLocal) {
-            minv = worldToLocal[si];
-        } else {   // inverse = transpose(inverse transpose)
-            const mcrt_mat4& t = shapes[si].toWorldInverseTranspose;
-            minv.m0 = {t.m0.x, t.m1.x, t.m2.x, t.m3.x};
-            minv.m1 = {t.m0.y, t.m1.y, t.m2.y, t.m3.y};
-            minv.m2 = {t.m0.z, t.m1.z, t.m2.z, t.m3.z};
-            minv.m3 = {t.m0.w, t.m1.w, t.m2.w, t.m3.w};
-        }
-        float* r = &rec[16 * p];
-        std::memcpy(r + 0, &minv.m0, 16);
-        std::memcpy(r + 4, &minv.m1, 16);
-        std::memcpy(r + 8, &minv.m2, 16);
-        putInts(r, -2, (int)meshBase[ent[si].mesh], si, 0);
-    }
+    // top level over the world-space boxes
+    build_bvh2l_top(st, shapes, worldToLocal, rec.data(), &out.depth, out.topBox);
     for (int m = 0; m < numMeshes; ++m) {
         const ObjBvh& t = *trees[m];
-        const int base = (int)meshBase[m];
+        const int base = (int)st.meshBase[m];
         emitInternal(t, base, rec);
         const mcrt_shape& s = shapes[meshShape[m]];
         for (size_t p = 0; p < t.nodeBox.size(); ++p) {
@@ -448,9 +481,6 @@ bool build_bvh2l(const mcrt_shape* shapes, size_t nshapes, const uint32_t* indic
     out.topNodes = topN;
     out.numMeshes = numMeshes;
     out.numInstances = numShapesTop - numMeshes;
-    out.depth = top.height.load() + maxBottom + 1;   // + the return marker
-    out.topBox[0] = top.rootBox.lo[0]; out.topBox[1] = top.rootBox.lo[1]; out.topBox[2] = top.rootBox.lo[2];
-    out.topBox[3] = top.rootBox.hi[0]; out.topBox[4] = top.rootBox.hi[1]; out.topBox[5] = top.rootBox.hi[2];
     for (auto* t : trees) delete t;
     return true;
 }

@@ -117,6 +117,16 @@ struct mcrt_scene_s {
     size_t qUnits = 0;
     uint32_t qRoot = 0;
     bool hintAllocFailed = false;   // no memory for the table: hints stay off for this scene
+    // transform updates (mcrt_accel_update_transforms): the options of the last mcrt_accel_build
+    // (without its world_to_local pointer), the two-level build's refit state, the device top-level
+    // builder's arrays (made by the first update that takes the device path)
+    mcrt_accel_opts lastOpts = {};
+    bool haveOpts = false;
+    mcrt::Bvh2lTop top2l;
+    uint64_t topNodes = 0;
+    mcrt::TopBuildDev* topDev = nullptr;
+    int updatePath = 0;
+    double updateMs = 0.0;
 };
 
 // One frame in flight (PT): the per-frame buffers of mcrt_render_frame, its own stream and
@@ -688,6 +698,8 @@ static void scene_free_device(mcrt_scene s) {
     if (s->dQNodes) hipFree(s->dQNodes);
     s->dQNodes = nullptr;
     s->qUnits = 0;
+    mcrt::top_build_destroy(s->topDev);
+    s->topDev = nullptr;
     s->dSpill = nullptr;
     s->spillRays = 0;
     s->dScratch = nullptr;
@@ -865,6 +877,9 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
     const int bins = opts ? opts->num_bins : 64;
     const bool sah = opts ? opts->use_sah != 0 : true;
     if (bins < 2 || bins > 4096) return fail(ctx, MCRT_ERROR_INVALID_ARG, "num_bins out of range");
+    s->haveOpts = opts != nullptr;
+    if (opts && opts != &s->lastOpts) s->lastOpts = *opts;
+    s->lastOpts.world_to_local = nullptr;   // the caller's array, not kept
     auto t0 = std::chrono::steady_clock::now();
     size_t n = 0;
     for (auto& sh : s->shapes) n += sh.numTriangles;
@@ -877,8 +892,9 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
     if (use2) {
         int threads = (int)std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
         mcrt::Bvh2lOut b2;
+        const mcrt_mat4* w2l = opts ? opts->world_to_local : nullptr;
         if (!mcrt::build_bvh2l(s->shapes.data(), s->shapes.size(), s->indices.data(), s->positions.data(),
-                               opts ? opts->world_to_local : nullptr, cost, bins, sah, threads, b2))
+                               w2l, cost, bins, sah, threads, b2))
             return fail(ctx, MCRT_ERROR_INVALID_ARG, "two-level BVH build failed");
         hipSetDevice(ctx->device);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -894,6 +910,10 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
         s->twoLevel = true;
         s->numMeshes = b2.numMeshes;
         s->numInstances = b2.numInstances;
+        s->top2l = std::move(b2.top);
+        s->topNodes = b2.topNodes;
+        mcrt::top_build_destroy(s->topDev);   // sized for the previous top level
+        s->topDev = nullptr;
         return finish_accel(s, t0, b2.topBox);
     }
     s->twoLevel = false;
@@ -985,8 +1005,21 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
     return finish_accel(s, t0, nullptr);
 }
 
-// traversal scratch: overflow flag; per-ray spill columns deep enough for the tree
-// (allocated by ensure_spill for the largest launch)
+// per-ray spill columns deep enough for the tree (allocated by ensure_spill for the largest launch)
+static void apply_spill_cap(mcrt_scene s) {
+    int needCap = ((s->bvhDepth + 2 + 15) / 16) * 16;   // whole spill blocks of STACK_LDS entries
+    // test hook: MCRT_TEST_SPILL_CAP=k caps the spill columns at k entries (0 = LDS stack only) so a
+    // test can drive a traversal past its capacity and check that the overflow is reported
+    if (const char* tc = std::getenv("MCRT_TEST_SPILL_CAP")) needCap = std::max(0, std::atoi(tc) / 16 * 16);
+    if (needCap != s->spillCap) {
+        if (s->dSpill) hipFree(s->dSpill);
+        s->dSpill = nullptr;
+        s->spillRays = 0;
+        s->spillCap = needCap;
+    }
+}
+
+// traversal scratch: overflow flag, spill columns
 static mcrt_status finish_accel(mcrt_scene s, std::chrono::steady_clock::time_point t0, const float* box6) {
     mcrt_ctx ctx = s->ctx;
     // wave packets for the coherent launches (mcrt_traverse.h traversePacket): flat trees whose
@@ -1028,16 +1061,7 @@ static mcrt_status finish_accel(mcrt_scene s, std::chrono::steady_clock::time_po
             (void)hipGetLastError();
         }
     }
-    int needCap = ((s->bvhDepth + 2 + 15) / 16) * 16;   // whole spill blocks of STACK_LDS entries
-    // test hook: MCRT_TEST_SPILL_CAP=k caps the spill columns at k entries (0 = LDS stack only) so a
-    // test can drive a traversal past its capacity and check that the overflow is reported
-    if (const char* tc = std::getenv("MCRT_TEST_SPILL_CAP")) needCap = std::max(0, std::atoi(tc) / 16 * 16);
-    if (needCap != s->spillCap) {
-        if (s->dSpill) hipFree(s->dSpill);
-        s->dSpill = nullptr;
-        s->spillRays = 0;
-        s->spillCap = needCap;
-    }
+    apply_spill_cap(s);
     if (box6) {
         for (int a = 0; a < 3; ++a) { s->bbLo[a] = box6[a]; s->bbHi[a] = box6[3 + a]; }
         s->buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1061,6 +1085,106 @@ static mcrt_status finish_accel(mcrt_scene s, std::chrono::steady_clock::time_po
         }
     }
     s->buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return MCRT_OK;
+}
+
+// Shapes from which a top-level instance count the device builds the top tree when MCRT_TOP_BUILD
+// is unset (tools/refit_time.py -> profiles/refit/refit_time.json, "threshold")
+static constexpr size_t MCRT_TOP_DEVICE_MIN_SHAPES = 10000;
+
+// same shapes but for transforms and surface data; two-level: the mesh key must not move
+static bool same_topology(const mcrt_shape* a, const mcrt_shape* b, size_t n, bool twoLevel) {
+    for (size_t i = 0; i < n; ++i)
+        if (a[i].startIdx != b[i].startIdx || a[i].numTriangles != b[i].numTriangles ||
+            (twoLevel && a[i].startVertex != b[i].startVertex))
+            return false;
+    return true;
+}
+
+MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape* sh, uint32_t n,
+                                                  const mcrt_mat4* world_to_local) {
+    if (!s || !sh || n != s->shapes.size())
+        return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "shape count must not change");
+    mcrt_ctx ctx = s->ctx;
+    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
+    if (!same_topology(sh, s->shapes.data(), n, s->twoLevel))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "shape topology must not change");
+    const auto t0 = std::chrono::steady_clock::now();
+    hipSetDevice(ctx->device);
+    // after every launch that reads the records or the shapes: the context stream and the
+    // frame-slot streams of the context's frame buffers (as mcrt_ctx_synchronize reaches them)
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    auto done = [&](int path) {
+        s->updatePath = path;
+        s->updateMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        return MCRT_OK;
+    };
+    if (!s->twoLevel) {
+        // RR's flat intersector rebuilds on every Commit: the last build's options again
+        mcrt_status st = mcrt_scene_update_shapes(s, sh, n);
+        if (st != MCRT_OK) return st;
+        mcrt_accel_opts o = s->lastOpts;
+        o.world_to_local = world_to_local;
+        const bool had = s->haveOpts;
+        st = mcrt_accel_build(s, had ? &o : nullptr);
+        if (st != MCRT_OK) return st;
+        return done(3);
+    }
+    // the mesh keys are unchanged, so the surface records and their bases are too
+    s->shapes.assign(sh, sh + n);
+    HIPCHK(ctx, hipMemcpy(s->dShapes, sh, sizeof(mcrt_shape) * n, hipMemcpyHostToDevice));
+    const mcrt::Bvh2lTop& top = s->top2l;
+    const char* env = std::getenv("MCRT_TOP_BUILD");
+    const bool forceHost = env && std::strcmp(env, "host") == 0;
+    const bool forceDev = env && std::strcmp(env, "device") == 0;
+    bool device = forceDev || (!forceHost && top.world.size() >= MCRT_TOP_DEVICE_MIN_SHAPES);
+    std::string devWhy;
+    if (device && top.bins > 64) {   // as mcrt_sahbuild.hip
+        device = false;
+        devWhy = "the device top-level build supports 2..64 bins";
+    }
+    int depth = 0, path = 2;
+    float box[6];
+    if (device) {
+        hipError_t e = hipSuccess;
+        const char* why = nullptr;
+        void* dW2l = nullptr;
+        if (!s->topDev) e = mcrt::top_build_create(top, &s->topDev);
+        if (e == hipSuccess && world_to_local) e = upload(&dW2l, world_to_local, (size_t)n, ctx->stream);
+        if (e == hipSuccess)
+            e = mcrt::top_build_run(s->topDev, (const mcrt_shape*)s->dShapes, (const mcrt_mat4*)dW2l,
+                                    (float4*)s->dNodes, ctx->stream, &depth, box, &why);
+        if (dW2l) {
+            (void)hipStreamSynchronize(ctx->stream);
+            (void)hipFree(dW2l);
+        }
+        if (e == hipSuccess) {
+            path = 1;
+        } else if (e == hipErrorNotSupported || e == hipErrorInvalidValue || e == hipErrorOutOfMemory) {
+            (void)hipGetLastError();
+            devWhy = why ? why : hipGetErrorString(e);   // the host path below rewrites the records
+        } else {
+            return fail(ctx, MCRT_ERROR_DEVICE, std::string("device top-level build: ") + hipGetErrorString(e));
+        }
+    }
+    if (path == 2) {
+        std::vector<float> rec(16 * (size_t)s->topNodes);
+        mcrt::build_bvh2l_top(top, s->shapes.data(), world_to_local, rec.data(), &depth, box);
+        HIPCHK(ctx, hipMemcpy(s->dNodes, rec.data(), 64 * (size_t)s->topNodes, hipMemcpyHostToDevice));
+    }
+    s->bvhDepth = depth;
+    for (int a = 0; a < 3; ++a) { s->bbLo[a] = box[a]; s->bbHi[a] = box[3 + a]; }
+    apply_spill_cap(s);
+    done(path);
+    if (forceDev && path != 1) return fail(ctx, MCRT_ERROR_DEVICE, "MCRT_TOP_BUILD=device: " + devWhy);
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_accel_update_info(mcrt_scene s, int32_t* path, double* ms) {
+    if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
+    if (path) *path = s->updatePath;
+    if (ms) *ms = s->updateMs;
     return MCRT_OK;
 }
 
@@ -1103,9 +1227,9 @@ MCRT_API mcrt_status mcrt_accel_builder(mcrt_scene s, int32_t* builder) {
     return MCRT_OK;
 }
 
-MCRT_API mcrt_status mcrt_accel_build_host_records(const mcrt_scene_desc* d, const mcrt_accel_opts* opts,
-                                                   float* out_records, uint64_t max_records, uint64_t* num_records,
-                                                   int32_t* info) {
+static mcrt_status host_records(const mcrt_scene_desc* d, const mcrt_accel_opts* opts, const mcrt_shape* moved,
+                                const mcrt_mat4* moved_w2l, float* out_records, uint64_t max_records,
+                                uint64_t* num_records, int32_t* info) {
     if (!d || !d->shapes || !d->indices || !d->positions || !num_records)
         return fail(nullptr, MCRT_ERROR_INVALID_ARG, "invalid arguments");
     const float cost = opts ? opts->traversal_cost : 10.0f;
@@ -1129,6 +1253,9 @@ MCRT_API mcrt_status mcrt_accel_build_host_records(const mcrt_scene_desc* d, con
         if (!mcrt::build_bvh2l(d->shapes, d->num_shapes, d->indices, d->positions, opts ? opts->world_to_local : nullptr,
                                cost, bins, sah, threads, b2))
             return fail(nullptr, MCRT_ERROR_INVALID_ARG, "two-level BVH build failed");
+        if (moved) {   // mcrt_accel_refit_host_records: the refit's top level over the built one
+            mcrt::build_bvh2l_top(b2.top, moved, moved_w2l, b2.records.data(), &b2.depth, b2.topBox);
+        }
         *num_records = b2.numNodes;
         if (out_records) std::memcpy(out_records, b2.records.data(), 64 * std::min<uint64_t>(max_records, b2.numNodes));
         inf[1] = (int32_t)b2.topNodes;
@@ -1163,6 +1290,31 @@ MCRT_API mcrt_status mcrt_accel_build_host_records(const mcrt_scene_desc* d, con
     }
     if (info) std::memcpy(info, inf, sizeof(inf));
     return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_accel_build_host_records(const mcrt_scene_desc* d, const mcrt_accel_opts* opts,
+                                                   float* out_records, uint64_t max_records, uint64_t* num_records,
+                                                   int32_t* info) {
+    return host_records(d, opts, nullptr, nullptr, out_records, max_records, num_records, info);
+}
+
+MCRT_API mcrt_status mcrt_accel_refit_host_records(const mcrt_scene_desc* d, const mcrt_accel_opts* opts,
+                                                   const mcrt_shape* moved_shapes, const mcrt_mat4* moved_world_to_local,
+                                                   float* out_records, uint64_t max_records, uint64_t* num_records,
+                                                   int32_t* info) {
+    if (!d || !d->shapes || !moved_shapes) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "invalid arguments");
+    const bool use2 = (opts && opts->force_2level) ||
+                      (!(opts && opts->force_flat) && mcrt::shapes_are_instanced(d->shapes, d->num_shapes));
+    if (!same_topology(moved_shapes, d->shapes, d->num_shapes, use2))
+        return fail(nullptr, MCRT_ERROR_INVALID_ARG, "shape topology must not change");
+    if (use2) return host_records(d, opts, moved_shapes, moved_world_to_local, out_records, max_records, num_records, info);
+    // a flat structure is rebuilt: the fresh build of the moved shapes
+    mcrt_scene_desc md = *d;
+    md.shapes = moved_shapes;
+    mcrt_accel_opts o = {10.0f, 64, 1, 0, 0, 0, nullptr};   // mcrt_accel_build's defaults
+    if (opts) o = *opts;
+    o.world_to_local = moved_world_to_local;
+    return host_records(&md, &o, nullptr, nullptr, out_records, max_records, num_records, info);
 }
 
 // ---------------------------------------------------------------------------

@@ -267,16 +267,42 @@ void free_bvh(BvhOut& out);
 }  // namespace mcrt
 // Host two-level (instanced) build (mcrt_bvh2l.cpp)
 namespace mcrt {
+// What a transform-only refit of the top level needs from the build (RR keeps the same across
+// its Refit branch, intersector_2level.cpp:495-660: the shape order and the per-mesh trees)
+struct Bvh2lTop {
+    std::vector<int32_t> world;       // top-level shapes in world order (after the meshes-first partition)
+    std::vector<int32_t> meshOf;      // mesh of world[i]
+    std::vector<uint32_t> meshBase;   // first record of each mesh's tree
+    std::vector<float> meshBox;       // Bvh::Bounds of each mesh's tree (lo xyz, hi xyz)
+    int maxBottom = 0;                // height of the deepest mesh tree
+    float cost = 10.0f;
+    int bins = 64;
+    bool sah = true;
+};
 struct Bvh2lOut {
     std::vector<float> records;   // 16 floats per record
     std::size_t numNodes = 0, topNodes = 0;
     int numMeshes = 0, numInstances = 0;
     int depth = 0;                // deepest top + bottom path (+ the return marker)
     float topBox[6] = {};         // world bounds (lo xyz, hi xyz)
+    Bvh2lTop top;
 };
 // true when two shapes share (startIdx, startVertex, numTriangles): RTScene::attachMesh then
 // creates RadeonRays instances and RR switches to its two-level intersector
 bool shapes_are_instanced(const mcrt_shape* shapes, std::size_t n);
 bool build_bvh2l(const mcrt_shape* shapes, std::size_t nshapes, const uint32_t* indices, const mcrt_float4* positions,
                  const mcrt_mat4* worldToLocal, float cost, int bins, bool sah, int threads, Bvh2lOut& out);
+// The top level alone, from the build's state and the shapes' current transforms: records
+// [0, 2 * world.size() - 1) into `records` (16 floats each), the structure's depth and world box.
+// build_bvh2l's own top level comes from here, so a refit equals a fresh build.
+void build_bvh2l_top(const Bvh2lTop& top, const mcrt_shape* shapes, const mcrt_mat4* worldToLocal, float* records,
+                     int* depth, float* topBox);
+// The same top level built on the device (mcrt_topbuild.hip), written straight into nodes[0, topNodes)
+struct TopBuildDev;
+hipError_t top_build_create(const Bvh2lTop& top, TopBuildDev** out);
+void top_build_destroy(TopBuildDev* d);
+// dWorldToLocal may be NULL; hipErrorNotSupported / hipErrorInvalidValue (*why names the reason):
+// the input is one the device path does not take and the records are unspecified
+hipError_t top_build_run(TopBuildDev* d, const mcrt_shape* dShapes, const mcrt_mat4* dWorldToLocal, float4* nodes,
+                         hipStream_t st, int* depth, float* topBox, const char** why);
 }  // namespace mcrt

@@ -44,6 +44,9 @@ SIGNATURES = {
     "mcrt_scene_update_materials": (_c.c_int, [_vp, _vp, _c.c_uint32]),
     "mcrt_scene_update_shapes": (_c.c_int, [_vp, _vp, _c.c_uint32]),
     "mcrt_accel_build": (_c.c_int, [_vp, _vp]),
+    "mcrt_accel_update_transforms": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp]),
+    "mcrt_accel_update_info": (_c.c_int, [_vp, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_double)]),
+    "mcrt_accel_refit_host_records": (_c.c_int, [_vp, _vp, _vp, _vp, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64), _vp]),
     "mcrt_accel_info": (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mcrt_accel_layout": (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mcrt_accel_builder": (_c.c_int, [_vp, _vp]),
@@ -261,6 +264,24 @@ def build_host_records(scene, **opts):
                  "meshes": int(info[3])}
 
 
+def refit_host_records(scene, moved_shapes, world_to_local=None, **opts):
+    """Host-only refit (no GPU): builds `scene`, then brings its structure up to date for
+    moved_shapes (mcrt_accel_refit_host_records); world_to_local belongs to the moved shapes.
+    Returns what build_host_records does."""
+    desc = scene.desc()
+    o = accel_opts(**opts)
+    moved = np.ascontiguousarray(moved_shapes)
+    w2l = None if world_to_local is None else np.ascontiguousarray(world_to_local, np.float32)
+    n = _c.c_uint64()
+    f = lib().mcrt_accel_refit_host_records
+    _check(f(_c.byref(desc), _c.byref(o), _p(moved), _p(w2l), None, 0, _c.byref(n), None))
+    rec = np.zeros((n.value, 16), np.float32)
+    info = np.zeros(4, np.int32)
+    _check(f(_c.byref(desc), _c.byref(o), _p(moved), _p(w2l), _p(rec), n.value, _c.byref(n), _p(info)))
+    return rec, {"two_level": int(info[0]), "top_records": int(info[1]), "depth": int(info[2]),
+                 "meshes": int(info[3])}
+
+
 class DeviceScene:
     def __init__(self, ctx, scene, build=True, cost=10.0, bins=64, sah=True, device_build=False,
                  force_2level=False, force_flat=False, world_to_local=None):
@@ -316,6 +337,20 @@ class DeviceScene:
         """mcrt_scene_update_shapes (same topology; call build() after a transform change)."""
         self._shapes = np.ascontiguousarray(shapes)
         _check(lib().mcrt_scene_update_shapes(self.h, _p(self._shapes), len(self._shapes)), self.ctx.h)
+
+    def update_transforms(self, shapes, world_to_local=None):
+        """mcrt_accel_update_transforms: the moved shapes (same topology) replace the scene's and
+        the acceleration structure follows -- two-level: the top level alone is rebuilt."""
+        self._shapes = np.ascontiguousarray(shapes)
+        w2l = None if world_to_local is None else np.ascontiguousarray(world_to_local, np.float32)
+        _check(lib().mcrt_accel_update_transforms(self.h, _p(self._shapes), len(self._shapes), _p(w2l)), self.ctx.h)
+
+    def update_info(self):
+        """The last update_transforms: path 0 none yet, 1 top level built on the device, 2 on the
+        host, 3 full rebuild; ms its wall time (mcrt_accel_update_info)."""
+        path, ms = _c.c_int32(), _c.c_double()
+        _check(lib().mcrt_accel_update_info(self.h, _c.byref(path), _c.byref(ms)), self.ctx.h)
+        return {"path": path.value, "ms": ms.value}
 
     def trace_closest(self, rays_dev_ptr, n, hits_dev_ptr):
         _check(lib().mcrt_trace_closest(self.h, rays_dev_ptr, n, hits_dev_ptr), self.ctx.h)

@@ -1,0 +1,53 @@
+"""Runs every tests/test_gpu_refit.py case that forces the top-level build path: the library reads
+MCRT_TOP_BUILD from its environment, so each forced run is a process of its own.
+
+usage: MCRT_TOP_BUILD=device|host python tests/refit_job.py OUT.npz
+Per case: the records after mcrt_accel_update_transforms, whether the records beyond the top level
+kept their bytes, the depth and the update path; for the cases with rays, the closest / any hits of
+the updated scene and of a fresh scene of the moved shapes.
+"""
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "monte-carlo-raytracer_amd"))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from refit_util import FORCED_CASES, forced_case, trace  # noqa: E402
+
+
+def main(out_path):
+    import torch
+    from clref_job import tl_rays
+    from mcrt import lib
+    assert torch.cuda.is_available()   # torch's runtime first, as in the test process
+    ctx = lib.Context(0)
+    res = {}
+    for name in FORCED_CASES:
+        sc, moved, rays = forced_case(name)
+        ds = lib.DeviceScene(ctx, sc, force_2level=True)
+        before = ds.records()
+        ds.update_transforms(moved.shapes)
+        after = ds.records()
+        top = 2 * len(sc.shapes) - 1
+        res[f"{name}_top"] = after[:top]
+        res[f"{name}_tail_kept"] = np.array(after[top:].tobytes() == before[top:].tobytes())
+        res[f"{name}_depth"] = np.array(ds.layout()["depth"])
+        res[f"{name}_path"] = np.array(ds.update_info()["path"])
+        if rays:
+            r = tl_rays(moved, 20000)
+            fresh = lib.DeviceScene(ctx, moved, force_2level=True)
+            for tag, d in (("upd", ds), ("fresh", fresh)):
+                res[f"{name}_{tag}_closest"] = trace(d, r).view(np.uint8)
+                res[f"{name}_{tag}_any"] = trace(d, r, True)
+            fresh.close()
+        ds.close()
+    ctx.close()
+    np.savez(out_path, **res)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1])
