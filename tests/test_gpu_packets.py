@@ -5,10 +5,13 @@ them nearer-first (the wave revisits the first child for the lanes that preferre
 every lane tests the nodes of the per-ray traversal in the per-ray order: results must be BIT-
 IDENTICAL to MCRT_CAMERA_PACKETS=0 (every launch per ray), ties included.  Compared here: single
 frames, batched TAA calls (packed waves), band splits, BDPT vertices, a one-triangle tree (the root
-is a leaf) and the camera AOV pass; the full-size reference tests run with packets on."""
+is a leaf), the camera AOV pass and an axis-aligned camera in a box-face plane of the lattice scene
+(exactly zero direction components: the octant instantiations traversePacketOct<., 0..7> at their
+edges); the full-size reference tests run with packets on."""
 import numpy as np
 import pytest
 
+import ray_truth
 from mcrt import scenes
 from mcrt import types as T
 from mcrt.camera import scene_camera
@@ -127,3 +130,55 @@ def test_packets_single_triangle_and_aov(hip_ctx, monkeypatch):
         ds.close()
     _same(out[True], out[False], "one triangle")
     assert (out[False][0][..., :3] > 0).any()
+
+
+def _axis_camera(pos, n=64):
+    """A hand-filled camera record looking along +z whose corner rays are symmetric about the axis:
+    the rays of column n / 2 have d.x = mix(-a, a, 0.5) = 0 and those of row n / 2 d.y = 0, exactly
+    (n a power of two: u = x * (1 / n) is exact), and the centre pixel's ray is (0, 0, 1)."""
+    a = np.float32(0.5)
+    cam = np.zeros(1, T.CAMERA_DTYPE)
+    cam["worldToClip"] = np.eye(4, dtype=np.float32)
+    cam["r00"][0, :3] = (-a, -a, 1.0)
+    cam["r10"][0, :3] = (a, -a, 1.0)
+    cam["r11"][0, :3] = (a, a, 1.0)
+    cam["r01"][0, :3] = (-a, a, 1.0)
+    cam["pos"][0, :3] = pos
+    cam["direction"][0, :3] = (0.0, 0.0, 1.0)
+    cam["width"] = cam["height"] = n
+    cam["area"] = 1.0
+    u = np.float32(n // 2) * (np.float32(1.0) / np.float32(n))
+    assert -a + (a - -a) * u == 0.0
+    return cam
+
+
+@pytest.mark.parametrize("offset", [0.0, 1000.0])
+@pytest.mark.parametrize("batch", [1, 4])
+def test_packets_axis_camera_in_face_plane(hip_ctx, monkeypatch, offset, batch):
+    """The lattice scene (tests/ray_truth.py edge_scene: box faces in shared planes at binary
+    fractions) seen from points IN those planes: the central column travels inside the plane
+    x = 0.5 (or -0.5, 1, -2), the central row inside y = -0.5 (...), edge-on to every face there;
+    the directional light is axis parallel too, so the bounce-0 shadow packets have two zero
+    components.  At the origin and 1000 units away (all coordinates stay exact in float32)."""
+    from mcrt import lib
+    sc = ray_truth.edge_scene((offset, offset, offset), lights=True)
+    planes = [(0.5, -0.5), (-0.5, 1.0), (1.0, -2.0), (-2.0, 0.5)]
+    cams = [_axis_camera((x + offset, y + offset, -4.0 + offset)) for x, y in planes[:batch]]
+    out = {}
+    for on in (False, True):
+        _with_packets(monkeypatch, on)
+        ds = lib.DeviceScene(hip_ctx, sc)
+        fb = lib.FrameBuffer(hip_ctx, 64, 64)
+        if batch == 1:
+            fb.render(ds, cams[0], frame=0, max_depth=3)
+            res = [fb.read(0)]
+        else:
+            fb.render_frames(ds, cams, frame=0, max_depth=3)
+            res = [fb.read_frame(k) for k in range(batch)]
+        res.append(fb.render_aov(ds, cams[0], T.AOV_ALBEDO))
+        out[on] = res
+        fb.close()
+        ds.close()
+    _same(out[True], out[False], f"axis camera offset={offset} batch={batch}")
+    for img in out[False]:
+        assert np.isfinite(img).all() and (img[..., :3] > 0).mean() > 0.1   # lit surfaces, not an empty frame
