@@ -510,8 +510,73 @@ MCRT_API mcrt_status mcrt_postprocess(mcrt_framebuffer fb, const mcrt_postproces
 #define MCRT_AOV_TEXTURE_LOD 1
 MCRT_API mcrt_status mcrt_render_aov(mcrt_scene scene, mcrt_framebuffer fb, const mcrt_camera* camera,
                                      const mcrt_frame_params* params, int aov, float* host_out);
+/* ---- Guide-buffer-driven denoiser (opt-in; nothing below changes any other call's output) ----
+ *
+ * An edge-avoiding a-trous wavelet filter (Dammertz et al. 2010) over the accumulated image,
+ * steered by geometry guides captured at the camera-ray hits and, optionally, by a per-pixel
+ * variance estimated from luminance moments accumulated next to the image (as in SVGF).
+ *
+ * Guides: two float4 planes of W*H records owned by the frame buffer (allocated on first use).
+ *   normal-plane  (n.x, n.y, n.z, n . (P - cam.pos)): n the interpolated shading normal before
+ *                 normal mapping, flipped to face the camera, P the hit point; the plane offset
+ *                 is camera-relative so that a scene far from the origin loses nothing
+ *   albedo-depth  (Kd.rgb, |P - cam.pos|): Kd exactly MCRT_AOV_ALBEDO's (honours texture_lod)
+ * A miss holds (0,0,0,0) and (0,0,0,-1).
+ *
+ * mcrt_render_guides traces the camera rays of `camera` (mcrt_render_aov's path: it waits for the
+ * frame slots and reuses the bound slot's camera and primary-hit buffers) and writes the guides of
+ * the rows the band fields of params select; other rows keep their content.  Everything stays on
+ * the device, enqueued on the context stream.  mcrt_framebuffer_set_guides installs both planes
+ * from device memory instead (tests, other renderers). */
+MCRT_API mcrt_status mcrt_render_guides(mcrt_scene scene, mcrt_framebuffer fb, const mcrt_camera* camera,
+                                        const mcrt_frame_params* params);
+MCRT_API mcrt_status mcrt_framebuffer_set_guides(mcrt_framebuffer fb, const void* d_normal_plane,
+                                                 const void* d_albedo_depth);
+/* Luminance moments.  While enabled, mcrt_accumulate / mcrt_accumulate_frames also update, for
+ * the pixels of the band and per frame of the batch in frame order,
+ *   l = (0.212671f*r + 0.715160f*g) + 0.072169f*b,  m1 += l,  m2 += l*l
+ * with r, g, b the radiance clamped to [0, 1000] as the accumulation clamps it; frame_index 0
+ * overwrites both and restarts the frame count.  The moments are UNWEIGHTED: the reconstruction
+ * filter weight (one number per frame) is deliberately not applied, they describe the samples.
+ * Enabling allocates and zeroes the plane (0 frames); disabling keeps it.
+ * mcrt_framebuffer_set_moments installs (m1, m2) float2 records of `frames` frames from device
+ * memory. */
+MCRT_API mcrt_status mcrt_framebuffer_set_moments_enabled(mcrt_framebuffer fb, int on);
+MCRT_API mcrt_status mcrt_framebuffer_set_moments(mcrt_framebuffer fb, const void* d_m1m2, int32_t frames);
+/* Reads guide data back: which 0 normal-plane (float4), 1 albedo-depth (float4), 2 moments
+ * (float2), 3 the filtered variance of the last mcrt_denoise_guided (float).  *needed (may be
+ * NULL) receives the byte size; host_dst may be NULL to query it; otherwise bytes must be >= it.
+ * MCRT_ERROR_NOT_READY when the plane does not exist yet. */
+MCRT_API mcrt_status mcrt_framebuffer_read_guides(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                  uint64_t* needed);
+/* The filter: image -> display image (mcrt_framebuffer_read which = 3), enqueued on the context
+ * stream after the last accumulate.  Level i = 0 .. levels-1 has step s = 2^i and the 25 taps
+ * q = p + s*(dx, dy), dx, dy in -2..2 (taps outside the image are skipped), h = [1/16, 1/4, 3/8, 1/4, 1/16]:
+ *   e  = |n_p - n_q|^2 / sigma_normal^2 + (d_p - d_q)^2 / (sigma_depth * z_p)^2
+ *        + (l_p - l_q)^2 / (sigma_i^2 * v_p + 1e-8)
+ *   w  = h[dx] h[dy] expf(-e);   c' = sum w c_q / sum w;   var' = sum w^2 var_q / (sum w)^2
+ * d the plane offset, z_p the centre's depth (1 on a miss), l the luminance of the level's input.
+ * With use_variance and moments of n >= 2 frames: var0 = max(0, m2/n - (m1/n)^2) / (n - 1),
+ * v_p = the 3x3 Gaussian of var around p, sigma_i = sigma_luminance; otherwise var = 1, v_p = 1 and
+ * sigma_i = sigma_luminance * 2^-i.  With demodulate_albedo the filter runs on image / albedo
+ * (channels with albedo <= 1e-3 are left alone) and multiplies the albedo back after the last
+ * level.  Alpha passes through.  mcrt_postprocess and its denoised image are not touched.
+ * MCRT_ERROR_NOT_READY without guides or with a band-split BDPT frame pending; under a band split
+ * run it on the gathering rank after mcrt_framebuffer_bands_unpack, with guides that rank renders
+ * whole-image (moments are not gathered: var = 1). */
+typedef struct {
+    int32_t levels;             /* 1..8; default 5 (steps 1,2,4,8,16) */
+    float   sigma_normal;       /* default 0.1 */
+    float   sigma_depth;        /* default 0.02, relative to the centre pixel's depth */
+    float   sigma_luminance;    /* default 4.0 (in standard deviations when variance is used) */
+    int32_t use_variance;       /* 1: guide the luminance weight by the moments when >= 2 frames are in them */
+    int32_t demodulate_albedo;  /* 1: filter image / albedo, multiply back after the last level */
+    int32_t use_tonemapping;    /* then k_tonemap, as mcrt_postprocess */
+    float   min_luminance;
+} mcrt_guided_denoise_params;
+MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_denoise_params* params);
 /* Copies device -> host (RGBA32F, W*H*4 floats).  which: 0 radiance, 1 weighted sum, 2 image,
- * 3 display image (mcrt_postprocess). */
+ * 3 display image (mcrt_postprocess, mcrt_denoise_guided). */
 MCRT_API mcrt_status mcrt_framebuffer_read(mcrt_framebuffer fb, int which, float* host_rgba);
 /* Radiance of frame k (0 <= k < count) of the last mcrt_render_frames call (k = 0: the same as
  * mcrt_framebuffer_read 0): the reference's RadianceBufferCL of that frame

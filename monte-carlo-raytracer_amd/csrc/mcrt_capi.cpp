@@ -35,15 +35,21 @@ void set_last_error(const std::string& msg) { g_lastError = msg; }
 namespace {
 
 #define MCRT_MAX_BOUNCES 32
+#define MCRT_ATROUS_MAX_LEVELS 8
 
 enum KernelId {
     K_PRIMARY, K_SHADE0, K_SHADEN, K_SHADOW, K_EXTEND, K_ACCUM, K_TRACE_CLOSEST, K_TRACE_ANY,
-    K_BDPT_START, K_BDPT_VERTEX, K_BDPT_CONNECT, K_BDPT_VIS, K_BDPT_GATHER, K_SHADOW_EXTEND, K_COUNT
+    K_BDPT_START, K_BDPT_VERTEX, K_BDPT_CONNECT, K_BDPT_VIS, K_BDPT_GATHER, K_SHADOW_EXTEND,
+    K_GUIDES, K_MOMENTS, K_ATROUS_PREP,
+    K_ATROUS,   // one entry per level: K_ATROUS + i is the launch of step 2^i
+    K_COUNT = K_ATROUS + MCRT_ATROUS_MAX_LEVELS
 };
 const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN",       "k_shadow",   "k_extend",
                                      "k_accumulate", "k_trace_closest", "k_trace_any",  "k_bdpt_start",
                                      "k_bdpt_vertex", "k_bdpt_connect", "k_bdpt_vis",   "k_bdpt_gather",
-                                     "k_shadow_extend"};
+                                     "k_shadow_extend", "k_guides",      "k_moments",    "k_atrous_prep",
+                                     "k_atrous_s1",   "k_atrous_s2",   "k_atrous_s4",  "k_atrous_s8",
+                                     "k_atrous_s16",  "k_atrous_s32",  "k_atrous_s64", "k_atrous_s128"};
 
 }  // namespace
 
@@ -248,6 +254,18 @@ struct mcrt_framebuffer_s {
     bool bdptPendingGather = false;   // band-split BDPT frame waiting for the ranks' summed splats
     int splatExchange = MCRT_SPLAT_EXCHANGE_DENSE;   // mcrt_framebuffer_set_splat_exchange
     int bdptSet = 0;             // the BDPT set of the last BDPT call
+    // Guided denoiser (mcrt_denoise_guided), every plane allocated on first use: the guides of the
+    // camera-ray hits, the luminance moments k_moments keeps next to the image, and two scratch
+    // colour / variance planes the levels ping-pong between (fb->denoised stays mcrt_postprocess's)
+    float4* guideNormal = nullptr;   // (n, n . (P - cam.pos))
+    float4* guideAlbedo = nullptr;   // (Kd, |P - cam.pos|), -1 on a miss
+    bool haveGuides = false;
+    float2* moments = nullptr;       // (sum l, sum l*l)
+    bool momentsOn = false;
+    int momentFrames = 0;            // frames in the moments (host side; restarts at frame_index 0)
+    float4* atrousC[2] = {};
+    float* atrousV[2] = {};
+    float* filteredVar = nullptr;    // the last level's variance (one of atrousV), NULL before a denoise
 };
 
 // BDPT queue counters (64 ints per frame set): [d] the subpath-ray queue of depth d (d <= 33;
@@ -1439,7 +1457,8 @@ static void fb_free(mcrt_framebuffer fb) {
         if (w) hipFree(w);
         w = nullptr;
     }
-    void* ptrs[] = {fb->wsum, fb->wts, fb->image, fb->denoised, fb->display, fb->hintPix};
+    void* ptrs[] = {fb->wsum, fb->wts, fb->image, fb->denoised, fb->display, fb->hintPix, fb->guideNormal,
+                    fb->guideAlbedo, fb->moments, fb->atrousC[0], fb->atrousC[1], fb->atrousV[0], fb->atrousV[1]};
     for (void* p : ptrs)
         if (p) hipFree(p);
     fb_free_bdpt(fb);
@@ -2241,6 +2260,11 @@ static mcrt_status accumulate(mcrt_framebuffer fb, const mcrt_filter* filters, i
         mcrt::launch_accumulate(f, frame_index, dFilt, nfilters == 1 ? 0 : 1, fb->radiance, fb->wsum, fb->wts, fb->image,
                                 ctx->stream);
     }
+    if (fb->momentsOn) {   // the same frames' luminance moments, before the slot is released
+        Timed t(ctx, K_MOMENTS, nullptr, (int64_t)f.numTiles * 64 * batch);
+        mcrt::launch_moments(f, frame_index, fb->radiance, fb->moments, ctx->stream);
+        fb->momentFrames = frame_index == 0 ? batch : fb->momentFrames + batch;
+    }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(slot.free, ctx->stream));   // the slot may take its next frame
     return MCRT_OK;
@@ -2284,6 +2308,159 @@ MCRT_API mcrt_status mcrt_postprocess(mcrt_framebuffer fb, const mcrt_postproces
         mcrt::launch_tonemap(W * H, p->min_luminance, src, fb->display, ctx->stream);
     else
         HIPCHK(ctx, hipMemcpyAsync(fb->display, src, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipGetLastError());
+    return MCRT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Guided denoiser: guides, moments, a-trous filter (mcrt_denoise.hip)
+// ---------------------------------------------------------------------------
+// Allocates *p (bytes, zero-filled on the context stream) when it does not exist yet.
+static hipError_t ensure_plane(mcrt_ctx ctx, void** p, size_t bytes) {
+    if (*p) return hipSuccess;
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, ctx->stream);
+    return e;
+}
+static hipError_t ensure_guides(mcrt_framebuffer fb) {
+    hipError_t e = ensure_plane(fb->ctx, (void**)&fb->guideNormal, 16 * fb->N);
+    if (e == hipSuccess) e = ensure_plane(fb->ctx, (void**)&fb->guideAlbedo, 16 * fb->N);
+    return e;
+}
+
+MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
+                                        const mcrt_frame_params* p) {
+    if (!s || !fb || !cam || !p) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = s->ctx;
+    if (fb->ctx != ctx) return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame buffer belongs to another context");
+    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
+    if (cam->width != fb->W || cam->height != fb->H)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
+    FrameArgs f;
+    std::string err;
+    if (!frame_args(fb, p, f, err)) return fail(ctx, MCRT_ERROR_INVALID_ARG, err);
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, ensure_guides(fb));
+    ctx_wait_slots(fb);   // as mcrt_render_aov: the bound slot's camera and primary-hit buffers are reused
+    mcrt_camera* dCam = reinterpret_cast<mcrt_camera*>(fb->counters + 128);
+    HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera), hipMemcpyHostToDevice, st));
+    if (!ensure_spill(s, std::max((size_t)f.numTiles * 64, 2 * fb->N + 64)))
+        return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "traversal spill buffer");
+    const TraceCtx tcs = packet_ctx(s);
+    mcrt::launch_primary(tcs, f, dCam, fb->hitsP, st);
+    {
+        Timed t(ctx, K_GUIDES, nullptr, (int64_t)f.numTiles * 64);
+        mcrt::launch_guides(scene_args(s), f, dCam, fb->hitsP, fb->guideNormal, fb->guideAlbedo, st);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    // the slot's next render (its own stream) may overwrite those buffers only after this pass
+    HIPCHK(ctx, hipEventRecord(fb->slot[fb->cur].free, st));
+    fb->haveGuides = true;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_guides(mcrt_framebuffer fb, const void* d_normal_plane,
+                                                 const void* d_albedo_depth) {
+    if (!fb || !d_normal_plane || !d_albedo_depth) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, ensure_guides(fb));
+    HIPCHK(ctx, hipMemcpyAsync(fb->guideNormal, d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->guideAlbedo, d_albedo_depth, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    fb->haveGuides = true;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_moments_enabled(mcrt_framebuffer fb, int on) {
+    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
+    mcrt_ctx ctx = fb->ctx;
+    hipSetDevice(ctx->device);
+    if (on && !fb->moments) {
+        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->moments, 8 * fb->N));
+        fb->momentFrames = 0;
+    }
+    fb->momentsOn = on != 0;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_moments(mcrt_framebuffer fb, const void* d_m1m2, int32_t frames) {
+    if (!fb || !d_m1m2 || frames < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    mcrt_ctx ctx = fb->ctx;
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->moments, 8 * fb->N));
+    HIPCHK(ctx, hipMemcpyAsync(fb->moments, d_m1m2, 8 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    fb->momentFrames = frames;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_read_guides(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                  uint64_t* needed) {
+    if (!fb || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    mcrt_ctx ctx = fb->ctx;
+    const void* src = which == 0 ? (const void*)fb->guideNormal : which == 1 ? (const void*)fb->guideAlbedo
+                      : which == 2 ? (const void*)fb->moments : (const void*)fb->filteredVar;
+    const uint64_t need = (which < 2 ? 16 : which == 2 ? 8 : 4) * (uint64_t)fb->N;
+    if (needed) *needed = need;
+    if (!host_dst) return MCRT_OK;
+    if (!src) return fail(ctx, MCRT_ERROR_NOT_READY, "no such guide data yet");
+    if (bytes < need) return fail(ctx, MCRT_ERROR_INVALID_ARG, "destination too small");
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, fb_sync(fb));
+    HIPCHK(ctx, hipMemcpy(host_dst, src, need, hipMemcpyDeviceToHost));
+    return MCRT_OK;
+}
+
+// Largest step whose level runs the tile-staged kernel (36 KB of LDS at step 4); larger steps read
+// their taps from memory.  MCRT_ATROUS_LDS_MAX_STEP overrides it (0: never stage) for measurements
+// and the test that both kernels agree bit for bit.
+static int atrous_lds_max_step() {
+    const char* e = std::getenv("MCRT_ATROUS_LDS_MAX_STEP");
+    const int v = e ? std::atoi(e) : 4;
+    return std::min(std::max(v, 0), 8);   // step 8: 48 x 48 x 36 B = 81 KB does not fit 64 KB
+}
+
+MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p) {
+    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    if (p->levels < 1 || p->levels > MCRT_ATROUS_MAX_LEVELS)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "levels must be 1 .. 8");
+    if (!(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f) || !(p->sigma_luminance > 0.0f))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "sigmas must be positive");
+    if (!fb->haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
+    if (fb->bdptPendingGather)
+        return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const int W = (int)fb->W, H = (int)fb->H;
+    for (int i = 0; i < 2; ++i) {
+        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->atrousC[i], 16 * fb->N));
+        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->atrousV[i], 4 * fb->N));
+    }
+    const bool useVar = p->use_variance && fb->moments && fb->momentFrames >= 2;
+    const int demod = p->demodulate_albedo ? 1 : 0;
+    {
+        Timed t(ctx, K_ATROUS_PREP, nullptr, (int64_t)fb->N);
+        mcrt::launch_atrous_prep((int)fb->N, fb->image, fb->guideAlbedo, useVar ? fb->moments : nullptr, fb->momentFrames,
+                                 demod, fb->atrousC[0], fb->atrousV[0], st);
+    }
+    const int ldsMax = atrous_lds_max_step();
+    int src = 0;
+    for (int i = 0; i < p->levels; ++i) {
+        const int step = 1 << i;
+        const bool last = i + 1 == p->levels;
+        // the last level writes the display image, or the other scratch plane when k_tonemap follows
+        float4* cOut = last && !p->use_tonemapping ? fb->display : fb->atrousC[src ^ 1];
+        const float sigmaLevel = useVar ? p->sigma_luminance : p->sigma_luminance * std::ldexp(1.0f, -i);
+        const bool lds = step <= ldsMax && mcrt::atrous_lds_bytes(step) <= 64 * 1024;
+        Timed t(ctx, K_ATROUS + i, nullptr, (int64_t)fb->N);
+        mcrt::launch_atrous(W, H, step, lds, p->sigma_normal, p->sigma_depth, sigmaLevel, useVar ? 1 : 0,
+                            last && demod ? 1 : 0, fb->atrousC[src], fb->guideNormal, fb->guideAlbedo, fb->atrousV[src],
+                            cOut, fb->atrousV[src ^ 1], st);
+        src ^= 1;
+    }
+    fb->filteredVar = fb->atrousV[src];
+    if (p->use_tonemapping) mcrt::launch_tonemap(W * H, p->min_luminance, fb->atrousC[src], fb->display, st);
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
 }

@@ -181,6 +181,19 @@ void launch_shadeN(const SceneArgs& s, const FrameArgs& f, int bounce, const int
                    int maxCount, hipStream_t st);
 void launch_aov(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits, int which,
                 float4* out, hipStream_t st);
+// denoiser guides at the camera-ray hits (k_guides): the band's rows of the two W*H planes
+void launch_guides(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
+                   float4* normalPlane, float4* albedoDepth, hipStream_t st);
+// mcrt_denoise.hip: the luminance moments (sum l, sum l*l) of the frames k_accumulate just added
+void launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st);
+// the a-trous filter's level-0 input (moments NULL: variance 1) and one level of step `step`
+// (lds: the tile-staged kernel, for steps whose atrous_lds_bytes fit; same bits either way)
+void launch_atrous_prep(int n, const float4* image, const float4* albedoDepth, const float2* moments, int frames,
+                        int demod, float4* cOut, float* vOut, hipStream_t st);
+size_t atrous_lds_bytes(int step);
+void launch_atrous(int W, int H, int step, bool lds, float sigmaNormal, float sigmaDepth, float sigmaLevel, int useVar,
+                   int remodulate, const float4* cIn, const float4* normalPlane, const float4* albedoDepth,
+                   const float* vIn, float4* cOut, float* vOut, hipStream_t st);
 // filters: the reconstruction filter of each batch frame in device memory (KRN/kernel_data.h:63-80), k_accumulate
 // evaluates its weight like ReconstructionPass (reconstruction.cl:21-42); filterStride 0 = one filter for all frames
 void launch_accumulate(const FrameArgs& f, int frame, const mcrt_filter* filters, int filterStride, const float4* radiance, float4* wsum, float* wts,

@@ -716,6 +716,47 @@ __global__ __launch_bounds__(256) void k_aov(SceneArgs s, FrameArgs f, const mcr
     }
 }
 
+// Denoiser guides of the camera-ray hits (mcrt_render_guides), tile order and albedo as k_aov:
+//   normalPlane = (n, n . (P - cam.pos)), n = the interpolated shading normal before normal
+//                 mapping, flipped to face the camera; the plane offset is camera-relative so a
+//                 scene far from the origin keeps its precision
+//   albedoDepth = (MCRT_AOV_ALBEDO's Kd, |P - cam.pos|)
+// A miss writes (0, 0, 0, 0) and (0, 0, 0, -1).  Band rows only.
+__global__ __launch_bounds__(256) void k_guides(SceneArgs s, FrameArgs f, const mcrt_camera* __restrict__ camp,
+                                                const float4* __restrict__ hits, float4* __restrict__ normalPlane,
+                                                float4* __restrict__ albedoDepth) {
+    const int lane = threadIdx.x & 63;
+    const int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    int x, y;
+    if (tile >= f.numTiles || !tilePixel(f, tile, lane, x, y)) return;
+    const int pix = y * (int)f.W + x;
+    const float4 hit = hits[hitSlot(f, tile, lane, 0, x, y)];
+    const int shapeIdx = __float_as_int(hit.z), primIdx = __float_as_int(hit.w);
+    if (shapeIdx < 0) {
+        normalPlane[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        albedoDepth[pix] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        return;
+    }
+    const mcrt_camera& cam = *camp;
+    f3 dpdu, dpdv, dx, dy;
+    const Frame si = computeSurfaceInteraction(s, shapeIdx, primIdx, f2{hit.x, hit.y}, &dpdu, &dpdv);
+    cameraDiffDirs(cam, x, y, dx, dy);
+    TexLod L = surfaceUVDifferentials(si, dpdu, dpdv, ld3(cam.pos), dx, dy);
+    L.on = f.textureLod != 0;
+    f3 kd = f3{0.0f, 0.0f, 0.0f};
+    const int materialId = s.shapes[shapeIdx].materialId;
+    if (materialId != -1 && s.materials[materialId].type == 0) kd = uberProps(s, s.materials[materialId], si.uv, L).Kd;
+    const f3 v = si.p - ld3(cam.pos);
+    f3 n = si.sn;
+    float off = cl_dot(n, v);
+    if (off > 0.0f) {
+        n = f3{-n.x, -n.y, -n.z};
+        off = -off;
+    }
+    normalPlane[pix] = make_float4(n.x, n.y, n.z, off);
+    albedoDepth[pix] = make_float4(kd.x, kd.y, kd.z, cl_length(v));
+}
+
 // ---------------------------------------------------------------------------
 // ReconstructionPass (KRN/reconstruction.cl:6-60) with the filters of KRN/filters.cl:12-69,
 // evaluated on the device as the reference does (same expression shapes, so clang contracts the
@@ -1242,6 +1283,12 @@ void launch_aov(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, 
                 float4* out, hipStream_t st) {
     const int blocks = (f.numTiles * 64 + 255) / 256;
     hipLaunchKernelGGL(k_aov, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, s, f, cam, hits, which, out);
+}
+void launch_guides(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
+                   float4* normalPlane, float4* albedoDepth, hipStream_t st) {
+    const int blocks = (f.numTiles * 64 + 255) / 256;
+    hipLaunchKernelGGL(k_guides, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, s, f, cam, hits, normalPlane,
+                       albedoDepth);
 }
 void launch_accumulate(const FrameArgs& f, int frame, const mcrt_filter* filters, int filterStride, const float4* radiance,
                        float4* wsum, float* wts, float4* image, hipStream_t st) {

@@ -95,6 +95,12 @@ SIGNATURES = {
     "mcrt_framebuffer_wave_clock": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_int64, _c.POINTER(_c.c_int64)]),
     "mcrt_postprocess": (_c.c_int, [_vp, _c.POINTER(T.PostprocessParams)]),
     "mcrt_render_aov": (_c.c_int, [_vp, _vp, _vp, _vp, _c.c_int, _vp]),
+    "mcrt_render_guides": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "mcrt_framebuffer_set_guides": (_c.c_int, [_vp, _vp, _vp]),
+    "mcrt_framebuffer_set_moments_enabled": (_c.c_int, [_vp, _c.c_int]),
+    "mcrt_framebuffer_set_moments": (_c.c_int, [_vp, _vp, _c.c_int32]),
+    "mcrt_framebuffer_read_guides": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    "mcrt_denoise_guided": (_c.c_int, [_vp, _c.POINTER(T.GuidedDenoiseParams)]),
     "mcrt_framebuffer_read_bdpt": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     "mcrt_make_pinhole_camera": (_c.c_int, [_vp, _vp, _vp, _c.c_float, _c.c_float, _c.c_float, _c.c_uint32,
                                             _c.c_uint32, _vp, _vp]),
@@ -218,7 +224,7 @@ class Context:
         return g.value
 
     def kernel_stats(self):
-        n = 16
+        n = 32
         names = (_c.c_char_p * n)()
         ms = np.zeros(n, np.float64)
         launches = np.zeros(n, np.int64)
@@ -433,6 +439,42 @@ class FrameBuffer:
         p = T.PostprocessParams(1 if denoise else 0, radius, sigma_spatial, sigma_range, 1 if tonemap else 0,
                                 min_luminance)
         _check(lib().mcrt_postprocess(self.h, _c.byref(p)), self.ctx.h)
+
+    def render_guides(self, dscene, cam, texture_lod=False, band_rows=8, num_bands=1, band_index=0):
+        """mcrt_render_guides: camera rays + the denoiser's guide planes, on the device."""
+        p = T.FrameParams(0, 1, T.SAMPLER_RANDOM, 0, 3, band_rows, num_bands, band_index, T.INTEGRATOR_PT,
+                          1 if texture_lod else 0)
+        cam = np.ascontiguousarray(cam)
+        _check(lib().mcrt_render_guides(dscene.h, self.h, _p(cam), _c.byref(p)), self.ctx.h)
+
+    def set_guides(self, normal_plane_ptr, albedo_depth_ptr):
+        """mcrt_framebuffer_set_guides: both (H, W, 4) float32 planes from device memory."""
+        _check(lib().mcrt_framebuffer_set_guides(self.h, normal_plane_ptr, albedo_depth_ptr), self.ctx.h)
+
+    def enable_moments(self, on=True):
+        """mcrt_framebuffer_set_moments_enabled: accumulate also keeps (sum l, sum l*l) per pixel."""
+        _check(lib().mcrt_framebuffer_set_moments_enabled(self.h, 1 if on else 0), self.ctx.h)
+
+    def set_moments(self, m1m2_ptr, frames):
+        """mcrt_framebuffer_set_moments: (H, W, 2) float32 moments of `frames` frames from device memory."""
+        _check(lib().mcrt_framebuffer_set_moments(self.h, m1m2_ptr, int(frames)), self.ctx.h)
+
+    GUIDE_SHAPES = {T.GUIDE_NORMAL_PLANE: (4,), T.GUIDE_ALBEDO_DEPTH: (4,), T.GUIDE_MOMENTS: (2,),
+                    T.GUIDE_FILTERED_VARIANCE: ()}
+
+    def read_guides(self, which):
+        """mcrt_framebuffer_read_guides: 0 normal-plane (H, W, 4), 1 albedo-depth (H, W, 4), 2 moments
+        (H, W, 2), 3 the filtered variance of the last denoise_guided (H, W)."""
+        out = np.zeros((self.H, self.W) + self.GUIDE_SHAPES[which], np.float32)
+        _check(lib().mcrt_framebuffer_read_guides(self.h, which, _p(out), out.nbytes, None), self.ctx.h)
+        return out
+
+    def denoise_guided(self, levels=5, sigma_normal=0.1, sigma_depth=0.02, sigma_luminance=4.0, use_variance=True,
+                       demodulate_albedo=True, tonemap=False, min_luminance=2.0):
+        """mcrt_denoise_guided: the edge-avoiding a-trous filter on the accumulated image -> read(3)."""
+        p = T.GuidedDenoiseParams(levels, sigma_normal, sigma_depth, sigma_luminance, 1 if use_variance else 0,
+                                  1 if demodulate_albedo else 0, 1 if tonemap else 0, min_luminance)
+        _check(lib().mcrt_denoise_guided(self.h, _c.byref(p)), self.ctx.h)
 
     def read(self, which=0):
         out = np.zeros((self.H, self.W, 4), np.float32)

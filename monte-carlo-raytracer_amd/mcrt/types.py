@@ -150,6 +150,17 @@ class PostprocessParams(ctypes.Structure):
                 ("use_tonemapping", ctypes.c_int32), ("min_luminance", ctypes.c_float)]
 
 
+class GuidedDenoiseParams(ctypes.Structure):
+    """mcrt_guided_denoise_params (include/mcrt_capi.h)."""
+    _fields_ = [("levels", ctypes.c_int32), ("sigma_normal", ctypes.c_float), ("sigma_depth", ctypes.c_float),
+                ("sigma_luminance", ctypes.c_float), ("use_variance", ctypes.c_int32),
+                ("demodulate_albedo", ctypes.c_int32), ("use_tonemapping", ctypes.c_int32),
+                ("min_luminance", ctypes.c_float)]
+
+
+# mcrt_framebuffer_read_guides `which`
+GUIDE_NORMAL_PLANE, GUIDE_ALBEDO_DEPTH, GUIDE_MOMENTS, GUIDE_FILTERED_VARIANCE = 0, 1, 2, 3
+
 INTEGRATOR_PT = 0
 INTEGRATOR_BDPT = 1
 
