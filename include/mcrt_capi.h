@@ -575,6 +575,94 @@ typedef struct {
     float   min_luminance;
 } mcrt_guided_denoise_params;
 MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_denoise_params* params);
+
+/* ---- Temporal reprojection and history for the guided denoiser ---------------------------------
+ * The temporal half of SVGF (Schied et al. 2017) for an interactive caller that shows 1..k samples
+ * per displayed frame while the camera moves.  All of it is opt-in: without these calls nothing
+ * else launches, allocates or changes.  Per displayed frame:
+ *   1. render 1..k frames and accumulate them starting at frame_index 0,
+ *   2. mcrt_render_guides(camera),
+ *   3. mcrt_temporal_accumulate(fb, camera, params)   -- the camera those guides were made with,
+ *   4. mcrt_denoise_guided_temporal(fb, params, feedback_level)  -> display image.
+ *
+ * History planes, owned by the frame buffer, W*H records each, allocated on first use:
+ *   colour   float4  the integrated colour in filter space (image / albedo with demodulate_albedo,
+ *                    channels with albedo <= 1e-3 left alone), alpha of the current image
+ *   moments  float4  (mu1, mu2, N, z): the integrated luminance moments, the history length N (a
+ *                    float), the pixel's guide depth when the record was written (-1 on a miss)
+ *   previous normal-plane float4: the guide record the pixel had when written
+ *   variance float   the variance handed to the filter
+ * and a host copy of the camera they belong to.  The first three exist twice (read / written) and
+ * swap per accumulate; the guide planes themselves are never swapped or written.
+ *
+ * mcrt_temporal_accumulate, pixel p = (x, y), c = image (demodulated), l its luminance:
+ *   P - prev.pos = m * (depth_p / |m|) + (camera.pos - prev.pos), m the bilinear blend of camera's
+ *   corner directions at (x / W, y / H); the world point itself is never formed, so a scene far
+ *   from the origin loses nothing.  Its clip coordinates are rows 0, 1 and 3 of prev.worldToClip
+ *   applied to that offset, xyz only, the translation column dropped:
+ *     REQUIREMENT: camera.worldToClip must be a view-projection centred on camera.pos (then
+ *     worldToClip * (pos, 1) has zero x, y and w and the dropped column cancels exactly).
+ *     mcrt_make_pinhole_camera and mcrt.camera.make_camera make such cameras.
+ *   worldToClip carries no TAA jitter while the corner directions do, so history is resampled at the
+ *   unjittered projection.  With f = ((clip.xy / clip.w + 1) / 2) * (W, H), the four history
+ *   records around f (bilinear weights w) are tested: a tap q counts when it was a hit,
+ *   |n_p - n_q|^2 <= normal_threshold, and the plane it stored passes through the point,
+ *   |n_q . (P - prev.pos) - d_q| <= plane_threshold * |P - prev.pos|.  The test is on the plane, not
+ *   on a depth difference: a floor seen at a grazing angle is not rejected.
+ *   With valid weight above 1e-4:  N = min(sum w N_q / sum w + 1, max_history),
+ *     a = max(alpha, 1 / N), colour = lerp(history, c, a); the moments likewise with alpha_moments.
+ *   Otherwise (disocclusion, miss, off screen, no history):  N = 1, colour = c, moments = (l, l*l).
+ * Then the variance:  N >= min_history: max(0, mu2 - mu1^2);  otherwise the same expression of the
+ * moments averaged over the 7x7 neighbours on p's surface (both misses, or both hits whose
+ * normals and plane offsets agree within the thresholds, the offsets relative to p's depth), times
+ * min_history / N.  This is the variance of the samples, not of the mean: sigma_luminance keeps
+ * its default.  The float32 operation order of both kernels is fixed in mcrt_denoise.hip and
+ * restated in tests/temporal_ref.py.
+ *
+ * mcrt_denoise_guided_temporal runs mcrt_denoise_guided's levels with the colour history as the
+ * level-0 colour (no demodulation pass: it is in filter space already), the variance plane as var0
+ * and use_variance as given (no moments of mcrt_accumulate are needed); remodulation, tone mapping
+ * and the display image as there.  feedback_level = k >= 0 makes the output of level k the colour
+ * history the next accumulate integrates (SVGF: k = 0) by exchanging plane pointers, no copy;
+ * -1 feeds nothing back.  params->demodulate_albedo must equal the last accumulate's flag.
+ *
+ * mcrt_temporal_reset: the next accumulate starts without history (planes are kept).
+ * mcrt_framebuffer_set_temporal_history installs colour, moments and previous normal-plane (float4
+ * planes in device memory) and the camera they belong to (tests, other renderers).
+ * mcrt_framebuffer_read_temporal reads the planes as the NEXT accumulate will read them: which 0
+ * colour history, 1 moments history, 2 variance (float), 3 previous normal-plane; needed / host_dst
+ * / bytes as mcrt_framebuffer_read_guides.
+ *
+ * MCRT_ERROR_INVALID_ARG: NULL arguments, alpha or alpha_moments outside [0, 1], max_history or
+ * min_history < 1, non-positive thresholds, a camera whose size differs from the frame buffer,
+ * feedback_level outside -1 .. levels - 2, demodulate_albedo differing from the last accumulate.
+ * MCRT_ERROR_NOT_READY: no guides, a band-split BDPT frame pending, mcrt_denoise_guided_temporal
+ * before any accumulate or a second time after the same accumulate when the first call fed back.
+ * Everything is enqueued on the context stream after the last accumulate and the guides, as
+ * mcrt_denoise_guided; mcrt_framebuffer_read_temporal synchronises.
+ *
+ * Not covered: per-object motion vectors.  A moved instance's history is rejected by the plane
+ * test, or ghosts when the instance slides within its own plane.  Band-split or multi-rank history
+ * is not kept either: run this on the gathering rank. */
+typedef struct {
+    float   alpha;              /* weight floor of the new frame's colour, 0..1, default 0.2 */
+    float   alpha_moments;      /* same for the luminance moments, default 0.2 */
+    int32_t max_history;        /* cap of the history length N, >= 1, default 32 */
+    int32_t min_history;        /* N below which the variance is estimated spatially, >= 1, default 4 */
+    float   normal_threshold;   /* a history tap is valid when |n_p - n_q|^2 <= this, > 0, default 0.1 */
+    float   plane_threshold;    /* ... and its plane passes P within this * |P - prev.pos|, > 0, default 0.01 */
+    int32_t demodulate_albedo;  /* 1: the history lives in image / albedo space (as mcrt_denoise_guided's flag) */
+} mcrt_temporal_params;
+MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* camera,
+                                              const mcrt_temporal_params* params);
+MCRT_API mcrt_status mcrt_temporal_reset(mcrt_framebuffer fb);
+MCRT_API mcrt_status mcrt_denoise_guided_temporal(mcrt_framebuffer fb, const mcrt_guided_denoise_params* params,
+                                                  int32_t feedback_level);
+MCRT_API mcrt_status mcrt_framebuffer_set_temporal_history(mcrt_framebuffer fb, const void* d_colour,
+                                                           const void* d_moments, const void* d_normal_plane,
+                                                           const mcrt_camera* prev_camera);
+MCRT_API mcrt_status mcrt_framebuffer_read_temporal(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                    uint64_t* needed);
 /* Copies device -> host (RGBA32F, W*H*4 floats).  which: 0 radiance, 1 weighted sum, 2 image,
  * 3 display image (mcrt_postprocess, mcrt_denoise_guided). */
 MCRT_API mcrt_status mcrt_framebuffer_read(mcrt_framebuffer fb, int which, float* host_rgba);

@@ -42,14 +42,16 @@ enum KernelId {
     K_BDPT_START, K_BDPT_VERTEX, K_BDPT_CONNECT, K_BDPT_VIS, K_BDPT_GATHER, K_SHADOW_EXTEND,
     K_GUIDES, K_MOMENTS, K_ATROUS_PREP,
     K_ATROUS,   // one entry per level: K_ATROUS + i is the launch of step 2^i
-    K_COUNT = K_ATROUS + MCRT_ATROUS_MAX_LEVELS
+    K_TEMPORAL = K_ATROUS + MCRT_ATROUS_MAX_LEVELS, K_TEMPORAL_VAR,
+    K_COUNT
 };
 const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN",       "k_shadow",   "k_extend",
                                      "k_accumulate", "k_trace_closest", "k_trace_any",  "k_bdpt_start",
                                      "k_bdpt_vertex", "k_bdpt_connect", "k_bdpt_vis",   "k_bdpt_gather",
                                      "k_shadow_extend", "k_guides",      "k_moments",    "k_atrous_prep",
                                      "k_atrous_s1",   "k_atrous_s2",   "k_atrous_s4",  "k_atrous_s8",
-                                     "k_atrous_s16",  "k_atrous_s32",  "k_atrous_s64", "k_atrous_s128"};
+                                     "k_atrous_s16",  "k_atrous_s32",  "k_atrous_s64", "k_atrous_s128",
+                                     "k_temporal",    "k_temporal_var"};
 
 }  // namespace
 
@@ -266,6 +268,19 @@ struct mcrt_framebuffer_s {
     float4* atrousC[2] = {};
     float* atrousV[2] = {};
     float* filteredVar = nullptr;    // the last level's variance (one of atrousV), NULL before a denoise
+    // Temporal history (mcrt_temporal_accumulate), allocated on first use.  Colour, moments and the
+    // previous normal-plane exist twice: k_temporal reads set tCur and writes the other, then tCur
+    // flips, so set tCur is always what the next accumulate (and mcrt_framebuffer_read_temporal) reads.
+    float4* tColour[2] = {};         // integrated colour in filter space, alpha of the current image
+    float4* tMoments[2] = {};        // (mu1, mu2, N, z)
+    float4* tNormal[2] = {};         // the guide record the pixel had when written
+    float* tVar = nullptr;           // the variance handed to the filter
+    int tCur = 0;
+    bool tHaveHistory = false;       // false: the next accumulate starts without history
+    bool tAccumulated = false;       // an accumulate has run: the planes feed mcrt_denoise_guided_temporal
+    bool tFedBack = false;           // the colour history already holds a filtered level of this accumulate
+    int tDemod = 0;                  // demodulate_albedo of the last accumulate
+    mcrt_camera tPrevCam = {};       // camera of the history planes
 };
 
 // BDPT queue counters (64 ints per frame set): [d] the subpath-ray queue of depth d (d <= 33;
@@ -1458,7 +1473,9 @@ static void fb_free(mcrt_framebuffer fb) {
         w = nullptr;
     }
     void* ptrs[] = {fb->wsum, fb->wts, fb->image, fb->denoised, fb->display, fb->hintPix, fb->guideNormal,
-                    fb->guideAlbedo, fb->moments, fb->atrousC[0], fb->atrousC[1], fb->atrousV[0], fb->atrousV[1]};
+                    fb->guideAlbedo, fb->moments, fb->atrousC[0], fb->atrousC[1], fb->atrousV[0], fb->atrousV[1],
+                    fb->tColour[0], fb->tColour[1], fb->tMoments[0], fb->tMoments[1], fb->tNormal[0], fb->tNormal[1],
+                    fb->tVar};
     for (void* p : ptrs)
         if (p) hipFree(p);
     fb_free_bdpt(fb);
@@ -2461,6 +2478,193 @@ MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_
     }
     fb->filteredVar = fb->atrousV[src];
     if (p->use_tonemapping) mcrt::launch_tonemap(W * H, p->min_luminance, fb->atrousC[src], fb->display, st);
+    HIPCHK(ctx, hipGetLastError());
+    return MCRT_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Temporal reprojection and history (k_temporal, k_temporal_var in mcrt_denoise.hip)
+// ---------------------------------------------------------------------------
+static hipError_t ensure_temporal(mcrt_framebuffer fb) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = ensure_plane(fb->ctx, (void**)&fb->tColour[i], 16 * fb->N);
+        if (e == hipSuccess) e = ensure_plane(fb->ctx, (void**)&fb->tMoments[i], 16 * fb->N);
+        if (e == hipSuccess) e = ensure_plane(fb->ctx, (void**)&fb->tNormal[i], 16 * fb->N);
+    }
+    if (e == hipSuccess) e = ensure_plane(fb->ctx, (void**)&fb->tVar, 4 * fb->N);
+    return e;
+}
+
+// MCRT_TEMPORAL_LOADS selects k_temporal's load form for measurements and the test that both agree
+// bit for bit: "eager" issues all twelve tap records together, anything else (the default, the
+// form measured faster) fetches the eight validity records first and a tap's colour only when valid.
+static bool temporal_eager_loads() {
+    const char* e = std::getenv("MCRT_TEMPORAL_LOADS");
+    return e && std::strcmp(e, "eager") == 0;
+}
+
+MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* cam,
+                                              const mcrt_temporal_params* p) {
+    if (!fb || !cam || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f) || !(p->alpha_moments >= 0.0f && p->alpha_moments <= 1.0f))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "alpha and alpha_moments must be in 0 .. 1");
+    if (p->max_history < 1 || p->min_history < 1)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "max_history and min_history must be >= 1");
+    if (!(p->normal_threshold > 0.0f) || !(p->plane_threshold > 0.0f))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "thresholds must be positive");
+    if (cam->width != fb->W || cam->height != fb->H)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
+    if (!fb->haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
+    if (fb->bdptPendingGather)
+        return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, ensure_temporal(fb));
+    const int W = (int)fb->W, H = (int)fb->H;
+    const int old = fb->tCur, now = old ^ 1;
+    mcrt::TemporalParams t;
+    t.W = W;
+    t.H = H;
+    t.demod = p->demodulate_albedo ? 1 : 0;
+    t.haveHistory = fb->tHaveHistory ? 1 : 0;
+    t.alpha = p->alpha;
+    t.alphaMoments = p->alpha_moments;
+    t.maxHistory = (float)p->max_history;
+    t.normalThr = p->normal_threshold;
+    t.planeThr = p->plane_threshold;
+    t.cam = cam;
+    t.prev = fb->tHaveHistory ? &fb->tPrevCam : cam;
+    t.image = fb->image;
+    t.albedoDepth = fb->guideAlbedo;
+    t.normalPlane = fb->guideNormal;
+    t.colourOld = fb->tColour[old];
+    t.momentsOld = fb->tMoments[old];
+    t.normalOld = fb->tNormal[old];
+    t.colourNew = fb->tColour[now];
+    t.momentsNew = fb->tMoments[now];
+    t.normalNew = fb->tNormal[now];
+    {
+        Timed tm(ctx, K_TEMPORAL, nullptr, (int64_t)fb->N);
+        mcrt::launch_temporal(t, temporal_eager_loads(), st);
+    }
+    {
+        Timed tm(ctx, K_TEMPORAL_VAR, nullptr, (int64_t)fb->N);
+        mcrt::launch_temporal_var(W, H, p->min_history, p->normal_threshold, p->plane_threshold, fb->tMoments[now],
+                                  fb->tNormal[now], fb->tVar, st);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    fb->tCur = now;
+    fb->tHaveHistory = true;
+    fb->tAccumulated = true;
+    fb->tFedBack = false;
+    fb->tDemod = t.demod;
+    fb->tPrevCam = *cam;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_temporal_reset(mcrt_framebuffer fb) {
+    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
+    fb->tHaveHistory = false;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_temporal_history(mcrt_framebuffer fb, const void* d_colour,
+                                                           const void* d_moments, const void* d_normal_plane,
+                                                           const mcrt_camera* prev_camera) {
+    if (!fb || !d_colour || !d_moments || !d_normal_plane || !prev_camera)
+        return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    if (prev_camera->width != fb->W || prev_camera->height != fb->H)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, ensure_temporal(fb));
+    const int cur = fb->tCur;
+    HIPCHK(ctx, hipMemcpyAsync(fb->tColour[cur], d_colour, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->tMoments[cur], d_moments, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->tNormal[cur], d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    fb->tPrevCam = *prev_camera;
+    fb->tHaveHistory = true;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_read_temporal(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                    uint64_t* needed) {
+    if (!fb || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    mcrt_ctx ctx = fb->ctx;
+    const int cur = fb->tCur;
+    const void* src = which == 0 ? (const void*)fb->tColour[cur] : which == 1 ? (const void*)fb->tMoments[cur]
+                      : which == 2 ? (const void*)fb->tVar : (const void*)fb->tNormal[cur];
+    const uint64_t need = (which == 2 ? 4 : 16) * (uint64_t)fb->N;
+    if (needed) *needed = need;
+    if (!host_dst) return MCRT_OK;
+    if (!src) return fail(ctx, MCRT_ERROR_NOT_READY, "no temporal history yet");
+    if (bytes < need) return fail(ctx, MCRT_ERROR_INVALID_ARG, "destination too small");
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, fb_sync(fb));
+    HIPCHK(ctx, hipMemcpy(host_dst, src, need, hipMemcpyDeviceToHost));
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_denoise_guided_temporal(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p,
+                                                  int32_t feedback_level) {
+    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    if (p->levels < 1 || p->levels > MCRT_ATROUS_MAX_LEVELS)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "levels must be 1 .. 8");
+    if (!(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f) || !(p->sigma_luminance > 0.0f))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "sigmas must be positive");
+    if (feedback_level < -1 || feedback_level > p->levels - 2)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "feedback_level must be -1 .. levels - 2");
+    if (!fb->haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
+    if (fb->bdptPendingGather)
+        return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
+    if (!fb->tAccumulated) return fail(ctx, MCRT_ERROR_NOT_READY, "no mcrt_temporal_accumulate yet");
+    if (fb->tFedBack)
+        return fail(ctx, MCRT_ERROR_NOT_READY, "the colour history already holds a filtered level of this accumulate");
+    const int demod = p->demodulate_albedo ? 1 : 0;
+    if (demod != fb->tDemod)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "demodulate_albedo differs from the last mcrt_temporal_accumulate");
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const int W = (int)fb->W, H = (int)fb->H;
+    for (int i = 0; i < 2; ++i) {
+        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->atrousC[i], 16 * fb->N));
+        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->atrousV[i], 4 * fb->N));
+    }
+    const int useVar = p->use_variance ? 1 : 0;
+    const int ldsMax = atrous_lds_max_step();
+    // level 0 reads the colour history (already in filter space) and the variance plane; the levels
+    // then ping-pong between the scratch planes as in mcrt_denoise_guided
+    const float4* cIn = fb->tColour[fb->tCur];
+    const float* vIn = fb->tVar;
+    int dst = 0;
+    for (int i = 0; i < p->levels; ++i) {
+        const int step = 1 << i;
+        const bool last = i + 1 == p->levels;
+        float4* cOut = last && !p->use_tonemapping ? fb->display : fb->atrousC[dst];
+        const float sigmaLevel = useVar ? p->sigma_luminance : p->sigma_luminance * std::ldexp(1.0f, -i);
+        const bool lds = step <= ldsMax && mcrt::atrous_lds_bytes(step) <= 64 * 1024;
+        {
+            Timed t(ctx, K_ATROUS + i, nullptr, (int64_t)fb->N);
+            mcrt::launch_atrous(W, H, step, lds, p->sigma_normal, p->sigma_depth, sigmaLevel, useVar,
+                                last && demod ? 1 : 0, cIn, fb->guideNormal, fb->guideAlbedo, vIn, cOut, fb->atrousV[dst],
+                                st);
+        }
+        if (i == feedback_level) {
+            // this level's output (never the last level's: a scratch plane) becomes the colour history
+            // by exchanging the two planes; the old history plane, which only level 0 read, is scratch
+            // from now on, and no later level writes the new history plane
+            std::swap(fb->tColour[fb->tCur], fb->atrousC[dst]);
+            fb->tFedBack = true;
+        }
+        cIn = cOut;
+        vIn = fb->atrousV[dst];
+        dst ^= 1;
+    }
+    fb->filteredVar = fb->atrousV[dst ^ 1];
+    if (p->use_tonemapping) mcrt::launch_tonemap(W * H, p->min_luminance, cIn, fb->display, st);
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
 }

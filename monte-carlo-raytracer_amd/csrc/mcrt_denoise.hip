@@ -217,9 +217,290 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_atrous(AtrousArgs
     a.vOut[p] = sv / (sw * sw);
 }
 
+// ---- temporal reprojection and history (mcrt_temporal_accumulate) -----------------------------
+// History planes (W*H each, old read / new written): colour float4 in filter space, moments float4
+// (mu1, mu2, N, z) = integrated luminance moments, history length, guide depth when written (-1 on
+// a miss), and the normal-plane record the pixel had when written.
+
+// One pixel p = (x, y) per lane; float32, each line one operation in this order (IEEE / and sqrtf):
+//   c = image[p];  ad = albedoDepth[p];  g = normalPlane[p]
+//   demodulate: c.rgb = c.rgb / demodChannel(ad.rgb);   l = lum3(c.rgb);  ll = l * l
+//   have = false;  with a history and ad.w > 0:
+//     u = (float)x / (float)W;  v = (float)y / (float)H
+//     a = r00 + (r10 - r00) * u;  b = r01 + (r11 - r01) * u;  m = a + (b - a) * v      (per component)
+//     k = ad.w / sqrtf((m.x * m.x + m.y * m.y) + m.z * m.z)
+//     r = m * k + dpos            (dpos = cam.pos - prev.pos, one float32 subtraction on the host;
+//                                  r = P - prev.pos, the world point itself is never formed)
+//     cx = (M0.x * r.x + M0.y * r.y) + M0.z * r.z;  cy with M1;  cw with M3   (rows of prev.worldToClip,
+//          xyz only: for a view-projection centred on prev.pos the dropped column cancels exactly)
+//     cw > 0:  fx = ((cx / cw + 1) * 0.5f) * W;  fy = ((cy / cw + 1) * 0.5f) * H
+//     fx > -1 && fx < W && fy > -1 && fy < H   (NaN and huge values never reach the int cast):
+//       ix = (int)floorf(fx);  tx = fx - (float)ix;  iy, ty likewise
+//       zr = sqrtf((r.x * r.x + r.y * r.y) + r.z * r.z);  tol = planeThr * zr
+//       for j in 0, 1 (outer), i in 0, 1, q = (ix + i, iy + j) inside the image:
+//         hm = momentsOld[q];  pn = normalOld[q];  dn = g.xyz - pn.xyz
+//         valid = hm.w > 0 && (dn.x * dn.x + dn.y * dn.y) + dn.z * dn.z <= normalThr
+//                 && fabsf(((pn.x * r.x + pn.y * r.y) + pn.z * r.z) - pn.w) <= tol
+//         w = (i ? tx : 1 - tx) * (j ? ty : 1 - ty)
+//         valid:  sw += w;  sc.rgb += w * colourOld[q].rgb;  s1 += w * hm.x;  s2 += w * hm.y;  sn += w * hm.z
+//       have = sw > 1e-4f
+//   have:  N = fminf(sn / sw + 1, maxHistory);  al = fmaxf(alpha, 1 / N);  am = fmaxf(alphaMoments, 1 / N)
+//          out.rgb = (sc.rgb / sw) * (1 - al) + c.rgb * al
+//          mu1 = (s1 / sw) * (1 - am) + l * am;  mu2 = (s2 / sw) * (1 - am) + ll * am
+//   else:  N = 1;  out.rgb = c.rgb;  mu1 = l;  mu2 = ll
+//   colourNew[p] = (out.rgb, c.a);  momentsNew[p] = (mu1, mu2, N, ad.w);  normalNew[p] = g
+// EAGER = true issues the four taps' twelve 16-B records together; EAGER = false fetches the eight
+// validity records first and a tap's colour only when the tap is valid.  Same values, same bits.
+struct TemporalArgs {
+    int W, H;
+    int demod, haveHistory;
+    float alpha, alphaMoments, maxHistory, normalThr, planeThr;
+    float r00[3], r10[3], r11[3], r01[3];   // current camera's corner directions
+    float dpos[3];                          // cam.pos - prev.pos
+    float M0[3], M1[3], M3[3];              // prev.worldToClip rows 0, 1, 3 (xyz)
+    const float4* image;
+    const float4* albedoDepth;
+    const float4* normalPlane;
+    const float4* colourOld;
+    const float4* momentsOld;
+    const float4* normalOld;
+    float4* colourNew;
+    float4* momentsNew;
+    float4* normalNew;
+};
+
+template <bool EAGER>
+__global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal(TemporalArgs a) {
+    const int W = a.W, H = a.H;
+    const int x = blockIdx.x * ATROUS_TILE + (threadIdx.x & (ATROUS_TILE - 1));
+    const int y = blockIdx.y * ATROUS_TILE + threadIdx.x / ATROUS_TILE;
+    if (x >= W || y >= H) return;
+    const size_t p = (size_t)y * W + x;
+    float4 c = a.image[p];
+    const float4 ad = a.albedoDepth[p];
+    const float4 g = a.normalPlane[p];
+    if (a.demod) {
+        c.x = c.x / demodChannel(ad.x);
+        c.y = c.y / demodChannel(ad.y);
+        c.z = c.z / demodChannel(ad.z);
+    }
+    const float l = lum3(c.x, c.y, c.z);
+    const float ll = l * l;
+    float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f;
+    bool have = false;
+    if (a.haveHistory && ad.w > 0.0f) {
+        const float u = (float)x / (float)W, v = (float)y / (float)H;
+        float m[3], r[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float ea = a.r00[k] + (a.r10[k] - a.r00[k]) * u;
+            const float eb = a.r01[k] + (a.r11[k] - a.r01[k]) * u;
+            m[k] = ea + (eb - ea) * v;
+        }
+        const float k = ad.w / sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) r[i] = m[i] * k + a.dpos[i];
+        const float cx = (a.M0[0] * r[0] + a.M0[1] * r[1]) + a.M0[2] * r[2];
+        const float cy = (a.M1[0] * r[0] + a.M1[1] * r[1]) + a.M1[2] * r[2];
+        const float cw = (a.M3[0] * r[0] + a.M3[1] * r[1]) + a.M3[2] * r[2];
+        if (cw > 0.0f) {
+            const float fx = ((cx / cw + 1.0f) * 0.5f) * (float)W;
+            const float fy = ((cy / cw + 1.0f) * 0.5f) * (float)H;
+            if (fx > -1.0f && fx < (float)W && fy > -1.0f && fy < (float)H) {
+                const int ix = (int)floorf(fx), iy = (int)floorf(fy);
+                const float tx = fx - (float)ix, ty = fy - (float)iy;
+                const float zr = sqrtf((r[0] * r[0] + r[1] * r[1]) + r[2] * r[2]);
+                const float tol = a.planeThr * zr;
+                float4 hm[4], pn[4], hc[4];
+                bool in[4];
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {   // t = 2 j + i; every in-image tap's loads are issued here
+                    const int qx = ix + (t & 1), qy = iy + (t >> 1);
+                    in[t] = qx >= 0 && qx < W && qy >= 0 && qy < H;
+                    const size_t q = in[t] ? (size_t)qy * W + qx : p;
+                    hm[t] = a.momentsOld[q];
+                    pn[t] = a.normalOld[q];
+                    if (EAGER) hc[t] = a.colourOld[q];
+                }
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const float dnx = g.x - pn[t].x, dny = g.y - pn[t].y, dnz = g.z - pn[t].z;
+                    const float dn2 = (dnx * dnx + dny * dny) + dnz * dnz;
+                    const float res = fabsf(((pn[t].x * r[0] + pn[t].y * r[1]) + pn[t].z * r[2]) - pn[t].w);
+                    const bool valid = in[t] && hm[t].w > 0.0f && dn2 <= a.normalThr && res <= tol;
+                    if (!valid) continue;
+                    if (!EAGER) hc[t] = a.colourOld[(size_t)(iy + (t >> 1)) * W + (ix + (t & 1))];
+                    const float w = ((t & 1) ? tx : 1.0f - tx) * ((t >> 1) ? ty : 1.0f - ty);
+                    sw = sw + w;
+                    sr = sr + w * hc[t].x;
+                    sg = sg + w * hc[t].y;
+                    sb = sb + w * hc[t].z;
+                    s1 = s1 + w * hm[t].x;
+                    s2 = s2 + w * hm[t].y;
+                    sn = sn + w * hm[t].z;
+                }
+                have = sw > 1e-4f;
+            }
+        }
+    }
+    float N = 1.0f, mu1 = l, mu2 = ll;
+    float4 o = c;
+    if (have) {
+        N = fminf(sn / sw + 1.0f, a.maxHistory);
+        const float al = fmaxf(a.alpha, 1.0f / N), am = fmaxf(a.alphaMoments, 1.0f / N);
+        o.x = (sr / sw) * (1.0f - al) + c.x * al;
+        o.y = (sg / sw) * (1.0f - al) + c.y * al;
+        o.z = (sb / sw) * (1.0f - al) + c.z * al;
+        mu1 = (s1 / sw) * (1.0f - am) + l * am;
+        mu2 = (s2 / sw) * (1.0f - am) + ll * am;
+    }
+    a.colourNew[p] = o;
+    a.momentsNew[p] = make_float4(mu1, mu2, N, ad.w);
+    a.normalNew[p] = g;
+}
+
+// The variance handed to the filter, from the planes k_temporal has just written; float32, each
+// line one operation in this order:
+//   (mu1, mu2, N, z) = moments[p];  n_p, d_p = normalPlane[p] (xyz, w)
+//   N >= minHistory:  var = fmaxf(0, mu2 - mu1 * mu1)
+//   else, over dy in -3..3 (outer), dx in -3..3, q = p + (dx, dy) inside the image and on p's surface:
+//       s1 += mu1_q;  s2 += mu2_q;  cnt += 1                         (sums start at 0; q = p always counts)
+//     p's surface: z_p <= 0 and z_q <= 0, or both > 0 with
+//       dn = n_p - n_q;  (dn.x * dn.x + dn.y * dn.y) + dn.z * dn.z <= normalThr  and
+//       dd = d_p - d_q;  t = planeThr * z_p;  dd * dd <= t * t
+//     m1 = s1 / cnt;  m2 = s2 / cnt;  var = fmaxf(0, m2 - m1 * m1) * (minHistory / N)
+// The variance of the samples (SVGF), not of the mean.  A workgroup with a pixel on the spatial
+// path stages the moments and normal-plane records of its 16x16 tile and 3-pixel halo in LDS once
+// (read from memory per tap, the 49 x 32 B of every pixel took 0.27 ms at 1080p after a reset);
+// the values and the operations on them are the same either way.
+__global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal_var(int W, int H, float minHistory,
+                                                                            float normalThr, float planeThr,
+                                                                            const float4* __restrict__ moments,
+                                                                            const float4* __restrict__ normalPlane,
+                                                                            float* __restrict__ var) {
+    constexpr int TW = ATROUS_TILE + 6;   // the tile and its 3-pixel halo: 2 x 7.6 KB of LDS
+    __shared__ float4 sM[TW * TW];
+    __shared__ float4 sN[TW * TW];
+    const int x0 = blockIdx.x * ATROUS_TILE - 3, y0 = blockIdx.y * ATROUS_TILE - 3;
+    const int x = blockIdx.x * ATROUS_TILE + (threadIdx.x & (ATROUS_TILE - 1));
+    const int y = blockIdx.y * ATROUS_TILE + threadIdx.x / ATROUS_TILE;
+    const bool inside = x < W && y < H;
+    const size_t p = inside ? (size_t)y * W + x : 0;
+    const float4 mp = moments[p];
+    const bool spatial = inside && !(mp.z >= minHistory);
+    // a workgroup none of whose pixels takes the spatial path (the steady state) stages nothing
+    if (!__syncthreads_or(spatial)) {
+        if (inside) var[p] = fmaxf(0.0f, mp.y - mp.x * mp.x);
+        return;
+    }
+    for (int i = threadIdx.x; i < TW * TW; i += ATROUS_TILE * ATROUS_TILE) {
+        const int gy = y0 + i / TW, gx = x0 + i % TW;
+        float4 m = make_float4(0.0f, 0.0f, 0.0f, 0.0f), n = m;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {   // records outside the image are never read
+            const size_t g = (size_t)gy * W + gx;
+            m = moments[g];
+            n = normalPlane[g];
+        }
+        sM[i] = m;
+        sN[i] = n;
+    }
+    __syncthreads();
+    if (!inside) return;
+    if (!spatial) {
+        var[p] = fmaxf(0.0f, mp.y - mp.x * mp.x);
+        return;
+    }
+    const float4 np = sN[(y - y0) * TW + (x - x0)];
+    const float t = planeThr * mp.w;
+    const float t2 = t * t;
+    float s1 = 0.0f, s2 = 0.0f, cnt = 0.0f;
+    for (int dy = -3; dy <= 3; ++dy) {
+        const int qy = y + dy;
+        if (qy < 0 || qy >= H) continue;
+#pragma unroll
+        for (int dx = -3; dx <= 3; ++dx) {
+            const int qx = x + dx;
+            if (qx < 0 || qx >= W) continue;
+            const int q = (qy - y0) * TW + (qx - x0);
+            const float4 mq = sM[q];
+            const float4 nq = sN[q];
+            bool same = dx == 0 && dy == 0;
+            if (!same) {
+                if (mp.w > 0.0f) {
+                    const float dnx = np.x - nq.x, dny = np.y - nq.y, dnz = np.z - nq.z;
+                    const float dn2 = (dnx * dnx + dny * dny) + dnz * dnz;
+                    const float dd = np.w - nq.w;
+                    same = mq.w > 0.0f && dn2 <= normalThr && dd * dd <= t2;
+                } else {
+                    same = !(mq.w > 0.0f);
+                }
+            }
+            if (same) {
+                s1 = s1 + mq.x;
+                s2 = s2 + mq.y;
+                cnt = cnt + 1.0f;
+            }
+        }
+    }
+    const float m1 = s1 / cnt, m2 = s2 / cnt;
+    var[p] = fmaxf(0.0f, m2 - m1 * m1) * (minHistory / mp.z);
+}
+
 }  // namespace
 
 namespace mcrt {
+
+void launch_temporal(const TemporalParams& t, bool eager, hipStream_t st) {
+    TemporalArgs a;
+    a.W = t.W;
+    a.H = t.H;
+    a.demod = t.demod;
+    a.haveHistory = t.haveHistory;
+    a.alpha = t.alpha;
+    a.alphaMoments = t.alphaMoments;
+    a.maxHistory = t.maxHistory;
+    a.normalThr = t.normalThr;
+    a.planeThr = t.planeThr;
+    const mcrt_camera& c = *t.cam;
+    const mcrt_camera& o = *t.prev;
+    const float cp[3] = {c.pos.x, c.pos.y, c.pos.z}, op[3] = {o.pos.x, o.pos.y, o.pos.z};
+    const mcrt_float3* corner[4] = {&c.r00, &c.r10, &c.r11, &c.r01};
+    float* dst[4] = {a.r00, a.r10, a.r11, a.r01};
+    for (int i = 0; i < 4; ++i) {
+        dst[i][0] = corner[i]->x;
+        dst[i][1] = corner[i]->y;
+        dst[i][2] = corner[i]->z;
+    }
+    for (int i = 0; i < 3; ++i) a.dpos[i] = cp[i] - op[i];
+    const mcrt_float4* row[3] = {&o.worldToClip.m0, &o.worldToClip.m1, &o.worldToClip.m3};
+    float* rdst[3] = {a.M0, a.M1, a.M3};
+    for (int i = 0; i < 3; ++i) {
+        rdst[i][0] = row[i]->x;
+        rdst[i][1] = row[i]->y;
+        rdst[i][2] = row[i]->z;
+    }
+    a.image = t.image;
+    a.albedoDepth = t.albedoDepth;
+    a.normalPlane = t.normalPlane;
+    a.colourOld = t.colourOld;
+    a.momentsOld = t.momentsOld;
+    a.normalOld = t.normalOld;
+    a.colourNew = t.colourNew;
+    a.momentsNew = t.momentsNew;
+    a.normalNew = t.normalNew;
+    const dim3 grid((t.W + ATROUS_TILE - 1) / ATROUS_TILE, (t.H + ATROUS_TILE - 1) / ATROUS_TILE);
+    if (eager)
+        hipLaunchKernelGGL(k_temporal<true>, grid, dim3(ATROUS_TILE * ATROUS_TILE), 0, st, a);
+    else
+        hipLaunchKernelGGL(k_temporal<false>, grid, dim3(ATROUS_TILE * ATROUS_TILE), 0, st, a);
+}
+
+void launch_temporal_var(int W, int H, int minHistory, float normalThr, float planeThr, const float4* moments,
+                         const float4* normalPlane, float* var, hipStream_t st) {
+    const dim3 grid((W + ATROUS_TILE - 1) / ATROUS_TILE, (H + ATROUS_TILE - 1) / ATROUS_TILE);
+    hipLaunchKernelGGL(k_temporal_var, grid, dim3(ATROUS_TILE * ATROUS_TILE), 0, st, W, H, (float)minHistory, normalThr,
+                       planeThr, moments, normalPlane, var);
+}
 
 void launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st) {
     const int blocks = (f.numTiles * 64 + 255) / 256;

@@ -101,6 +101,11 @@ SIGNATURES = {
     "mcrt_framebuffer_set_moments": (_c.c_int, [_vp, _vp, _c.c_int32]),
     "mcrt_framebuffer_read_guides": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     "mcrt_denoise_guided": (_c.c_int, [_vp, _c.POINTER(T.GuidedDenoiseParams)]),
+    "mcrt_temporal_accumulate": (_c.c_int, [_vp, _vp, _c.POINTER(T.TemporalParams)]),
+    "mcrt_temporal_reset": (_c.c_int, [_vp]),
+    "mcrt_denoise_guided_temporal": (_c.c_int, [_vp, _c.POINTER(T.GuidedDenoiseParams), _c.c_int32]),
+    "mcrt_framebuffer_set_temporal_history": (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "mcrt_framebuffer_read_temporal": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     "mcrt_framebuffer_read_bdpt": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     "mcrt_make_pinhole_camera": (_c.c_int, [_vp, _vp, _vp, _c.c_float, _c.c_float, _c.c_float, _c.c_uint32,
                                             _c.c_uint32, _vp, _vp]),
@@ -475,6 +480,42 @@ class FrameBuffer:
         p = T.GuidedDenoiseParams(levels, sigma_normal, sigma_depth, sigma_luminance, 1 if use_variance else 0,
                                   1 if demodulate_albedo else 0, 1 if tonemap else 0, min_luminance)
         _check(lib().mcrt_denoise_guided(self.h, _c.byref(p)), self.ctx.h)
+
+    def temporal_accumulate(self, cam, alpha=0.2, alpha_moments=0.2, max_history=32, min_history=4,
+                            normal_threshold=0.1, plane_threshold=0.01, demodulate_albedo=True):
+        """mcrt_temporal_accumulate: reprojects the history into `cam` (the camera of the guides) and
+        integrates the accumulated image and its luminance moments into it."""
+        p = T.TemporalParams(alpha, alpha_moments, max_history, min_history, normal_threshold, plane_threshold,
+                             1 if demodulate_albedo else 0)
+        cam = np.ascontiguousarray(cam)
+        _check(lib().mcrt_temporal_accumulate(self.h, _p(cam), _c.byref(p)), self.ctx.h)
+
+    def temporal_reset(self):
+        """mcrt_temporal_reset: the next temporal_accumulate starts without history."""
+        _check(lib().mcrt_temporal_reset(self.h), self.ctx.h)
+
+    def denoise_guided_temporal(self, levels=5, sigma_normal=0.1, sigma_depth=0.02, sigma_luminance=4.0,
+                                use_variance=True, demodulate_albedo=True, tonemap=False, min_luminance=2.0,
+                                feedback_level=0):
+        """mcrt_denoise_guided_temporal: the a-trous levels over the colour history and its variance
+        -> read(3); the output of level `feedback_level` becomes the colour history (-1: none)."""
+        p = T.GuidedDenoiseParams(levels, sigma_normal, sigma_depth, sigma_luminance, 1 if use_variance else 0,
+                                  1 if demodulate_albedo else 0, 1 if tonemap else 0, min_luminance)
+        _check(lib().mcrt_denoise_guided_temporal(self.h, _c.byref(p), int(feedback_level)), self.ctx.h)
+
+    def set_temporal_history(self, colour_ptr, moments_ptr, normal_plane_ptr, prev_cam):
+        """mcrt_framebuffer_set_temporal_history: colour, moments (mu1, mu2, N, z) and previous
+        normal-plane, (H, W, 4) float32 each in device memory, and the camera they belong to."""
+        prev_cam = np.ascontiguousarray(prev_cam)
+        _check(lib().mcrt_framebuffer_set_temporal_history(self.h, colour_ptr, moments_ptr, normal_plane_ptr,
+                                                           _p(prev_cam)), self.ctx.h)
+
+    def read_temporal(self, which):
+        """mcrt_framebuffer_read_temporal, as the next accumulate reads them: 0 colour history,
+        1 moments history, 3 previous normal-plane (H, W, 4), 2 the variance (H, W)."""
+        out = np.zeros((self.H, self.W) + (() if which == T.TEMPORAL_VARIANCE else (4,)), np.float32)
+        _check(lib().mcrt_framebuffer_read_temporal(self.h, which, _p(out), out.nbytes, None), self.ctx.h)
+        return out
 
     def read(self, which=0):
         out = np.zeros((self.H, self.W, 4), np.float32)

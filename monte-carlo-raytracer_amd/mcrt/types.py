@@ -161,6 +161,17 @@ class GuidedDenoiseParams(ctypes.Structure):
 # mcrt_framebuffer_read_guides `which`
 GUIDE_NORMAL_PLANE, GUIDE_ALBEDO_DEPTH, GUIDE_MOMENTS, GUIDE_FILTERED_VARIANCE = 0, 1, 2, 3
 
+
+class TemporalParams(ctypes.Structure):
+    """mcrt_temporal_params (include/mcrt_capi.h)."""
+    _fields_ = [("alpha", ctypes.c_float), ("alpha_moments", ctypes.c_float), ("max_history", ctypes.c_int32),
+                ("min_history", ctypes.c_int32), ("normal_threshold", ctypes.c_float),
+                ("plane_threshold", ctypes.c_float), ("demodulate_albedo", ctypes.c_int32)]
+
+
+# mcrt_framebuffer_read_temporal `which`
+TEMPORAL_COLOUR, TEMPORAL_MOMENTS, TEMPORAL_VARIANCE, TEMPORAL_NORMAL_PLANE = 0, 1, 2, 3
+
 INTEGRATOR_PT = 0
 INTEGRATOR_BDPT = 1
 
