@@ -9,6 +9,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -19,10 +20,8 @@
 #include <thread>
 #include <tuple>
 #include <vector>
-#include <map>
-#include <tuple>
-#include <vector>
 
+#include "mcrt_devbuf.h"
 #include "mcrt_internal.h"
 
 namespace {
@@ -31,7 +30,12 @@ thread_local std::string g_lastError;
 }  // namespace
 namespace mcrt {
 void set_last_error(const std::string& msg) { g_lastError = msg; }
+// DevBuf's three ways to the device (mcrt_devbuf.h)
+int dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
+void dev_free(void* p) { (void)hipFree(p); }
+int dev_sync(void* stream) { return (int)hipStreamSynchronize((hipStream_t)stream); }
 }  // namespace mcrt
+using mcrt::DevBuf;
 namespace {
 
 #define MCRT_MAX_BOUNCES 32
@@ -84,24 +88,23 @@ struct mcrt_scene_s {
     std::vector<uint32_t> indices;
     std::vector<mcrt_float4> positions;
     // device arrays
-    void* dShapes = nullptr;
-    void* dIndices = nullptr;
-    void* dPositions = nullptr;
-    void* dUvs = nullptr;
-    void* dNormals = nullptr;
-    void* dTextures = nullptr;
-    void* dTexData = nullptr;
-    void* dSobol = nullptr;
-    void* dLights = nullptr;
-    void* dMaterials = nullptr;
-    void* dSurf = nullptr;       // surface records (SceneArgs::surf), 128 B per distinct mesh triangle
-    void* dSurfBase = nullptr;   // per shape: its first surface record
-    void* dSurfMeshes = nullptr; // build scratch: startIdx | startVertex | base per distinct mesh
+    DevBuf<mcrt_shape> dShapes;
+    DevBuf<uint32_t> dIndices;
+    DevBuf<float4> dPositions;
+    DevBuf<float2> dUvs;
+    DevBuf<float4> dNormals;
+    DevBuf<mcrt_texture_desc> dTextures;
+    DevBuf<uint8_t> dTexData;
+    DevBuf<uint32_t> dSobol;
+    DevBuf<mcrt_light> dLights;
+    DevBuf<mcrt_material> dMaterials;
+    DevBuf<float4> dSurf;           // surface records (SceneArgs::surf), 128 B per distinct mesh triangle
+    DevBuf<uint32_t> dSurfBase;     // per shape: its first surface record
+    DevBuf<uint32_t> dSurfMeshes;   // build scratch: startIdx | startVertex | base per distinct mesh
     uint32_t numLights = 0, numMaterials = 0, numTextures = 0;
     bool hasSobol = false;
     // BVH
-    void* dNodes = nullptr;
-    void* dTris = nullptr;
+    DevBuf<float4> dNodes;     // 4 float4 per record
     bool packets = false;      // coherent launches as wave packets (finish_accel)
     uint64_t numNodes = 0;
     uint32_t numTris = 0;
@@ -111,18 +114,16 @@ struct mcrt_scene_s {
     bool twoLevel = false;          // instanced scene: two-level records (mcrt_bvh2l.cpp)
     int numMeshes = 0, numInstances = 0;
     // traversal scratch
-    uint32_t* dSpill = nullptr;
+    DevBuf<uint32_t> dSpill;   // spillCap words per ray (ensure_spill)
     int spillCap = 0;
-    size_t spillRays = 0;           // rays the spill buffer covers (spillCap words each)
-    int* dScratch = nullptr;   // work counters for API queries
+    DevBuf<int> dScratch;      // work counters for API queries
     float bbLo[3] = {0, 0, 0}, bbHi[3] = {0, 0, 0};   // world bounds (root record of the BVH)
     // occluder hints of the shadow rays after bounce 0, by origin cell (TraceCtx::hint, flat trees):
     // allocated on the first shadow launch that uses hints (ensure_hint_cell), 2^hintBits words
-    uint32_t* dHintCell = nullptr;
+    DevBuf<uint32_t> dHintCell;
     int hintBits = 0;
-    // compact records of the flat tree (TraceCtx::qnodes; mcrt::build_qnodes), NULL when not built
-    float4* dQNodes = nullptr;
-    size_t qUnits = 0;
+    // compact records of the flat tree (TraceCtx::qnodes; mcrt::build_qnodes), empty when not built
+    DevBuf<float4> dQNodes;
     uint32_t qRoot = 0;
     bool hintAllocFailed = false;   // no memory for the table: hints stay off for this scene
     // transform updates (mcrt_accel_update_transforms): the options of the last mcrt_accel_build
@@ -135,6 +136,7 @@ struct mcrt_scene_s {
     mcrt::TopBuildDev* topDev = nullptr;
     int updatePath = 0;
     double updateMs = 0.0;
+    ~mcrt_scene_s() { mcrt::top_build_destroy(topDev); }   // the buffers free themselves
 };
 
 // One frame in flight (PT): the per-frame buffers of mcrt_render_frame, its own stream and
@@ -143,17 +145,22 @@ struct mcrt_scene_s {
 // `free` after reading the slot's radiance), so S frames overlap on the GPU -- each frame's
 // arithmetic and the per-pixel accumulation order are unchanged, so the image is the same bit
 // for bit.  Small per-rank frames (tile split over many GPUs) do not fill 256 CUs alone.
+#define SLOT_FILTER_OFFSET (512 + 176 * MCRT_MAX_BATCH_FRAMES)   // the batch's filters (mcrt_accumulate_frames)
+#define SLOT_COUNTER_BYTES (SLOT_FILTER_OFFSET + (int)sizeof(mcrt_filter) * MCRT_MAX_BATCH_FRAMES + 1536)
 struct FrameSlot {
-    float4* radiance = nullptr;
-    float4* hitsP = nullptr;     // primary hits (mcrt_kernels.hip hitSlot)
-    float4* hitsE = nullptr;     // extension hits by queue slot
-    float4* eO[2] = {};
-    float4* eD[2] = {};
-    float4* eT[2] = {};
-    float4 *sO = nullptr, *sD = nullptr, *sL = nullptr;
-    int* counters = nullptr;     // [0..31] shadow counts, [32..63] ext counts, [64..] work counters, camera @128
-    uint32_t* spill = nullptr;   // per-ray traversal spill columns of this slot's launches
-    size_t spillWords = 0;
+    DevBuf<float4> radiance;
+    DevBuf<float4> hitsP;        // primary hits (mcrt_kernels.hip hitSlot)
+    DevBuf<float4> hitsE;        // extension hits by queue slot
+    DevBuf<float4> eO[2], eD[2], eT[2];
+    DevBuf<float4> sO, sD, sL;
+    // [0..31] shadow counts, [32..63] ext counts, [64..127] work counters, then the batch's cameras
+    // (176 B each) from byte 512 and its filters from SLOT_FILTER_OFFSET
+    DevBuf<int> counters;
+    mcrt_camera* cameras() const { return reinterpret_cast<mcrt_camera*>(counters.get() + 128); }
+    mcrt_filter* filters() const {
+        return reinterpret_cast<mcrt_filter*>(reinterpret_cast<char*>(counters.get()) + SLOT_FILTER_OFFSET);
+    }
+    DevBuf<uint32_t> spill;      // per-ray traversal spill columns of this slot's launches
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;   // recorded after the slot's last render
     hipEvent_t free = nullptr;   // recorded on the context stream after the slot's buffers were last read
@@ -164,50 +171,43 @@ struct FrameSlot {
     size_t queueCap = 0;         // entries of each ray-queue buffer
     // longest-first tile order (FrameArgs::tileOrder): the camera-wave cost of each tile recorded by
     // this slot's last call, and the order made from it; stream-ordered on the slot's stream
-    uint32_t* tileCost = nullptr;
-    uint32_t* tileOrder = nullptr;
+    DevBuf<uint32_t> tileCost, tileOrder;   // the same size
     int costTiles = 0;           // tiles of the recorded costs (0: none)
-    int tileCap = 0;
     // suspended extension walks (TraceCtx::walkCap): MCRT_SUSPEND_F4 float4 per queue entry, and
     // one count per bounce (zeroed per call)
-    float4* suspend = nullptr;
-    size_t suspendCap = 0;
-    int* suspendCnt = nullptr;
+    DevBuf<float4> suspend;
+    DevBuf<int> suspendCnt;
 };
-#define SLOT_FILTER_OFFSET (512 + 176 * MCRT_MAX_BATCH_FRAMES)   // the batch's filters (mcrt_accumulate_frames)
-#define SLOT_COUNTER_BYTES (SLOT_FILTER_OFFSET + (int)sizeof(mcrt_filter) * MCRT_MAX_BATCH_FRAMES + 1536)
+static_assert(SLOT_COUNTER_BYTES % sizeof(int) == 0, "the counter block is allocated as ints");
 
 // Per-frame BDPT arrays (RTBDPTPass::createBuffers, RTBDPTPass.cpp:442-479), one set per frame
 // slot so BDPT frames overlap like PT frames; layouts in mcrt_bdpt.hip.
 struct BdptSet {
-    float4 *camV = nullptr, *lightV = nullptr, *slots = nullptr, *splat = nullptr;
-    int *camCount = nullptr, *lightCount = nullptr, *bdptCounters = nullptr;
-    float4 *bqO[2] = {}, *bqD[2] = {}, *bqT[2] = {}, *bHits = nullptr;
-    float4 *cO = nullptr, *cD = nullptr, *cL = nullptr;
-    uint32_t* spill = nullptr;   // traversal spill columns of this set's launches
+    DevBuf<float4> camV, lightV, slots, splat;
+    DevBuf<int> camCount, lightCount;
+    DevBuf<int> bdptCounters;    // 64 ints: the queue counters (BDPT_CNT_*)
+    DevBuf<float4> bqO[2], bqD[2], bqT[2], bHits;
+    DevBuf<float4> cO, cD, cL;   // connection queue
+    DevBuf<uint32_t> spill;      // traversal spill columns of this set's launches
     // the light-start queue's sort (mcrt::bdpt_light_sort): keys, sorted keys, slots, permutation
-    uint32_t *lkey = nullptr, *lkey2 = nullptr, *lslot = nullptr, *lperm = nullptr;
+    DevBuf<uint32_t> lkey, lkey2, lslot, lperm;
     // the traced bounce queues' sort (same routine; k_bdpt_vertex's keys over 2 N slots)
-    uint32_t *ekey = nullptr, *ekey2 = nullptr, *eslot = nullptr, *eperm = nullptr;
-    void* sortTmp = nullptr;
-    size_t sortTmpBytes = 0;
+    DevBuf<uint32_t> ekey, ekey2, eslot, eperm;
+    DevBuf<uint8_t> sortTmp;
     int frames = 0;              // batch frames the per-frame arrays hold (plane stride N x frames)
-    size_t spillWords = 0;
     // plane stride and band (rows, count, index) whose depth-0 frame-invariant planes k_bdpt_start
     // wrote for every path of the band
     size_t constStride = 0;
     int constBand[3] = {0, 0, -1};
     // band split, sparse splat exchange: the splats landing in other ranks' rows (BdptArgs::splatList)
     // and 128 ints of grouping scratch (per-owner counts, cursors)
-    float4* splatList = nullptr;
-    size_t splatListCap = 0;
-    int* splatAux = nullptr;
+    DevBuf<float4> splatList;
+    DevBuf<int> splatAux;
     // suspended closest-hit walks (TraceCtx::walkCap): MCRT_SUSPEND_F4 float4 per queue entry, one
     // count per traced queue (zeroed per call)
-    float4* suspend = nullptr;
-    size_t suspendCap = 0;
-    int* suspendCnt = nullptr;
-};   // [0..127] ints: counters; cameras (176 B each, <= MCRT_MAX_BATCH_FRAMES) from byte 512, then filters
+    DevBuf<float4> suspend;
+    DevBuf<int> suspendCnt;
+};
 
 struct mcrt_framebuffer_s {
     mcrt_ctx ctx = nullptr;
@@ -216,23 +216,12 @@ struct mcrt_framebuffer_s {
     std::vector<FrameSlot> slot;   // slot[0] always allocated; others on first use
     int cur = 0, next = 0;         // slot of the last rendered frame / of the next one
     int framesInFlight = 0;        // 0 = auto (mcrt_framebuffer_set_frames_in_flight)
-    // views of slot[cur] (the last rendered frame)
-    float4* radiance = nullptr;
-    float4* wsum = nullptr;
-    float* wts = nullptr;
-    float4* image = nullptr;
-    float4* denoised = nullptr;  // RTDenoisePass output (persistent: the reference keeps its image)
-    float4* display = nullptr;   // post-processed image (mcrt_postprocess)
-    uint32_t* hintPix = nullptr; // occluder hint of each pixel's bounce-0 shadow ray (TraceCtx::hint)
-    float4* hitsP = nullptr;     // primary hits (mcrt_kernels.hip hitSlot)
-    float4* hitsE = nullptr;     // extension hits by queue slot
-    float4* eO[2] = {};
-    float4* eD[2] = {};
-    float4* eT[2] = {};
-    float4 *sO = nullptr, *sD = nullptr, *sL = nullptr;
-    int* counters = nullptr;
-    int lastMaxDepth = 0;
-    int64_t lastPixels = 0;
+    DevBuf<float4> wsum;
+    DevBuf<float> wts;
+    DevBuf<float4> image;
+    DevBuf<float4> denoised;     // RTDenoisePass output (persistent: the reference keeps its image)
+    DevBuf<float4> display;      // post-processed image (mcrt_postprocess)
+    DevBuf<uint32_t> hintPix;    // occluder hint of each pixel's bounce-0 shadow ray (TraceCtx::hint)
     FrameArgs bands{};      // band layout of the last mcrt_render_frame (used by mcrt_accumulate)
     bool haveBands = false;
     // BDPT state (allocated on the first BDPT frame for a max depth; mcrt_bdpt.hip has the layout):
@@ -243,13 +232,8 @@ struct mcrt_framebuffer_s {
     hipEvent_t bdptConnect = nullptr;   // recorded after the last enqueued frame's connect launch
     // diagnostics (MCRT_WAVE_CLOCK=1): per-workgroup (start, end) clocks of the last PT call's camera,
     // shadow+extension and last shadow launches (mcrt_framebuffer_wave_clock)
-    uint32_t* waveClk[3] = {};
-    size_t waveClkBlocks[3] = {};
-    // views of the set of the last BDPT frame (read-back API)
-    float4 *camV = nullptr, *lightV = nullptr, *sampLight = nullptr, *slots = nullptr, *splat = nullptr;
-    int *camCount = nullptr, *lightCount = nullptr, *bdptCounters = nullptr;
-    float4 *bqO[2] = {}, *bqD[2] = {}, *bqT[2] = {}, *bHits = nullptr;
-    float4 *cO = nullptr, *cD = nullptr, *cL = nullptr;   // connection queue
+    DevBuf<uint32_t> waveClk[3];   // 2 words per workgroup
+    DevBuf<float4> sampLight;      // the sampled-light-vertex planes (D x N)
     int lastIntegrator = MCRT_INTEGRATOR_PT;
     int bdptBatch = 1;           // frames of the last BDPT call (plane stride N x bdptBatch)
     bool bdptOneSet = false;     // a second BDPT set did not fit in HBM: BDPT frames use slot 0 only
@@ -259,22 +243,22 @@ struct mcrt_framebuffer_s {
     // Guided denoiser (mcrt_denoise_guided), every plane allocated on first use: the guides of the
     // camera-ray hits, the luminance moments k_moments keeps next to the image, and two scratch
     // colour / variance planes the levels ping-pong between (fb->denoised stays mcrt_postprocess's)
-    float4* guideNormal = nullptr;   // (n, n . (P - cam.pos))
-    float4* guideAlbedo = nullptr;   // (Kd, |P - cam.pos|), -1 on a miss
+    DevBuf<float4> guideNormal;      // (n, n . (P - cam.pos))
+    DevBuf<float4> guideAlbedo;      // (Kd, |P - cam.pos|), -1 on a miss
     bool haveGuides = false;
-    float2* moments = nullptr;       // (sum l, sum l*l)
+    DevBuf<float2> moments;          // (sum l, sum l*l)
     bool momentsOn = false;
     int momentFrames = 0;            // frames in the moments (host side; restarts at frame_index 0)
-    float4* atrousC[2] = {};
-    float* atrousV[2] = {};
-    float* filteredVar = nullptr;    // the last level's variance (one of atrousV), NULL before a denoise
+    DevBuf<float4> atrousC[2];
+    DevBuf<float> atrousV[2];
+    int filteredVar = -1;            // which of atrousV holds the last level's variance, -1 before a denoise
     // Temporal history (mcrt_temporal_accumulate), allocated on first use.  Colour, moments and the
     // previous normal-plane exist twice: k_temporal reads set tCur and writes the other, then tCur
     // flips, so set tCur is always what the next accumulate (and mcrt_framebuffer_read_temporal) reads.
-    float4* tColour[2] = {};         // integrated colour in filter space, alpha of the current image
-    float4* tMoments[2] = {};        // (mu1, mu2, N, z)
-    float4* tNormal[2] = {};         // the guide record the pixel had when written
-    float* tVar = nullptr;           // the variance handed to the filter
+    DevBuf<float4> tColour[2];       // integrated colour in filter space, alpha of the current image
+    DevBuf<float4> tMoments[2];      // (mu1, mu2, N, z)
+    DevBuf<float4> tNormal[2];       // the guide record the pixel had when written
+    DevBuf<float> tVar;              // the variance handed to the filter
     int tCur = 0;
     bool tHaveHistory = false;       // false: the next accumulate starts without history
     bool tAccumulated = false;       // an accumulate has run: the planes feed mcrt_denoise_guided_temporal
@@ -282,6 +266,11 @@ struct mcrt_framebuffer_s {
     int tDemod = 0;                  // demodulate_albedo of the last accumulate
     mcrt_camera tPrevCam = {};       // camera of the history planes
 };
+// The slot of the last rendered frame and the set of the last BDPT call: what the read-back entry
+// points show.  After a failed regrow their buffers are empty, never stale.
+static FrameSlot& cur_slot(mcrt_framebuffer fb) { return fb->slot[fb->cur]; }
+static BdptSet& cur_bset(mcrt_framebuffer fb) { return fb->bset[fb->bdptSet]; }
+static const char* const kNoSlotBuffers = "the frame slot has no buffers (its last allocation failed)";
 
 // BDPT queue counters (64 ints per frame set): [d] the subpath-ray queue of depth d (d <= 33;
 // at depth 0 the light rays only), then these
@@ -298,19 +287,20 @@ static mcrt_status fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg) 
 }
 #define HIPCHK(ctx, expr)                                                                                   \
     do {                                                                                                    \
-        hipError_t e_ = (expr);                                                                             \
+        hipError_t e_ = (hipError_t)(expr);   /* DevBuf reports the runtime's codes as int */               \
         if (e_ != hipSuccess)                                                                               \
             return fail(ctx, e_ == hipErrorOutOfMemory ? MCRT_ERROR_OUT_OF_MEMORY : MCRT_ERROR_DEVICE,      \
                         std::string(#expr) + ": " + hipGetErrorString(e_));                                 \
     } while (0)
 
-template <class T>
-static hipError_t upload(void** dst, const T* src, size_t count, hipStream_t st) {
-    *dst = nullptr;
+// `count` host elements into the (empty) buffer; S is T or the C ABI's name for it
+template <class T, class S>
+static hipError_t upload(DevBuf<T>& dst, const S* src, size_t count, hipStream_t st) {
+    static_assert(sizeof(S) == sizeof(T), "same element");
     if (!src || count == 0) return hipSuccess;
-    hipError_t e = hipMalloc(dst, sizeof(T) * count);
+    hipError_t e = (hipError_t)dst.alloc(count);
     if (e != hipSuccess) return e;
-    return hipMemcpyAsync(*dst, src, sizeof(T) * count, hipMemcpyHostToDevice, st);
+    return hipMemcpyAsync(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice, st);
 }
 
 struct Timed {
@@ -377,38 +367,34 @@ static inline void xformPoint(const mcrt_mat4& m, const mcrt_float4& p, float* o
 // Per-ray spill columns for `rays` rays (rounded up to whole waves); grown on demand.
 static bool ensure_spill(mcrt_scene s, size_t rays) {
     rays = (rays + 63) / 64 * 64;
-    if (rays <= s->spillRays && s->dSpill) return true;
-    hipStreamSynchronize(s->ctx->stream);   // the old buffer may still be in use
-    if (s->dSpill) hipFree(s->dSpill);
-    s->dSpill = nullptr;
-    s->spillRays = 0;
-    if (hipMalloc(&s->dSpill, rays * (size_t)s->spillCap * sizeof(uint32_t)) != hipSuccess) return false;
-    s->spillRays = rays;
-    return true;
+    return s->dSpill.grow(rays * (size_t)s->spillCap, s->ctx->stream) == 0;
 }
 
 static TraceCtx trace_ctx(mcrt_scene s) {
     TraceCtx c = {};
-    c.nodes = (const float4*)s->dNodes;
+    c.nodes = s->dNodes.get();
     c.packet = 0;
-    c.spill = s->dSpill;
+    c.spill = s->dSpill.get();
     c.spillCap = s->spillCap;
     c.overflow = s->ctx->dFlags;
     c.twoLevel = s->twoLevel ? 1 : 0;
     c.numNodes = (uint32_t)s->numNodes;
-    c.qnodes = s->dQNodes;
+    c.qnodes = s->dQNodes.get();
     c.qroot = s->qRoot;
     return c;
+}
+
+// An integer environment variable clamped to lo .. hi, or `def` when it is not set.
+static int env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX) {
+    const char* e = std::getenv(name);
+    return e ? (int)std::min<long>(hi, std::max<long>(lo, std::strtol(e, nullptr, 10))) : def;
 }
 
 // Occluder hints for a shadow launch (mcrt_traverse.h hintOccludes; flat trees only -- the leaf test
 // of a two-level record would need the instance transform): bounce-0 rays by pixel (table `pix`,
 // n pixels), later ones by origin cell.  The answers are the walk's with or without them;
 // MCRT_SHADOW_HINTS=0 turns them off (A/B, tests).
-static bool hints_enabled() {
-    const char* e = std::getenv("MCRT_SHADOW_HINTS");
-    return !(e && std::atoi(e) == 0);
-}
+static bool hints_enabled() { return env_int("MCRT_SHADOW_HINTS", 1) != 0; }
 // test hook: MCRT_TEST_HINT_FILL=seed fills a new hint table with pseudo-random words below
 // `range` instead of "no hint", so a test can check that arbitrary hints change no answer
 static hipError_t fill_hints(uint32_t* d, size_t n, uint32_t range, hipStream_t st) {
@@ -439,13 +425,12 @@ static bool ensure_hint_cell(mcrt_scene s) {
     if (s->hintAllocFailed) return false;
     mcrt_ctx ctx = s->ctx;
     const int bits = hint_bits_for((uint32_t)s->numNodes);
-    hipError_t e = hipMalloc(&s->dHintCell, sizeof(uint32_t) << bits);
-    if (e == hipSuccess) e = fill_hints(s->dHintCell, (size_t)1 << bits, (uint32_t)s->numNodes + 64, ctx->stream);
+    hipError_t e = (hipError_t)s->dHintCell.alloc((size_t)1 << bits);
+    if (e == hipSuccess) e = fill_hints(s->dHintCell.get(), (size_t)1 << bits, (uint32_t)s->numNodes + 64, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) {
         hipGetLastError();
-        if (s->dHintCell) hipFree(s->dHintCell);
-        s->dHintCell = nullptr;
+        s->dHintCell.reset();
         s->hintAllocFailed = true;
         return false;
     }
@@ -454,14 +439,14 @@ static bool ensure_hint_cell(mcrt_scene s) {
 }
 static void with_hints(TraceCtx& c, mcrt_scene s, uint32_t* pix, uint32_t n) {
     if (s->twoLevel || !hints_enabled() || !ensure_hint_cell(s)) return;
-    c.hintCell = s->dHintCell;
+    c.hintCell = s->dHintCell.get();
     c.hintMask = (1u << s->hintBits) - 1;
     for (int a = 0; a < 3; ++a) {
         const float ext = s->bbHi[a] - s->bbLo[a];
         c.hintLo[a] = s->bbLo[a];
         c.hintInvExt[a] = ext > 0.0f ? 1.0f / ext : 0.0f;
     }
-    c.hint = pix ? pix : s->dHintCell;
+    c.hint = pix ? pix : s->dHintCell.get();
     c.hintMode = pix ? MCRT_HINT_PIXEL : MCRT_HINT_CELL;
     c.hintPixels = n;
 }
@@ -470,10 +455,7 @@ static void with_hints(TraceCtx& c, mcrt_scene s, uint32_t* pix, uint32_t n) {
 // once it has taken MCRT_WALK_CAP steps (0 = never) and MCRT_WALK_LANES of its lanes or fewer are
 // still walking (64: a fixed step limit).  Default 60 / 8: k_shadow_extend 0.643 -> 0.603 ms per
 // frame on the headline (a fixed 130-step limit 0.609; profiles/r05/ab/README.txt item 20)
-static int walk_cap() {
-    const char* e = std::getenv("MCRT_WALK_CAP");
-    return e ? std::max(0, std::atoi(e)) : 60;
-}
+static int walk_cap() { return env_int("MCRT_WALK_CAP", 60, 0); }
 // PT: the stop rule for the extension launches of bounces <= MCRT_WALK_MAXB (default 0: the first,
 // full-size one).  At depth 5 the later, smaller launches -- whose any-hit shadow blocks otherwise
 // overlap the long walks' tail -- lost what the first gained: k_shadow_extend 2.951 ms per frame
@@ -482,24 +464,12 @@ static int walk_cap() {
 // strong-scaled frame (N = 8: 5 M paths per call) finishes the resumed walks in a launch too small
 // to hide their tail (emulated N = 8 rank 0.175 -> 0.179 ms per frame with the rule; BDPT 0.649 ->
 // 0.659).  The tests set it to 0 to run the rule on small frames.
-static int64_t walk_min_paths() {
-    const char* e = std::getenv("MCRT_WALK_MIN_PATHS");
-    return e ? std::atoll(e) : 16000000;
-}
-static int walk_max_bounce() {
-    const char* e = std::getenv("MCRT_WALK_MAXB");
-    return e ? std::atoi(e) : 0;
-}
+static int64_t walk_min_paths() { return env_int("MCRT_WALK_MIN_PATHS", 16000000); }
+static int walk_max_bounce() { return env_int("MCRT_WALK_MAXB", 0); }
 // BDPT: the light-tracing strategies (t = 1) evaluated by the vertex launches that create their
 // light vertices instead of by a connection launch that re-reads them (MCRT_BDPT_LIGHT_IN_VERTEX)
-static int bdpt_light_in_vertex() {
-    const char* e = std::getenv("MCRT_BDPT_LIGHT_IN_VERTEX");
-    return e ? (std::atoi(e) != 0) : 1;
-}
-static int walk_lanes() {
-    const char* e = std::getenv("MCRT_WALK_LANES");
-    return e ? std::min(64, std::max(0, std::atoi(e))) : 8;
-}
+static int bdpt_light_in_vertex() { return env_int("MCRT_BDPT_LIGHT_IN_VERTEX", 1) != 0; }
+static int walk_lanes() { return env_int("MCRT_WALK_LANES", 8, 0, 64); }
 
 // the coherent launches' view (camera rays, bounce-0 shadow rays): wave packets when the tree allows
 static TraceCtx packet_ctx(mcrt_scene s) {
@@ -510,22 +480,53 @@ static TraceCtx packet_ctx(mcrt_scene s) {
 
 static SceneArgs scene_args(mcrt_scene s) {
     SceneArgs a;
-    a.shapes = (const mcrt_shape*)s->dShapes;
-    a.indices = (const uint32_t*)s->dIndices;
-    a.positions = (const float4*)s->dPositions;
-    a.uvs = (const float2*)s->dUvs;
-    a.normals = (const float4*)s->dNormals;
-    a.textures = (const mcrt_texture_desc*)s->dTextures;
-    a.texData = (const uint8_t*)s->dTexData;
-    a.sobol = (const uint32_t*)s->dSobol;
-    a.lights = (const mcrt_light*)s->dLights;
-    a.materials = (const mcrt_material*)s->dMaterials;
-    a.nodes = (const float4*)s->dNodes;
-    a.surf = (const float4*)s->dSurf;
-    a.surfBase = (const uint32_t*)s->dSurfBase;
+    a.shapes = s->dShapes.get();
+    a.indices = s->dIndices.get();
+    a.positions = s->dPositions.get();
+    a.uvs = s->dUvs.get();
+    a.normals = s->dNormals.get();
+    a.textures = s->dTextures.get();
+    a.texData = s->dTexData.get();
+    a.sobol = s->dSobol.get();
+    a.lights = s->dLights.get();
+    a.materials = s->dMaterials.get();
+    a.nodes = s->dNodes.get();
+    a.surf = s->dSurf.get();
+    a.surfBase = s->dSurfBase.get();
     a.numLights = (int)s->numLights;
     return a;
 }
+
+// Replaces a scene array once the context stream has finished with the old one.
+template <class T>
+static mcrt_status replace_array(mcrt_scene s, DevBuf<T>& dst, const T* src, size_t count) {
+    mcrt_ctx ctx = s->ctx;
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    dst.reset();
+    if (count) {
+        HIPCHK(ctx, dst.alloc(count));
+        HIPCHK(ctx, hipMemcpy(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice));
+    }
+    return MCRT_OK;
+}
+
+// Allocates the plane (one T per pixel, zero-filled on the context stream) when it does not exist yet.
+template <class T>
+static hipError_t ensure_plane(mcrt_framebuffer fb, DevBuf<T>& p) {
+    if (p) return hipSuccess;
+    hipError_t e = (hipError_t)p.alloc(fb->N);
+    if (e == hipSuccess) e = hipMemsetAsync(p.get(), 0, sizeof(T) * fb->N, fb->ctx->stream);
+    return e;
+}
+
+// Level 0's input of an a-trous chain: colour in filter space and its variance plane.
+struct AtrousIn {
+    const float4* colour = nullptr;
+    const float* var = nullptr;
+    int useVar = 0;
+};
+using AtrousBegin = mcrt_status (*)(mcrt_framebuffer, const mcrt_guided_denoise_params*, AtrousIn&);
 
 // ---------------------------------------------------------------------------
 // context
@@ -716,28 +717,6 @@ MCRT_API mcrt_status mcrt_ctx_reset_stats(mcrt_ctx ctx) {
 // ---------------------------------------------------------------------------
 // scene
 // ---------------------------------------------------------------------------
-static void scene_free_device(mcrt_scene s) {
-    void** ptrs[] = {&s->dShapes, &s->dIndices, &s->dPositions, &s->dUvs, &s->dNormals, &s->dTextures,
-                     &s->dTexData, &s->dSobol, &s->dLights, &s->dMaterials, &s->dNodes, &s->dTris,
-                     &s->dSurf, &s->dSurfBase, &s->dSurfMeshes};
-    for (void** p : ptrs) {
-        if (*p) hipFree(*p);
-        *p = nullptr;
-    }
-    if (s->dSpill) hipFree(s->dSpill);
-    if (s->dScratch) hipFree(s->dScratch);
-    if (s->dHintCell) hipFree(s->dHintCell);
-    s->dHintCell = nullptr;
-    if (s->dQNodes) hipFree(s->dQNodes);
-    s->dQNodes = nullptr;
-    s->qUnits = 0;
-    mcrt::top_build_destroy(s->topDev);
-    s->topDev = nullptr;
-    s->dSpill = nullptr;
-    s->spillRays = 0;
-    s->dScratch = nullptr;
-}
-
 // Surface records (SceneArgs::surf): shapes with the same (startIdx, startVertex, numTriangles)
 // -- RTScene's instances of one mesh -- share one record range; the records are gathered on the
 // device from the uploaded index/vertex arrays.  Rebuilt when shapes change.
@@ -762,24 +741,21 @@ static hipError_t build_surface_records(mcrt_scene s) {
         shapeBase[i] = it->second;
     }
     hipError_t e = hipStreamSynchronize(st);   // the old records may still be read
-    void** old[] = {&s->dSurf, &s->dSurfBase, &s->dSurfMeshes};
-    for (void** p : old) {
-        if (*p) hipFree(*p);
-        *p = nullptr;
-    }
+    s->dSurf.reset();
+    s->dSurfBase.reset();
+    s->dSurfMeshes.reset();
     const int nm = (int)mBase.size();
     std::vector<uint32_t> meshes(3 * (size_t)std::max(nm, 1));
     std::copy(mStart.begin(), mStart.end(), meshes.begin());
     std::copy(mVert.begin(), mVert.end(), meshes.begin() + nm);
     std::copy(mBase.begin(), mBase.end(), meshes.begin() + 2 * nm);
-    if (e == hipSuccess) e = hipMalloc(&s->dSurf, (size_t)std::max(total, 1u) * 128);
-    if (e == hipSuccess) e = upload(&s->dSurfBase, shapeBase.data(), shapeBase.size(), st);
-    if (e == hipSuccess) e = upload(&s->dSurfMeshes, meshes.data(), meshes.size(), st);
+    if (e == hipSuccess) e = (hipError_t)s->dSurf.alloc((size_t)std::max(total, 1u) * 8);   // 128 B per record
+    if (e == hipSuccess) e = upload(s->dSurfBase, shapeBase.data(), shapeBase.size(), st);
+    if (e == hipSuccess) e = upload(s->dSurfMeshes, meshes.data(), meshes.size(), st);
     if (e == hipSuccess && nm > 0) {
-        const uint32_t* m = (const uint32_t*)s->dSurfMeshes;
-        mcrt::launch_surface_records(m, m + nm, m + 2 * nm, nm, total, (const uint32_t*)s->dIndices,
-                                     (const float4*)s->dPositions, (const float2*)s->dUvs, (const float4*)s->dNormals,
-                                     (float4*)s->dSurf, st);
+        const uint32_t* m = s->dSurfMeshes.get();
+        mcrt::launch_surface_records(m, m + nm, m + 2 * nm, nm, total, s->dIndices.get(), s->dPositions.get(),
+                                     s->dUvs.get(), s->dNormals.get(), s->dSurf.get(), st);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -824,7 +800,7 @@ MCRT_API mcrt_status mcrt_scene_create(mcrt_ctx ctx, const mcrt_scene_desc* d, m
     s->positions.assign(d->positions, d->positions + d->num_vertices);
     hipStream_t st = ctx->stream;
     hipError_t e = hipSuccess;
-#define UP(dst, src, cnt) if (e == hipSuccess) e = upload(&s->dst, src, cnt, st)
+#define UP(dst, src, cnt) if (e == hipSuccess) e = upload(s->dst, src, cnt, st)
     UP(dShapes, d->shapes, d->num_shapes);
     UP(dIndices, d->indices, d->num_indices);
     UP(dPositions, d->positions, d->num_vertices);
@@ -839,7 +815,6 @@ MCRT_API mcrt_status mcrt_scene_create(mcrt_ctx ctx, const mcrt_scene_desc* d, m
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e == hipSuccess) e = build_surface_records(s);
     if (e != hipSuccess) {
-        scene_free_device(s);
         delete s;
         return fail(ctx, e == hipErrorOutOfMemory ? MCRT_ERROR_OUT_OF_MEMORY : MCRT_ERROR_DEVICE,
                     std::string("scene upload: ") + hipGetErrorString(e));
@@ -856,34 +831,20 @@ MCRT_API mcrt_status mcrt_scene_destroy(mcrt_scene s) {
     if (!s) return MCRT_OK;
     hipSetDevice(s->ctx->device);
     hipStreamSynchronize(s->ctx->stream);
-    scene_free_device(s);
     delete s;
-    return MCRT_OK;
-}
-
-static mcrt_status replace_array(mcrt_scene s, void** dst, const void* src, size_t bytes) {
-    mcrt_ctx ctx = s->ctx;
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (*dst) HIPCHK(ctx, hipFree(*dst));
-    *dst = nullptr;
-    if (bytes) {
-        HIPCHK(ctx, hipMalloc(dst, bytes));
-        HIPCHK(ctx, hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-    }
     return MCRT_OK;
 }
 
 MCRT_API mcrt_status mcrt_scene_update_lights(mcrt_scene s, const mcrt_light* lights, uint32_t n) {
     if (!s || (n && !lights)) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "invalid lights");
-    mcrt_status st = replace_array(s, &s->dLights, lights, sizeof(mcrt_light) * n);
+    mcrt_status st = replace_array(s, s->dLights, lights, n);
     if (st == MCRT_OK) s->numLights = n;
     return st;
 }
 
 MCRT_API mcrt_status mcrt_scene_update_materials(mcrt_scene s, const mcrt_material* m, uint32_t n) {
     if (!s || (n && !m)) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "invalid materials");
-    mcrt_status st = replace_array(s, &s->dMaterials, m, sizeof(mcrt_material) * n);
+    mcrt_status st = replace_array(s, s->dMaterials, m, n);
     if (st == MCRT_OK) s->numMaterials = n;
     return st;
 }
@@ -895,7 +856,7 @@ MCRT_API mcrt_status mcrt_scene_update_shapes(mcrt_scene s, const mcrt_shape* sh
         if (sh[i].startIdx != s->shapes[i].startIdx || sh[i].numTriangles != s->shapes[i].numTriangles)
             return fail(s->ctx, MCRT_ERROR_INVALID_ARG, "shape topology must not change");
     s->shapes.assign(sh, sh + n);
-    mcrt_status st = replace_array(s, &s->dShapes, sh, sizeof(mcrt_shape) * n);
+    mcrt_status st = replace_array(s, s->dShapes, sh, n);
     if (st != MCRT_OK) return st;
     HIPCHK(s->ctx, build_surface_records(s));   // startVertex may have moved
     return MCRT_OK;
@@ -931,11 +892,9 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
             return fail(ctx, MCRT_ERROR_INVALID_ARG, "two-level BVH build failed");
         hipSetDevice(ctx->device);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->dNodes) hipFree(s->dNodes);
-        if (s->dTris) hipFree(s->dTris);
-        s->dNodes = s->dTris = nullptr;
-        hipError_t e = hipMalloc(&s->dNodes, 64 * b2.numNodes);
-        if (e == hipSuccess) e = hipMemcpy(s->dNodes, b2.records.data(), 64 * b2.numNodes, hipMemcpyHostToDevice);
+        s->dNodes.reset();
+        hipError_t e = (hipError_t)s->dNodes.alloc(4 * b2.numNodes);
+        if (e == hipSuccess) e = hipMemcpy(s->dNodes.get(), b2.records.data(), 64 * b2.numNodes, hipMemcpyHostToDevice);
         if (e != hipSuccess) return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, std::string("BVH upload: ") + hipGetErrorString(e));
         s->numNodes = b2.numNodes;
         s->numTris = (uint32_t)n;
@@ -961,14 +920,10 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
         float4* nodes = nullptr;
         int depth = 0;
         const char* why = nullptr;
-        const hipError_t e = mcrt::gpu_build_sah((const mcrt_shape*)s->dShapes, first, (const uint32_t*)s->dIndices,
-                                                 (const float4*)s->dPositions, n, cost, bins, sah, ctx->stream, &nodes,
-                                                 &depth, &why);
+        const hipError_t e = mcrt::gpu_build_sah(s->dShapes.get(), first, s->dIndices.get(), s->dPositions.get(), n, cost,
+                                                 bins, sah, ctx->stream, &nodes, &depth, &why);
         if (e == hipSuccess) {
-            if (s->dNodes) hipFree(s->dNodes);
-            if (s->dTris) hipFree(s->dTris);
-            s->dTris = nullptr;
-            s->dNodes = nodes;
+            s->dNodes.adopt(nodes, 4 * (2 * n - 1));
             s->numNodes = 2 * n - 1;
             s->numTris = (uint32_t)n;
             s->bvhDepth = depth;
@@ -993,12 +948,9 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
         float4* nodes = nullptr;
         int depth = 0;
-        HIPCHK(ctx, mcrt::gpu_build_bvh((const mcrt_shape*)s->dShapes, first, (const uint32_t*)s->dIndices,
-                                        (const float4*)s->dPositions, n, ctx->stream, &nodes, &depth));
-        if (s->dNodes) hipFree(s->dNodes);
-        if (s->dTris) hipFree(s->dTris);
-        s->dTris = nullptr;
-        s->dNodes = nodes;
+        HIPCHK(ctx, mcrt::gpu_build_bvh(s->dShapes.get(), first, s->dIndices.get(), s->dPositions.get(), n, ctx->stream,
+                                        &nodes, &depth));
+        s->dNodes.adopt(nodes, 4 * (2 * n - 1));
         s->numNodes = 2 * n - 1;
         s->numTris = (uint32_t)n;
         s->bvhDepth = depth;
@@ -1025,11 +977,9 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
     if (buildMode == 4) s->builder = 4;   // the perf tree (3-axis SAH), not the reference's
     hipSetDevice(ctx->device);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    if (s->dNodes) hipFree(s->dNodes);
-    if (s->dTris) hipFree(s->dTris);
-    s->dNodes = s->dTris = nullptr;
-    hipError_t e = hipMalloc(&s->dNodes, 64 * bvh.numNodes);
-    if (e == hipSuccess) e = hipMemcpy(s->dNodes, bvh.nodes, 64 * bvh.numNodes, hipMemcpyHostToDevice);
+    s->dNodes.reset();
+    hipError_t e = (hipError_t)s->dNodes.alloc(4 * bvh.numNodes);
+    if (e == hipSuccess) e = hipMemcpy(s->dNodes.get(), bvh.nodes, 64 * bvh.numNodes, hipMemcpyHostToDevice);
     s->numNodes = bvh.numNodes;
     s->numTris = (uint32_t)bvh.numTris;
     s->bvhDepth = bvh.depth;
@@ -1045,9 +995,7 @@ static void apply_spill_cap(mcrt_scene s) {
     // test can drive a traversal past its capacity and check that the overflow is reported
     if (const char* tc = std::getenv("MCRT_TEST_SPILL_CAP")) needCap = std::max(0, std::atoi(tc) / 16 * 16);
     if (needCap != s->spillCap) {
-        if (s->dSpill) hipFree(s->dSpill);
-        s->dSpill = nullptr;
-        s->spillRays = 0;
+        s->dSpill.reset();
         s->spillCap = needCap;
     }
 }
@@ -1059,35 +1007,29 @@ static mcrt_status finish_accel(mcrt_scene s, std::chrono::steady_clock::time_po
     // depth fits the packet stack (at most 2 entries per internal level: 2 x depth, the leaves'
     // level).  MCRT_CAMERA_PACKETS=0 walks them per ray (A/B and tests: the results are the same bit
     // for bit).
-    const char* pe = std::getenv("MCRT_CAMERA_PACKETS");
     s->packets = !s->twoLevel && 2 * s->bvhDepth <= MCRT_PK_STACK && s->numNodes < (1u << 26) &&   // 32-bit offsets
-                 !(pe && std::atoi(pe) == 0);
-    if (!s->dScratch) HIPCHK(ctx, hipMalloc(&s->dScratch, 256 * sizeof(int)));
-    HIPCHK(ctx, hipMemset(s->dScratch, 0, 256 * sizeof(int)));
+                 env_int("MCRT_CAMERA_PACKETS", 1) != 0;
+    if (!s->dScratch) HIPCHK(ctx, s->dScratch.alloc(256));
+    HIPCHK(ctx, hipMemset(s->dScratch.get(), 0, 256 * sizeof(int)));
     if (!s->twoLevel) {
         // parent links of the leaves (occluder hints).  The origin-cell hint table is allocated on
         // its first use (ensure_hint_cell, sized for the tree); a rebuild drops the old one
-        mcrt::launch_leaf_parents((float4*)s->dNodes, (uint32_t)s->numNodes, ctx->stream);
+        mcrt::launch_leaf_parents(s->dNodes.get(), (uint32_t)s->numNodes, ctx->stream);
         HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        if (s->dHintCell) hipFree(s->dHintCell);
-        s->dHintCell = nullptr;
+        s->dHintCell.reset();
         s->hintAllocFailed = false;
     }
     // compact records for the per-ray walks (mcrt_traverse.h traverseQOct): depth-first flat trees;
     // MCRT_QUANT_NODES=0 keeps the 64-B records everywhere (A/B, tests).  A tree the converter
     // cannot take (LBVH numbering) or a device without room for it (~0.8 GB at 10 M triangles)
     // keeps the 64-B walk: the same answers.
-    if (s->dQNodes) hipFree(s->dQNodes);
-    s->dQNodes = nullptr;
-    s->qUnits = 0;
-    const char* qe = std::getenv("MCRT_QUANT_NODES");
-    if (!s->twoLevel && !(qe && std::atoi(qe) == 0)) {
+    s->dQNodes.reset();
+    if (!s->twoLevel && env_int("MCRT_QUANT_NODES", 1) != 0) {
         float4* q = nullptr;
         size_t units = 0;
-        const hipError_t e = mcrt::build_qnodes((const float4*)s->dNodes, (uint32_t)s->numNodes, &q, &units, ctx->stream);
+        const hipError_t e = mcrt::build_qnodes(s->dNodes.get(), (uint32_t)s->numNodes, &q, &units, ctx->stream);
         if (e == hipSuccess) {
-            s->dQNodes = q;
-            s->qUnits = units;
+            s->dQNodes.adopt(q, units);
         } else if (e != hipErrorNotSupported && e != hipErrorOutOfMemory) {
             return fail(ctx, MCRT_ERROR_DEVICE, std::string("compact records: ") + hipGetErrorString(e));
         } else {
@@ -1102,7 +1044,7 @@ static mcrt_status finish_accel(mcrt_scene s, std::chrono::steady_clock::time_po
     }
     // world bounds = the root record's two child boxes (or its triangle)
     float r[16];
-    HIPCHK(ctx, hipMemcpy(r, s->dNodes, 64, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(r, s->dNodes.get(), 64, hipMemcpyDeviceToHost));
     int32_t mark;
     std::memcpy(&mark, &r[12], 4);
     s->qRoot = mark >= 0 ? 0u : 1u;   // compact reference of the root: offset 0, leaf bit
@@ -1166,7 +1108,7 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
     }
     // the mesh keys are unchanged, so the surface records and their bases are too
     s->shapes.assign(sh, sh + n);
-    HIPCHK(ctx, hipMemcpy(s->dShapes, sh, sizeof(mcrt_shape) * n, hipMemcpyHostToDevice));
+    HIPCHK(ctx, hipMemcpy(s->dShapes.get(), sh, sizeof(mcrt_shape) * n, hipMemcpyHostToDevice));
     const mcrt::Bvh2lTop& top = s->top2l;
     const char* env = std::getenv("MCRT_TOP_BUILD");
     const bool forceHost = env && std::strcmp(env, "host") == 0;
@@ -1182,15 +1124,15 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
     if (device) {
         hipError_t e = hipSuccess;
         const char* why = nullptr;
-        void* dW2l = nullptr;
+        DevBuf<mcrt_mat4> dW2l;
         if (!s->topDev) e = mcrt::top_build_create(top, &s->topDev);
-        if (e == hipSuccess && world_to_local) e = upload(&dW2l, world_to_local, (size_t)n, ctx->stream);
+        if (e == hipSuccess && world_to_local) e = upload(dW2l, world_to_local, (size_t)n, ctx->stream);
         if (e == hipSuccess)
-            e = mcrt::top_build_run(s->topDev, (const mcrt_shape*)s->dShapes, (const mcrt_mat4*)dW2l,
-                                    (float4*)s->dNodes, ctx->stream, &depth, box, &why);
+            e = mcrt::top_build_run(s->topDev, s->dShapes.get(), dW2l.get(), s->dNodes.get(), ctx->stream, &depth, box,
+                                    &why);
         if (dW2l) {
             (void)hipStreamSynchronize(ctx->stream);
-            (void)hipFree(dW2l);
+            dW2l.reset();
         }
         if (e == hipSuccess) {
             path = 1;
@@ -1204,7 +1146,7 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
     if (path == 2) {
         std::vector<float> rec(16 * (size_t)s->topNodes);
         mcrt::build_bvh2l_top(top, s->shapes.data(), world_to_local, rec.data(), &depth, box);
-        HIPCHK(ctx, hipMemcpy(s->dNodes, rec.data(), 64 * (size_t)s->topNodes, hipMemcpyHostToDevice));
+        HIPCHK(ctx, hipMemcpy(s->dNodes.get(), rec.data(), 64 * (size_t)s->topNodes, hipMemcpyHostToDevice));
     }
     s->bvhDepth = depth;
     for (int a = 0; a < 3; ++a) { s->bbLo[a] = box[a]; s->bbHi[a] = box[3 + a]; }
@@ -1225,7 +1167,7 @@ MCRT_API mcrt_status mcrt_accel_info(mcrt_scene s, uint64_t* num_nodes, uint64_t
                                      uint32_t* num_triangles) {
     if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
     if (num_nodes) *num_nodes = s->numNodes;
-    if (device_bytes) *device_bytes = 64ull * s->numNodes + 16ull * s->qUnits;
+    if (device_bytes) *device_bytes = 64ull * s->numNodes + 16ull * s->dQNodes.size();
     if (build_ms) *build_ms = s->buildMs;
     if (num_triangles) *num_triangles = s->numTris;
     return MCRT_OK;
@@ -1250,7 +1192,7 @@ MCRT_API mcrt_status mcrt_accel_read_records(mcrt_scene s, float* out, uint64_t 
     mcrt_ctx ctx = s->ctx;
     hipSetDevice(ctx->device);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(out, s->dNodes, 64 * std::min<uint64_t>(max_records, s->numNodes), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(out, s->dNodes.get(), 64 * std::min<uint64_t>(max_records, s->numNodes), hipMemcpyDeviceToHost));
     return MCRT_OK;
 }
 
@@ -1432,52 +1374,25 @@ MCRT_API mcrt_status mcrt_event_destroy(mcrt_event ev) {
 // ---------------------------------------------------------------------------
 // frame buffer + integrator
 // ---------------------------------------------------------------------------
-static void bset_free(BdptSet& b) {
-    void* ptrs[] = {b.camV,   b.lightV, b.slots,  b.splat,  b.camCount, b.lightCount, b.bdptCounters,
-                    b.bqO[0], b.bqO[1], b.bqD[0], b.bqD[1], b.bqT[0], b.bqT[1], b.bHits, b.cO, b.cD, b.cL, b.spill,
-                    b.lkey, b.lkey2, b.lslot, b.lperm, b.ekey, b.ekey2, b.eslot, b.eperm, b.sortTmp,
-                    b.splatList, b.splatAux, b.suspend, b.suspendCnt};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
-    b = BdptSet();
-}
-
 static void fb_free_bdpt(mcrt_framebuffer fb) {
-    for (auto& b : fb->bset) bset_free(b);
-    if (fb->sampLight) hipFree(fb->sampLight);
+    for (auto& b : fb->bset) b = BdptSet();
+    fb->sampLight.reset();
     if (fb->bdptConnect) hipEventDestroy(fb->bdptConnect);
     fb->bdptConnect = nullptr;
-    fb->camV = fb->lightV = fb->sampLight = fb->slots = fb->splat = fb->bHits = fb->cO = fb->cD = fb->cL = nullptr;
-    fb->camCount = fb->lightCount = fb->bdptCounters = nullptr;
-    for (int i = 0; i < 2; ++i) fb->bqO[i] = fb->bqD[i] = fb->bqT[i] = nullptr;
     fb->bdptDepth = 0;
 }
 
 static void slot_free(FrameSlot& k) {
     if (k.stream) hipStreamSynchronize(k.stream);
-    void* ptrs[] = {k.radiance, k.hitsP, k.hitsE, k.eO[0], k.eO[1], k.eD[0], k.eD[1], k.eT[0], k.eT[1],
-                    k.sO,       k.sD,    k.sL,    k.counters, k.spill, k.tileCost, k.tileOrder,
-                    k.suspend,  k.suspendCnt};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
     if (k.done) hipEventDestroy(k.done);
     if (k.free) hipEventDestroy(k.free);
     if (k.stream) hipStreamDestroy(k.stream);
     k = FrameSlot();
 }
 
+// the slots' streams and events and every slot and set; the frame buffer's own planes go with it
 static void fb_free(mcrt_framebuffer fb) {
     for (auto& k : fb->slot) slot_free(k);
-    for (auto& w : fb->waveClk) {
-        if (w) hipFree(w);
-        w = nullptr;
-    }
-    void* ptrs[] = {fb->wsum, fb->wts, fb->image, fb->denoised, fb->display, fb->hintPix, fb->guideNormal,
-                    fb->guideAlbedo, fb->moments, fb->atrousC[0], fb->atrousC[1], fb->atrousV[0], fb->atrousV[1],
-                    fb->tColour[0], fb->tColour[1], fb->tMoments[0], fb->tMoments[1], fb->tNormal[0], fb->tNormal[1],
-                    fb->tVar};
-    for (void* p : ptrs)
-        if (p) hipFree(p);
     fb_free_bdpt(fb);
 }
 
@@ -1486,17 +1401,17 @@ static void fb_free(mcrt_framebuffer fb) {
 static hipError_t slot_alloc(FrameSlot& k, size_t N, size_t T, int frames = 1, size_t Q = 0) {
     hipError_t e = hipSuccess;
     if (Q < N) Q = N;
-    auto A = [&](auto** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc((void**)p, bytes);
+    auto A = [&](auto& buf, size_t count) {
+        if (e == hipSuccess) e = (hipError_t)buf.alloc(count);
     };
-    A(&k.radiance, 16 * N * frames);
-    A(&k.hitsP, 16 * std::max(N, T) * frames);
-    A(&k.hitsE, 16 * Q);
-    for (int i = 0; i < 2; ++i) { A(&k.eO[i], 16 * Q); A(&k.eD[i], 16 * Q); A(&k.eT[i], 16 * Q); }
-    A(&k.sO, 16 * Q);
-    A(&k.sD, 16 * Q);
-    A(&k.sL, 16 * Q);
-    A(&k.counters, SLOT_COUNTER_BYTES);
+    A(k.radiance, N * frames);
+    A(k.hitsP, std::max(N, T) * frames);
+    A(k.hitsE, Q);
+    for (int i = 0; i < 2; ++i) { A(k.eO[i], Q); A(k.eD[i], Q); A(k.eT[i], Q); }
+    A(k.sO, Q);
+    A(k.sD, Q);
+    A(k.sL, Q);
+    A(k.counters, SLOT_COUNTER_BYTES / sizeof(int));
     k.frames = frames;
     k.queueCap = Q;
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&k.stream, hipStreamNonBlocking);
@@ -1504,27 +1419,11 @@ static hipError_t slot_alloc(FrameSlot& k, size_t N, size_t T, int frames = 1, s
     if (e == hipSuccess) e = hipEventCreateWithFlags(&k.free, hipEventDisableTiming);
     // zero-fills on the slot's own stream, ahead of its first launch; `done` covers them for
     // readers on other streams (ctx_wait_slots) before the slot's first frame records it
-    if (e == hipSuccess) e = hipMemsetAsync(k.radiance, 0, 16 * N * frames, k.stream);
-    if (e == hipSuccess) e = hipMemsetAsync(k.counters, 0, SLOT_COUNTER_BYTES, k.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(k.radiance.get(), 0, 16 * N * frames, k.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(k.counters.get(), 0, SLOT_COUNTER_BYTES, k.stream);
     if (e == hipSuccess) e = hipEventRecord(k.done, k.stream);
     if (e != hipSuccess) slot_free(k);
     return e;
-}
-
-// The fb's radiance/queue/counter fields view slot k (the last rendered frame).
-static void fb_bind(mcrt_framebuffer fb, int k) {
-    FrameSlot& s = fb->slot[k];
-    fb->cur = k;
-    fb->radiance = s.radiance;
-    fb->hitsP = s.hitsP;
-    fb->hitsE = s.hitsE;
-    for (int i = 0; i < 2; ++i) { fb->eO[i] = s.eO[i]; fb->eD[i] = s.eD[i]; fb->eT[i] = s.eT[i]; }
-    fb->sO = s.sO;
-    fb->sD = s.sD;
-    fb->sL = s.sL;
-    fb->counters = s.counters;
-    fb->lastMaxDepth = s.lastMaxDepth;
-    fb->lastPixels = s.lastPixels;
 }
 
 // Host reads and context-stream work that touch the slots: all slot streams first.
@@ -1550,50 +1449,39 @@ static hipError_t bset_alloc(BdptSet& b, size_t N, size_t NQ, int D, int frames,
     N *= frames;    // every per-frame array holds the batch's frames
     NQ *= frames;
     hipError_t e = hipSuccess;
-    auto A = [&](auto** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc((void**)p, bytes);
+    auto A = [&](auto& buf, size_t count) {
+        if (e == hipSuccess) e = (hipError_t)buf.alloc(count);
     };
-    A(&b.camV, 16 * N * BDPT_VERTEX_PLANES * (D + 2));
-    A(&b.lightV, 16 * N * BDPT_VERTEX_PLANES * (D + 1));
-    A(&b.slots, 16 * N * (C - D));
-    A(&b.splat, 16 * N);
-    A(&b.camCount, 4 * N);
-    A(&b.lightCount, 4 * N);
-    A(&b.bdptCounters, 64 * sizeof(int));
-    for (int i = 0; i < 2; ++i) { A(&b.bqO[i], 32 * NQ); A(&b.bqD[i], 32 * NQ); A(&b.bqT[i], 32 * NQ); }
-    A(&b.bHits, 32 * NQ);
-    A(&b.cO, 16 * N * C);
-    A(&b.cD, 16 * N * C);
-    A(&b.cL, 16 * N * C);
-    A(&b.lkey, 4 * NQ);
-    A(&b.lkey2, 4 * NQ);
-    A(&b.lslot, 4 * NQ);
-    A(&b.lperm, 4 * NQ);
-    A(&b.ekey, 8 * N);
-    A(&b.ekey2, 8 * N);
-    A(&b.eslot, 8 * N);
-    A(&b.eperm, 8 * N);
-    b.sortTmpBytes = mcrt::bdpt_light_sort_temp_bytes((int)std::max(NQ, 2 * N));
-    A(&b.sortTmp, b.sortTmpBytes);
+    A(b.camV, N * BDPT_VERTEX_PLANES * (D + 2));
+    A(b.lightV, N * BDPT_VERTEX_PLANES * (D + 1));
+    A(b.slots, N * (C - D));
+    A(b.splat, N);
+    A(b.camCount, N);
+    A(b.lightCount, N);
+    A(b.bdptCounters, 64);
+    for (int i = 0; i < 2; ++i) { A(b.bqO[i], 2 * NQ); A(b.bqD[i], 2 * NQ); A(b.bqT[i], 2 * NQ); }
+    A(b.bHits, 2 * NQ);
+    A(b.cO, N * C);
+    A(b.cD, N * C);
+    A(b.cL, N * C);
+    A(b.lkey, NQ);
+    A(b.lkey2, NQ);
+    A(b.lslot, NQ);
+    A(b.lperm, NQ);
+    A(b.ekey, 2 * N);
+    A(b.ekey2, 2 * N);
+    A(b.eslot, 2 * N);
+    A(b.eperm, 2 * N);
+    A(b.sortTmp, mcrt::bdpt_light_sort_temp_bytes((int)std::max(NQ, 2 * N)));
     // zero-fills on the stream of the set's frames (st, its slot's), ahead of the first launch
     // that writes the set: a 3 GB vertex-plane memset on another stream could still be running
     // under k_bdpt_start and zero its vertices
-    if (e == hipSuccess) e = hipMemsetAsync(b.splat, 0, 16 * N, st);
-    if (e == hipSuccess) e = hipMemsetAsync(b.camV, 0, 16 * N * BDPT_VERTEX_PLANES * (D + 2), st);
-    if (e == hipSuccess) e = hipMemsetAsync(b.lightV, 0, 16 * N * BDPT_VERTEX_PLANES * (D + 1), st);
-    if (e != hipSuccess) bset_free(b);
+    if (e == hipSuccess) e = hipMemsetAsync(b.splat.get(), 0, 16 * N, st);
+    if (e == hipSuccess) e = hipMemsetAsync(b.camV.get(), 0, 16 * N * BDPT_VERTEX_PLANES * (D + 2), st);
+    if (e == hipSuccess) e = hipMemsetAsync(b.lightV.get(), 0, 16 * N * BDPT_VERTEX_PLANES * (D + 1), st);
+    if (e != hipSuccess) b = BdptSet();
     else b.frames = frames;
     return e;
-}
-
-// The fb's BDPT views show set k (the last BDPT frame).
-static void fb_bind_bdpt(mcrt_framebuffer fb, int k) {
-    const BdptSet& b = fb->bset[k];
-    fb->bdptSet = k;
-    fb->camV = b.camV; fb->lightV = b.lightV; fb->slots = b.slots; fb->splat = b.splat;
-    fb->camCount = b.camCount; fb->lightCount = b.lightCount; fb->bdptCounters = b.bdptCounters;
-    for (int i = 0; i < 2; ++i) { fb->bqO[i] = b.bqO[i]; fb->bqD[i] = b.bqD[i]; fb->bqT[i] = b.bqT[i]; }
-    fb->bHits = b.bHits; fb->cO = b.cO; fb->cD = b.cD; fb->cL = b.cL;
 }
 
 // RTBDPTPass::createBuffers (RTBDPTPass.cpp:442-479), sized for max depth D: set k of the
@@ -1610,11 +1498,11 @@ static hipError_t fb_ensure_bdpt(mcrt_framebuffer fb, int D, int k, int frames, 
             if (sl.stream) hipStreamSynchronize(sl.stream);
         hipStreamSynchronize(fb->ctx->stream);
         fb_free_bdpt(fb);
-        hipError_t e = hipMalloc(&fb->sampLight, 16 * N * D);
+        hipError_t e = (hipError_t)fb->sampLight.alloc(N * D);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&fb->bdptConnect, hipEventDisableTiming);
         // zeroed on this frame's stream; every connect launch (the planes' only reader and writer)
         // waits for bdptConnect, recorded here first
-        if (e == hipSuccess) e = hipMemsetAsync(fb->sampLight, 0, 16 * N * D, st);
+        if (e == hipSuccess) e = hipMemsetAsync(fb->sampLight.get(), 0, 16 * N * D, st);
         if (e == hipSuccess) e = hipEventRecord(fb->bdptConnect, st);
         if (e != hipSuccess) { fb_free_bdpt(fb); return e; }
         fb->bdptDepth = D;
@@ -1624,8 +1512,7 @@ static hipError_t fb_ensure_bdpt(mcrt_framebuffer fb, int D, int k, int frames, 
         for (auto& sl : fb->slot)
             if (sl.stream) hipStreamSynchronize(sl.stream);
         hipStreamSynchronize(fb->ctx->stream);
-        bset_free(bs);
-        bs = BdptSet{};
+        bs = BdptSet();
     }
     if (!bs.camV) return bset_alloc(bs, N, bdpt_queue_cap(fb), D, frames, st);
     return hipSuccess;
@@ -1642,26 +1529,18 @@ MCRT_API mcrt_status mcrt_framebuffer_create(mcrt_ctx ctx, uint32_t width, uint3
     fb->N = (size_t)width * height;
     const size_t N = fb->N;
     hipError_t e = hipSuccess;
-    auto A = [&](auto** p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc((void**)p, bytes);
-    };
-    A(&fb->wsum, 16 * N);
-    A(&fb->wts, 4 * N);
-    A(&fb->image, 16 * N);
-    A(&fb->denoised, 16 * N);
-    A(&fb->display, 16 * N);
-    A(&fb->hintPix, 4 * N);
+    for (auto* img : {&fb->wsum, &fb->image, &fb->denoised, &fb->display})
+        if (e == hipSuccess) e = (hipError_t)img->alloc(N);
+    if (e == hipSuccess) e = (hipError_t)fb->wts.alloc(N);
+    if (e == hipSuccess) e = (hipError_t)fb->hintPix.alloc(N);
     fb->slot.resize(MCRT_MAX_FRAMES_IN_FLIGHT);
     if (e == hipSuccess) e = slot_alloc(fb->slot[0], N, N);   // one frame: hits by pixel
-    if (e == hipSuccess) fb_bind(fb, 0);
     // zero-fills on slot 0's (private) stream, finished before the frame buffer is handed out:
     // only this buffer's work is waited for, not the device (other contexts, a captured caller stream)
-    if (e == hipSuccess) e = hipMemsetAsync(fb->wsum, 0, 16 * N, fb->slot[0].stream);
-    if (e == hipSuccess) e = hipMemsetAsync(fb->wts, 0, 4 * N, fb->slot[0].stream);
-    if (e == hipSuccess) e = hipMemsetAsync(fb->image, 0, 16 * N, fb->slot[0].stream);
-    if (e == hipSuccess) e = hipMemsetAsync(fb->denoised, 0, 16 * N, fb->slot[0].stream);
-    if (e == hipSuccess) e = hipMemsetAsync(fb->display, 0, 16 * N, fb->slot[0].stream);
-    if (e == hipSuccess) e = fill_hints(fb->hintPix, N, 1u << 22, fb->slot[0].stream);   // no hints
+    for (auto* img : {&fb->wsum, &fb->image, &fb->denoised, &fb->display})
+        if (e == hipSuccess) e = hipMemsetAsync(img->get(), 0, 16 * N, fb->slot[0].stream);
+    if (e == hipSuccess) e = hipMemsetAsync(fb->wts.get(), 0, 4 * N, fb->slot[0].stream);
+    if (e == hipSuccess) e = fill_hints(fb->hintPix.get(), N, 1u << 22, fb->slot[0].stream);   // no hints
     if (e == hipSuccess) e = hipStreamSynchronize(fb->slot[0].stream);
     if (e != hipSuccess) {
         fb_free(fb);
@@ -1731,33 +1610,29 @@ static bool frame_args(mcrt_framebuffer fb, const mcrt_frame_params* p, FrameArg
 // (mcrt_render_frames) rather than by more slots: 4 slots of 1/8-image frames reach 0.49 ms per
 // frame at N = 8, 2 slots of 16-frame batches 0.25.
 // MCRT_WAVE_CLOCK=1: record per-workgroup clocks of launch `which` (grid of `blocks`) on stream st
+static bool wave_clock_on() {
+    static const bool on = env_int("MCRT_WAVE_CLOCK", 0) != 0;
+    return on;
+}
 static uint32_t* wave_clock_buf(mcrt_framebuffer fb, int which, size_t blocks, hipStream_t st) {
-    static const bool on = [] { const char* e = std::getenv("MCRT_WAVE_CLOCK"); return e && std::atoi(e) != 0; }();
-    if (!on) return nullptr;
-    if (fb->waveClkBlocks[which] < blocks) {
-        hipStreamSynchronize(st);
-        if (fb->waveClk[which]) hipFree(fb->waveClk[which]);
-        fb->waveClk[which] = nullptr;
-        fb->waveClkBlocks[which] = 0;
-        if (hipMalloc(&fb->waveClk[which], 8 * blocks) != hipSuccess) { hipGetLastError(); return nullptr; }
-        fb->waveClkBlocks[which] = blocks;
-    }
-    hipMemsetAsync(fb->waveClk[which], 0, 8 * fb->waveClkBlocks[which], st);
-    return fb->waveClk[which];
+    if (!wave_clock_on()) return nullptr;
+    DevBuf<uint32_t>& clk = fb->waveClk[which];
+    if (clk.grow(2 * blocks, st) != 0) { hipGetLastError(); return nullptr; }
+    hipMemsetAsync(clk.get(), 0, 4 * clk.size(), st);
+    return clk.get();
 }
 
 #define MCRT_LPT_SHADE_MAX_PATHS 16000000
 // MCRT_LONGEST_FIRST=0: camera / first-shading tiles in plain tile order (A/B)
 static bool longest_first() {
-    static const bool on = [] { const char* e = std::getenv("MCRT_LONGEST_FIRST"); return !(e && std::atoi(e) == 0); }();
+    static const bool on = env_int("MCRT_LONGEST_FIRST", 1) != 0;
     return on;
 }
 
 static int frames_in_flight(mcrt_framebuffer fb, const FrameArgs& f) {
     // MCRT_WAVE_CLOCK=1: one frame in flight -- the clock buffers are per frame buffer, so two slots'
     // launches in flight would write the same per-workgroup entries
-    static const bool clocks = [] { const char* e = std::getenv("MCRT_WAVE_CLOCK"); return e && std::atoi(e) != 0; }();
-    if (clocks) return 1;
+    if (wave_clock_on()) return 1;
     int n = fb->framesInFlight;
     if (n <= 0) n = 2;
     return std::max(1, std::min(n, MCRT_MAX_FRAMES_IN_FLIGHT));
@@ -1766,43 +1641,37 @@ static int frames_in_flight(mcrt_framebuffer fb, const FrameArgs& f) {
 // RTBDPTPass::update (RTBDPTPass.cpp:67-128): start vertices, D+1 rounds of (trace, vertex),
 // connections + MIS, visibility, gather.  Rays of both subpaths share one compacted queue.
 static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_frame_params* p,
-                               const FrameArgs& f, int k, hipStream_t st) {
-    // frame slot k on stream st: per-frame arrays of set k; the connect launch (the only reader
+                               const FrameArgs& f, int k, FrameSlot& slot) {
+    // frame slot k on its stream: per-frame arrays of set k; the connect launch (the only reader
     // and writer of the shared sampled-light-vertex planes) waits for the previous frame's connect
     mcrt_ctx ctx = s->ctx;
+    hipStream_t st = slot.stream;
     const int D = p->max_depth;
     const int B = f.batch;   // frames of this call (mcrt_render_frames): path = k * W*H + pixel
     HIPCHK(ctx, fb_ensure_bdpt(fb, D, k, B, st));
-    fb_bind_bdpt(fb, k);
-    fb->lastMaxDepth = D;
-    fb->lastPixels = 0;
+    BdptSet& bs = fb->bset[k];
+    fb->bdptSet = k;
+    slot.lastMaxDepth = D;
+    slot.lastPixels = 0;
     fb->bands = f;
     fb->haveBands = true;
     fb->lastIntegrator = MCRT_INTEGRATOR_BDPT;
     fb->bdptBatch = B;
-    mcrt_camera* dCam = reinterpret_cast<mcrt_camera*>(fb->counters + 128);
+    mcrt_camera* dCam = slot.cameras();
     HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(fb->bdptCounters, 0, 64 * sizeof(int), st));
+    HIPCHK(ctx, hipMemsetAsync(bs.bdptCounters.get(), 0, 64 * sizeof(int), st));
     if (s->numLights == 0) {   // RTBDPTPass.cpp:69: no lights -> pass skipped
-        HIPCHK(ctx, hipMemsetAsync(fb->radiance, 0, 16 * fb->N * (size_t)B, st));
+        HIPCHK(ctx, hipMemsetAsync(slot.radiance.get(), 0, 16 * fb->N * (size_t)B, st));
         return MCRT_OK;
     }
     const size_t N = fb->N * (size_t)B, C = (size_t)bdpt_max_connections(D);   // N: paths of the batch
-    BdptSet& bs = fb->bset[k];
     const size_t NQ = bdpt_queue_cap(fb) * (size_t)B;
     // spill columns: one per ray of the widest closest-hit launch (2 NQ) and one per wave of the
     // grid-stride visibility launch (mcrt::BDPT_VIS_MAX_WAVES)
     const size_t spillWords = (std::max(2 * NQ, (size_t)mcrt::BDPT_VIS_MAX_WAVES * 64) + 63) / 64 * 64 * (size_t)s->spillCap;
-    if (bs.spillWords < spillWords) {
-        HIPCHK(ctx, hipStreamSynchronize(st));
-        if (bs.spill) hipFree(bs.spill);
-        bs.spill = nullptr;
-        bs.spillWords = 0;
-        HIPCHK(ctx, hipMalloc(&bs.spill, spillWords * sizeof(uint32_t)));
-        bs.spillWords = spillWords;
-    }
+    HIPCHK(ctx, bs.spill.grow(spillWords, st));
     TraceCtx tcs = trace_ctx(s);
-    tcs.spill = bs.spill;
+    tcs.spill = bs.spill.get();
     const SceneArgs sa = scene_args(s);
     // the closest-hit launches' stop rule (TraceCtx::walkCap): a traced queue holds at most
     // max(bandQ, nSort) = nSort rays (below)
@@ -1810,34 +1679,27 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
     TraceCtx tce = tcs;
     if (wcap > 0) {
         const size_t need = (size_t)std::min((size_t)2 * N, (size_t)2 * (size_t)f.numTiles * 64 * B);
-        if (bs.suspendCap < need) {
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            if (bs.suspend) hipFree(bs.suspend);
-            bs.suspend = nullptr;
-            bs.suspendCap = 0;
-            HIPCHK(ctx, hipMalloc(&bs.suspend, sizeof(float4) * MCRT_SUSPEND_F4 * need));
-            bs.suspendCap = need;
-        }
-        if (!bs.suspendCnt) HIPCHK(ctx, hipMalloc(&bs.suspendCnt, 64 * sizeof(int)));
-        HIPCHK(ctx, hipMemsetAsync(bs.suspendCnt, 0, 64 * sizeof(int), st));
+        HIPCHK(ctx, bs.suspend.grow(MCRT_SUSPEND_F4 * need, st));
+        if (!bs.suspendCnt) HIPCHK(ctx, bs.suspendCnt.alloc(64));
+        HIPCHK(ctx, hipMemsetAsync(bs.suspendCnt.get(), 0, 64 * sizeof(int), st));
         tce.walkCap = wcap;
         tce.walkLanes = walk_lanes();
-        tce.suspend = bs.suspend;
+        tce.suspend = bs.suspend.get();
     }
     BdptArgs b{};
-    b.camV = fb->camV;
-    b.lightV = fb->lightV;
-    b.camCount = fb->camCount;
-    b.lightCount = fb->lightCount;
-    b.sampLight = fb->sampLight;
-    b.slots = fb->slots;
-    b.splat = fb->splat;
+    b.camV = bs.camV.get();
+    b.lightV = bs.lightV.get();
+    b.camCount = bs.camCount.get();
+    b.lightCount = bs.lightCount.get();
+    b.sampLight = fb->sampLight.get();
+    b.slots = bs.slots.get();
+    b.splat = bs.splat.get();
     b.ownSlots = (int)C - D;
     // (planes at another stride hold other data; another band's paths were never written)
     // the light-start rays are traced in cell order (keys from k_bdpt_start, rocPRIM sort below):
     // k_extend 3.07 -> 2.82 ms per frame at 1080p (profiles/r04/ab/README.txt)
-    b.lightKey = bs.lkey;
-    b.lightSlot = bs.lslot;
+    b.lightKey = bs.lkey.get();
+    b.lightSlot = bs.lslot.get();
     // the bounce queues that are traced (depths 1..D) in octant / origin-cell order: keys written by
     // k_bdpt_vertex, sorted below, walked through the permutation by k_extend
     b.extKey = nullptr;
@@ -1848,14 +1710,14 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
         b.keyScale[a] = ext > 0.0f ? (a == 1 ? 8.0f : 32.0f) / ext : 0.0f;
     }
     b.cams = dCam;
-    b.connCount = fb->bdptCounters + BDPT_CNT_CONN;
-    b.connO = fb->cO;
-    b.connD = fb->cD;
-    b.connL = fb->cL;
+    b.connCount = bs.bdptCounters.get() + BDPT_CNT_CONN;
+    b.connO = bs.cO.get();
+    b.connD = bs.cD.get();
+    b.connL = bs.cL.get();
     b.lightInVertex = bdpt_light_in_vertex();
     BdptArgs bk = b;   // the vertex launches whose output queue is traced
-    bk.extKey = bs.ekey;
-    bk.extSlot = bs.eslot;
+    bk.extKey = bs.ekey.get();
+    bk.extSlot = bs.eslot.get();
     // a bounce queue holds at most the band's camera + light rays (2 per path of this rank's tiles),
     // appended compactly from slot 0: sort (and clear) only that range, not the whole frame's -- a
     // rank of a band split would otherwise sort 8 x its own rays at N = 8
@@ -1865,7 +1727,7 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
     // most one per path, so it is sorted (and its keys cleared) over bandQ slots, not 2 x bandQ
     auto sortRange = [&](int tracedAt) { return tracedAt == D + 1 ? std::min(nSort, bandQ) : nSort; };
     auto clearKeys = [&](int n) {   // unwritten slots sort last (stable sort: after the written ones)
-        return hipMemsetAsync(bs.ekey, 0xFF, 4 * (size_t)n, st);
+        return hipMemsetAsync(bs.ekey.get(), 0xFF, 4 * (size_t)n, st);
     };
     b.depth0Const = bs.constStride == N && bs.constBand[0] == f.bandRows && bs.constBand[1] == f.numBands &&
                     bs.constBand[2] == f.bandIndex ? 1 : 0;
@@ -1873,13 +1735,14 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
     bs.constBand[0] = f.bandRows;
     bs.constBand[1] = f.numBands;
     bs.constBand[2] = f.bandIndex;
-    int* cnt = fb->bdptCounters;   // [d] ray queue of depth d (d <= D + 1 <= 33), BDPT_CNT_* below
+    float4* const bHits = bs.bHits.get();
+    int* cnt = bs.bdptCounters.get();   // [d] ray queue of depth d (d <= D + 1 <= 33), BDPT_CNT_* below
     auto queue = [&](int d) {
         BdptQueue q;
         q.count = cnt + d;
-        q.o = fb->bqO[d & 1];
-        q.d = fb->bqD[d & 1];
-        q.t = fb->bqT[d & 1];
+        q.o = bs.bqO[d & 1].get();
+        q.d = bs.bqD[d & 1].get();
+        q.t = bs.bqT[d & 1].get();
         return q;
     };
     const bool bandSplit = f.numBands > 1;
@@ -1888,16 +1751,9 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
         // the splats landing in other ranks' rows go to a list (at most D per path: t = 1, s = 2..D+1);
         // the rank's own rows are zeroed by k_bdpt_start, the other rows of its plane stay unused
         const size_t cap = (size_t)D * (size_t)bandQ;
-        if (bs.splatListCap < cap || !bs.splatAux) {
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            if (bs.splatList) hipFree(bs.splatList);
-            bs.splatList = nullptr;
-            bs.splatListCap = 0;
-            HIPCHK(ctx, hipMalloc(&bs.splatList, 16 * cap));
-            bs.splatListCap = cap;
-            if (!bs.splatAux) HIPCHK(ctx, hipMalloc(&bs.splatAux, 128 * sizeof(int)));
-        }
-        b.splatList = bs.splatList;
+        HIPCHK(ctx, bs.splatList.grow(cap, st));
+        if (!bs.splatAux) HIPCHK(ctx, bs.splatAux.alloc(128));
+        b.splatList = bs.splatList.get();
         b.splatListCount = cnt + BDPT_CNT_SPLATS;
         b.splatListCap = (int)std::min(cap, (size_t)INT32_MAX);
         b.splatW = (int)f.W;
@@ -1906,7 +1762,7 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
         b.splatBands = f.numBands;
         b.splatBand = f.bandIndex;
     } else if (bandSplit) {   // splats of this rank's light paths land in any pixel: clear the whole buffer
-        mcrt::launch_bdpt_clear_splat((int)N, fb->splat, st);
+        mcrt::launch_bdpt_clear_splat((int)N, bs.splat.get(), st);
     }
     // depth 0: camera rays (coherent, 8x8 tiles in order) in the first half of queue 0's buffers
     // with their own count, light rays in the second half with count [0]; ONE launch traces both,
@@ -1923,48 +1779,48 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
     }
     {
         TraceCtx tcc = packet_ctx(s);
-        tcc.spill = bs.spill;
+        tcc.spill = bs.spill.get();
         Timed t(ctx, K_EXTEND, camQ.count, 0, st);
         // exactly the slots k_bdpt_start wrote (the light queue's count, f.numTiles x 64 x B <= NQ)
-        HIPCHK(ctx, mcrt::bdpt_light_sort(bs.lkey, bs.lkey2, bs.lslot, bs.lperm, f.numTiles * 64 * B, bs.sortTmp,
-                                          bs.sortTmpBytes, st));
+        HIPCHK(ctx, mcrt::bdpt_light_sort(bs.lkey.get(), bs.lkey2.get(), bs.lslot.get(), bs.lperm.get(), f.numTiles * 64 * B,
+                                          bs.sortTmp.get(), bs.sortTmp.size(), st));
         TraceCtx tl = tce;
-        tl.suspendCount = wcap > 0 ? bs.suspendCnt : nullptr;
-        mcrt::launch_extend_pair(tcc, tl, camQ.count, camQ.o, camQ.d, fb->bHits, lightQ.count, lightQ.o, lightQ.d,
-                                 fb->bHits + NQ, bandQ, bandQ, st, bs.lperm);   // grids sized to the band
-        if (wcap > 0) mcrt::launch_walk_resume(tl, lightQ.o, lightQ.d, fb->bHits + NQ, bandQ, st);
+        tl.suspendCount = wcap > 0 ? bs.suspendCnt.get() : nullptr;
+        mcrt::launch_extend_pair(tcc, tl, camQ.count, camQ.o, camQ.d, bHits, lightQ.count, lightQ.o, lightQ.d,
+                                 bHits + NQ, bandQ, bandQ, st, bs.lperm.get());   // grids sized to the band
+        if (wcap > 0) mcrt::launch_walk_resume(tl, lightQ.o, lightQ.d, bHits + NQ, bandQ, st);
     }
     HIPCHK(ctx, clearKeys(sortRange(2)));   // queue 1 is traced (D >= 1), at round 2
     {
         Timed t(ctx, K_BDPT_VERTEX, camQ.count, 0, st);
-        mcrt::launch_bdpt_vertex(sa, f, bk, 1, camQ, fb->bHits, queue(1), bandQ, st);
+        mcrt::launch_bdpt_vertex(sa, f, bk, 1, camQ, bHits, queue(1), bandQ, st);
     }
     {
         Timed t(ctx, K_BDPT_VERTEX, lightQ.count, 0, st);
-        mcrt::launch_bdpt_vertex(sa, f, bk, 1, lightQ, fb->bHits + NQ, queue(1), bandQ, st);
+        mcrt::launch_bdpt_vertex(sa, f, bk, 1, lightQ, bHits + NQ, queue(1), bandQ, st);
     }
     for (int d = 2; d <= D + 1; ++d) {
         const BdptQueue qIn = queue(d - 1), qOut = queue(d);
         {
             Timed t(ctx, K_EXTEND, qIn.count, 0, st);
             const int nQ = sortRange(d);
-            HIPCHK(ctx, mcrt::bdpt_light_sort(bs.ekey, bs.ekey2, bs.eslot, bs.eperm, nQ, bs.sortTmp,
-                                              bs.sortTmpBytes, st, 16));
+            HIPCHK(ctx, mcrt::bdpt_light_sort(bs.ekey.get(), bs.ekey2.get(), bs.eslot.get(), bs.eperm.get(), nQ,
+                                              bs.sortTmp.get(), bs.sortTmp.size(), st, 16));
             TraceCtx te = tce;
-            te.suspendCount = wcap > 0 ? bs.suspendCnt + d : nullptr;
-            mcrt::launch_extend(te, qIn.count, qIn.o, qIn.d, fb->bHits, nQ, st, bs.eperm);
-            if (wcap > 0) mcrt::launch_walk_resume(te, qIn.o, qIn.d, fb->bHits, nQ, st);
+            te.suspendCount = wcap > 0 ? bs.suspendCnt.get() + d : nullptr;
+            mcrt::launch_extend(te, qIn.count, qIn.o, qIn.d, bHits, nQ, st, bs.eperm.get());
+            if (wcap > 0) mcrt::launch_walk_resume(te, qIn.o, qIn.d, bHits, nQ, st);
         }
         const bool traced = d <= D;   // queue d is traced by the next round
         if (traced) HIPCHK(ctx, clearKeys(sortRange(d + 1)));
         Timed t(ctx, K_BDPT_VERTEX, qIn.count, 0, st);
-        mcrt::launch_bdpt_vertex(sa, f, traced ? bk : b, d, qIn, fb->bHits, qOut, nSort, st);
+        mcrt::launch_bdpt_vertex(sa, f, traced ? bk : b, d, qIn, bHits, qOut, nSort, st);
     }
     BdptQueue cq;
     cq.count = cnt + BDPT_CNT_CONN;
-    cq.o = fb->cO;
-    cq.d = fb->cD;
-    cq.t = fb->cL;
+    cq.o = bs.cO.get();
+    cq.d = bs.cD.get();
+    cq.t = bs.cL.get();
     HIPCHK(ctx, hipStreamWaitEvent(st, fb->bdptConnect, 0));   // sampled-light planes in frame order
     {
         Timed t(ctx, K_BDPT_CONNECT, nullptr, (int64_t)f.numTiles * 64 * B, st);
@@ -1981,10 +1837,10 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
         fb->bdptPendingGather = true;
     } else {
         Timed t(ctx, K_BDPT_GATHER, nullptr, (int64_t)f.numTiles * 64 * B, st);
-        mcrt::launch_bdpt_gather(f, b, fb->radiance, nullptr, 0, st);
+        mcrt::launch_bdpt_gather(f, b, slot.radiance.get(), nullptr, 0, st);
     }
     HIPCHK(ctx, hipGetLastError());
-    fb->lastPixels = (int64_t)f.numTiles * 64 * B;
+    slot.lastPixels = (int64_t)f.numTiles * 64 * B;
     return MCRT_OK;
 }
 
@@ -2053,12 +1909,10 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
             HIPCHK(ctx, slot_alloc(slot, fb->N, bdpt_queue_cap(fb), count));
         }
         HIPCHK(ctx, hipStreamWaitEvent(slot.stream, slot.free, 0));
-        fb_bind(fb, ks);
+        fb->cur = ks;
         fb->next = (ks + 1) % (fb->bdptOneSet ? 1 : S);
         slot.lastBatch = count;
-        const mcrt_status r = render_bdpt(s, fb, cam, p, f, ks, slot.stream);
-        slot.lastMaxDepth = fb->lastMaxDepth;
-        slot.lastPixels = fb->lastPixels;
+        const mcrt_status r = render_bdpt(s, fb, cam, p, f, ks, slot);
         hipEventRecord(slot.done, slot.stream);
         return r;
     }
@@ -2074,86 +1928,70 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
     }
     const int cap = s->spillCap;
     const size_t spillRays = (std::max((size_t)bandPaths, 2 * qNeed + 64) + 63) / 64 * 64;
-    if (!slot.spill || slot.spillWords < spillRays * cap) {
-        HIPCHK(ctx, hipStreamSynchronize(slot.stream));
-        if (slot.spill) hipFree(slot.spill);
-        slot.spill = nullptr;
-        slot.spillWords = 0;
-        HIPCHK(ctx, hipMalloc(&slot.spill, spillRays * cap * sizeof(uint32_t)));
-        slot.spillWords = spillRays * cap;
-    }
+    HIPCHK(ctx, slot.spill.grow(spillRays * cap, slot.stream));
     hipStream_t st = slot.stream;
     HIPCHK(ctx, hipStreamWaitEvent(st, slot.free, 0));
-    fb_bind(fb, ks);
+    fb->cur = ks;
     fb->next = (ks + 1) % S;
-    fb->lastMaxDepth = slot.lastMaxDepth = p->max_depth;
-    fb->lastPixels = slot.lastPixels = 0;
+    slot.lastMaxDepth = p->max_depth;
+    slot.lastPixels = 0;
     slot.lastBatch = count;
     fb->bands = f;
     fb->haveBands = true;
-    mcrt_camera* dCam = reinterpret_cast<mcrt_camera*>(fb->counters + 128);   // 176 B per frame after the counters
+    mcrt_camera* dCam = slot.cameras();
+    int* const counters = slot.counters.get();
+    float4 *const radiance = slot.radiance.get(), *const hitsP = slot.hitsP.get(), *const hitsE = slot.hitsE.get();
+    float4 *const sO = slot.sO.get(), *const sD = slot.sD.get(), *const sL = slot.sL.get();
     HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera) * count, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(fb->counters, 0, 128 * sizeof(int), st));
-    int* shadowCnt = fb->counters;          // [b]
-    int* extCnt = fb->counters + 32;        // [b]
+    HIPCHK(ctx, hipMemsetAsync(counters, 0, 128 * sizeof(int), st));
+    int* shadowCnt = counters;          // [b]
+    int* extCnt = counters + 32;        // [b]
     const SceneArgs sa = scene_args(s);
     fb->lastIntegrator = MCRT_INTEGRATOR_PT;
     if (s->numLights == 0) {   // RTPathTracingPass.cpp:42: no lights -> pass skipped; radiance = 0 here
         // every frame plane of the batch: accumulate reads `count` of them
-        HIPCHK(ctx, hipMemsetAsync(fb->radiance, 0, 16 * fb->N * (size_t)count, st));
+        HIPCHK(ctx, hipMemsetAsync(radiance, 0, 16 * fb->N * (size_t)count, st));
         HIPCHK(ctx, hipEventRecord(slot.done, st));
         return MCRT_OK;
     }
     TraceCtx tcs = trace_ctx(s);
-    tcs.spill = slot.spill;
+    tcs.spill = slot.spill.get();
     const int qCap = bandPaths;
     const int wcap = tcs.qnodes && !tcs.twoLevel && p->max_depth > 1 && bandPaths >= walk_min_paths() ? walk_cap() : 0;
     if (wcap > 0) {
-        if (slot.suspendCap < (size_t)qCap) {
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            if (slot.suspend) hipFree(slot.suspend);
-            slot.suspend = nullptr;
-            slot.suspendCap = 0;
-            HIPCHK(ctx, hipMalloc(&slot.suspend, sizeof(float4) * MCRT_SUSPEND_F4 * (size_t)qCap));
-            slot.suspendCap = qCap;
-        }
-        if (!slot.suspendCnt) HIPCHK(ctx, hipMalloc(&slot.suspendCnt, 32 * sizeof(int)));
-        HIPCHK(ctx, hipMemsetAsync(slot.suspendCnt, 0, 32 * sizeof(int), st));
+        HIPCHK(ctx, slot.suspend.grow(MCRT_SUSPEND_F4 * (size_t)qCap, st));
+        if (!slot.suspendCnt) HIPCHK(ctx, slot.suspendCnt.alloc(32));
+        HIPCHK(ctx, hipMemsetAsync(slot.suspendCnt.get(), 0, 32 * sizeof(int), st));
     }
     if (longest_first()) {
         // the camera / first-shading tiles in descending cost of this slot's previous call (same
         // tiles), and this call's costs recorded for the next one -- all on the slot's stream
-        if (slot.tileCap < f.numTiles) {
-            HIPCHK(ctx, hipStreamSynchronize(st));
-            if (slot.tileCost) hipFree(slot.tileCost);
-            if (slot.tileOrder) hipFree(slot.tileOrder);
-            slot.tileCost = slot.tileOrder = nullptr;
-            slot.tileCap = slot.costTiles = 0;
-            HIPCHK(ctx, hipMalloc(&slot.tileCost, 4 * (size_t)f.numTiles));
-            HIPCHK(ctx, hipMalloc(&slot.tileOrder, 4 * (size_t)f.numTiles));
-            slot.tileCap = f.numTiles;
+        if (slot.tileOrder.size() < (size_t)f.numTiles) {   // (the one allocated last)
+            slot.costTiles = 0;
+            HIPCHK(ctx, slot.tileCost.grow((size_t)f.numTiles, st));
+            HIPCHK(ctx, slot.tileOrder.grow((size_t)f.numTiles, st));
         }
         if (slot.costTiles == f.numTiles) {
-            mcrt::launch_tile_order(slot.tileCost, f.numTiles, slot.tileOrder, st);
-            f.tileOrder = slot.tileOrder;
+            mcrt::launch_tile_order(slot.tileCost.get(), f.numTiles, slot.tileOrder.get(), st);
+            f.tileOrder = slot.tileOrder.get();
         }
-        HIPCHK(ctx, hipMemsetAsync(slot.tileCost, 0, 4 * (size_t)f.numTiles, st));
-        f.tileCost = slot.tileCost;
+        HIPCHK(ctx, hipMemsetAsync(slot.tileCost.get(), 0, 4 * (size_t)f.numTiles, st));
+        f.tileCost = slot.tileCost.get();
         slot.costTiles = f.numTiles;
     }
     {
         Timed t(ctx, K_PRIMARY, nullptr, (int64_t)bandPaths, st);
         TraceCtx tcp = packet_ctx(s);   // coherent camera rays: wave packets
-        tcp.spill = slot.spill;
+        tcp.spill = slot.spill.get();
         tcp.waveClock = wave_clock_buf(fb, 0, (size_t)f.numTiles * count, st);
-        mcrt::launch_primary(tcp, f, dCam, fb->hitsP, st);
+        mcrt::launch_primary(tcp, f, dCam, hitsP, st);
     }
     for (int b = 0; b < p->max_depth; ++b) {
         QueueArgs q;
         q.shadowCount = shadowCnt + b;
-        q.sO = fb->sO; q.sD = fb->sD; q.sL = fb->sL;
+        q.sO = sO; q.sD = sD; q.sL = sL;
         q.extCountOut = extCnt + b;
-        q.eOout = fb->eO[b & 1]; q.eDout = fb->eD[b & 1]; q.eTout = fb->eT[b & 1];
+        q.eOout = slot.eO[b & 1].get(); q.eDout = slot.eD[b & 1].get(); q.eTout = slot.eT[b & 1].get();
         if (b == 0) {
             Timed t(ctx, K_SHADE0, nullptr, (int64_t)bandPaths, st);
             // the longest-first order also for the first shading (its extension queue then starts with
@@ -2162,11 +2000,11 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
             // spatial locality (+2.8 % k_shade0, +1.2 % k_shadow_extend; profiles/r05/ab/longest_first)
             FrameArgs fs = f;
             if ((int64_t)bandPaths > MCRT_LPT_SHADE_MAX_PATHS) fs.tileOrder = nullptr;
-            mcrt::launch_shade0(sa, fs, dCam, fb->hitsP, fb->radiance, q, st);
+            mcrt::launch_shade0(sa, fs, dCam, hitsP, radiance, q, st);
         } else {
             Timed t(ctx, K_SHADEN, extCnt + b - 1, 0, st);
-            mcrt::launch_shadeN(sa, f, b, extCnt + b - 1, fb->eO[(b - 1) & 1], fb->eD[(b - 1) & 1],
-                                fb->eT[(b - 1) & 1], fb->hitsE, fb->radiance, q, qCap, st);
+            mcrt::launch_shadeN(sa, f, b, extCnt + b - 1, slot.eO[(b - 1) & 1].get(), slot.eD[(b - 1) & 1].get(),
+                                slot.eT[(b - 1) & 1].get(), hitsE, radiance, q, qCap, st);
         }
         if (b + 1 < p->max_depth) {
             // shadow rays of bounce b + extension rays for bounce b+1 (both from this shading pass) in
@@ -2174,32 +2012,32 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
             Timed t(ctx, K_SHADOW_EXTEND, extCnt + b, 0, st, shadowCnt + b);   // items: extension + shadow rays
             // bounce-0 shadow rays are coherent (a packed wave's paths share a pixel): wave packets
             TraceCtx tse = b == 0 ? packet_ctx(s) : tcs;
-            tse.spill = slot.spill;
-            with_hints(tse, s, b == 0 ? fb->hintPix : nullptr, (uint32_t)fb->N);
-            if (tse.hint && ctx->countHints) tse.hintHits = fb->counters + 64 + b;
-            if (tse.qnodes && ctx->countHints) tse.retraces = fb->counters + 96 + b;
+            tse.spill = slot.spill.get();
+            with_hints(tse, s, b == 0 ? fb->hintPix.get() : nullptr, (uint32_t)fb->N);
+            if (tse.hint && ctx->countHints) tse.hintHits = counters + 64 + b;
+            if (tse.qnodes && ctx->countHints) tse.retraces = counters + 96 + b;
             if (b == 0) tse.waveClock = wave_clock_buf(fb, 1, 2 * (((size_t)qCap + 63) / 64), st);
             if (wcap > 0 && b <= walk_max_bounce()) {
                 tse.walkCap = wcap;
                 tse.walkLanes = walk_lanes();
-                tse.suspend = slot.suspend;
-                tse.suspendCount = slot.suspendCnt + b;
+                tse.suspend = slot.suspend.get();
+                tse.suspendCount = slot.suspendCnt.get() + b;
             }
-            mcrt::launch_shadow_extend(tse, extCnt + b, fb->eO[b & 1], fb->eD[b & 1], fb->hitsE, shadowCnt + b,
-                                       fb->sO, fb->sD, fb->sL, fb->radiance, qCap, qCap, st);
-            if (tse.walkCap > 0) mcrt::launch_walk_resume(tse, fb->eO[b & 1], fb->eD[b & 1], fb->hitsE, qCap, st);
+            mcrt::launch_shadow_extend(tse, extCnt + b, slot.eO[b & 1].get(), slot.eD[b & 1].get(), hitsE, shadowCnt + b,
+                                       sO, sD, sL, radiance, qCap, qCap, st);
+            if (tse.walkCap > 0) mcrt::launch_walk_resume(tse, slot.eO[b & 1].get(), slot.eD[b & 1].get(), hitsE, qCap, st);
         } else {
             Timed t(ctx, K_SHADOW, shadowCnt + b, 0, st);
             TraceCtx tsh = tcs;
-            with_hints(tsh, s, b == 0 ? fb->hintPix : nullptr, (uint32_t)fb->N);
-            if (tsh.hint && ctx->countHints) tsh.hintHits = fb->counters + 64 + b;
+            with_hints(tsh, s, b == 0 ? fb->hintPix.get() : nullptr, (uint32_t)fb->N);
+            if (tsh.hint && ctx->countHints) tsh.hintHits = counters + 64 + b;
             tsh.waveClock = wave_clock_buf(fb, 2, ((size_t)qCap + 63) / 64, st);
-            mcrt::launch_shadow(tsh, shadowCnt + b, fb->sO, fb->sD, fb->sL, fb->radiance, qCap, st);
+            mcrt::launch_shadow(tsh, shadowCnt + b, sO, sD, sL, radiance, qCap, st);
         }
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(slot.done, st));
-    fb->lastPixels = slot.lastPixels = (int64_t)bandPaths;
+    slot.lastPixels = (int64_t)bandPaths;
     return MCRT_OK;
 }
 
@@ -2226,18 +2064,20 @@ MCRT_API mcrt_status mcrt_render_aov(mcrt_scene s, mcrt_framebuffer fb, const mc
     if (!frame_args(fb, p, f, err)) return fail(ctx, MCRT_ERROR_INVALID_ARG, err);
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    ctx_wait_slots(fb);   // the AOV pass reuses the bound slot's camera and primary-hit buffers
-    mcrt_camera* dCam = reinterpret_cast<mcrt_camera*>(fb->counters + 128);
+    FrameSlot& slot = cur_slot(fb);   // the AOV pass reuses the current slot's camera and primary-hit buffers
+    if (!slot.counters) return fail(ctx, MCRT_ERROR_NOT_READY, kNoSlotBuffers);
+    ctx_wait_slots(fb);
+    mcrt_camera* dCam = slot.cameras();
     HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera), hipMemcpyHostToDevice, st));
     if (!ensure_spill(s, std::max((size_t)f.numTiles * 64, 2 * fb->N + 64)))
         return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "traversal spill buffer");
     const TraceCtx tcs = packet_ctx(s);
-    mcrt::launch_primary(tcs, f, dCam, fb->hitsP, st);
+    mcrt::launch_primary(tcs, f, dCam, slot.hitsP.get(), st);
     const size_t stride = aov == MCRT_AOV_TEXTURE_LOD ? 3 : 1;
     float4* dOut = nullptr;
     HIPCHK(ctx, hipMallocAsync((void**)&dOut, 16 * stride * fb->N, st));
     HIPCHK(ctx, hipMemsetAsync(dOut, 0, 16 * stride * fb->N, st));
-    mcrt::launch_aov(scene_args(s), f, dCam, fb->hitsP, aov, dOut, st);
+    mcrt::launch_aov(scene_args(s), f, dCam, slot.hitsP.get(), aov, dOut, st);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(host_out, dOut, 16 * stride * fb->N, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -2261,25 +2101,26 @@ static mcrt_status accumulate(mcrt_framebuffer fb, const mcrt_filter* filters, i
         fb->haveBands = true;
     }
     hipSetDevice(ctx->device);
-    FrameSlot& slot = fb->slot[fb->cur];
+    FrameSlot& slot = cur_slot(fb);
     const int batch = slot.lastBatch;
     if (nfilters != 1 && nfilters != batch)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "one filter, or one per frame of the last mcrt_render_frames");
+    if (!slot.counters) return fail(ctx, MCRT_ERROR_NOT_READY, kNoSlotBuffers);
     FrameArgs f = fb->bands;
     f.batch = batch;
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, slot.done, 0));   // the frame's render (its slot stream)
     // weights are evaluated on the device (k_accumulate, filters.cl); the filters go to the slot's
     // counter block, which its next render (after slot.free below) does not touch before this launch
-    mcrt_filter* dFilt = reinterpret_cast<mcrt_filter*>(reinterpret_cast<char*>(slot.counters) + SLOT_FILTER_OFFSET);
+    mcrt_filter* dFilt = slot.filters();
     HIPCHK(ctx, hipMemcpyAsync(dFilt, filters, sizeof(mcrt_filter) * nfilters, hipMemcpyHostToDevice, ctx->stream));
     {
         Timed t(ctx, K_ACCUM, nullptr, (int64_t)f.numTiles * 64 * batch);
-        mcrt::launch_accumulate(f, frame_index, dFilt, nfilters == 1 ? 0 : 1, fb->radiance, fb->wsum, fb->wts, fb->image,
-                                ctx->stream);
+        mcrt::launch_accumulate(f, frame_index, dFilt, nfilters == 1 ? 0 : 1, slot.radiance.get(), fb->wsum.get(), fb->wts.get(),
+                                fb->image.get(), ctx->stream);
     }
     if (fb->momentsOn) {   // the same frames' luminance moments, before the slot is released
         Timed t(ctx, K_MOMENTS, nullptr, (int64_t)f.numTiles * 64 * batch);
-        mcrt::launch_moments(f, frame_index, fb->radiance, fb->moments, ctx->stream);
+        mcrt::launch_moments(f, frame_index, slot.radiance.get(), fb->moments.get(), ctx->stream);
         fb->momentFrames = frame_index == 0 ? batch : fb->momentFrames + batch;
     }
     HIPCHK(ctx, hipGetLastError());
@@ -2299,10 +2140,10 @@ MCRT_API mcrt_status mcrt_accumulate_frames(mcrt_framebuffer fb, const mcrt_filt
 MCRT_API mcrt_status mcrt_framebuffer_device_ptrs(mcrt_framebuffer fb, void** radiance, void** weighted_sum,
                                                   void** weight_sum, void** image) {
     if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
-    if (radiance) *radiance = fb->radiance;
-    if (weighted_sum) *weighted_sum = fb->wsum;
-    if (weight_sum) *weight_sum = fb->wts;
-    if (image) *image = fb->image;
+    if (radiance) *radiance = cur_slot(fb).radiance.get();
+    if (weighted_sum) *weighted_sum = fb->wsum.get();
+    if (weight_sum) *weight_sum = fb->wts.get();
+    if (image) *image = fb->image.get();
     return MCRT_OK;
 }
 
@@ -2311,20 +2152,20 @@ MCRT_API mcrt_status mcrt_postprocess(mcrt_framebuffer fb, const mcrt_postproces
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
     const int W = (int)fb->W, H = (int)fb->H;
-    const float4* src = fb->image;
+    const float4* src = fb->image.get();
     if (p->use_denoise) {
         // RTDenoisePass (RTDenoisePass.cpp:21-60): the kernel writes nothing for a non-positive
         // radius or sigma (Denoise.cl:18-19), so the pass then shows its image's old content.
         if (p->denoise_radius > 16) return fail(ctx, MCRT_ERROR_INVALID_ARG, "denoise_radius > 16 (the GUI allows <= 10)");
         if (p->denoise_radius > 0 && p->sigma_spatial > 0.0f && p->sigma_range > 0.0f)
-            mcrt::launch_denoise(W, H, p->denoise_radius, p->sigma_spatial, p->sigma_range, fb->image, fb->denoised,
+            mcrt::launch_denoise(W, H, p->denoise_radius, p->sigma_spatial, p->sigma_range, fb->image.get(), fb->denoised.get(),
                                  ctx->stream);
-        src = fb->denoised;
+        src = fb->denoised.get();
     }
     if (p->use_tonemapping)   // RTToneMappingPass::applyReinhardToneMapping (RTToneMappingPass.cpp:38-72)
-        mcrt::launch_tonemap(W * H, p->min_luminance, src, fb->display, ctx->stream);
+        mcrt::launch_tonemap(W * H, p->min_luminance, src, fb->display.get(), ctx->stream);
     else
-        HIPCHK(ctx, hipMemcpyAsync(fb->display, src, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+        HIPCHK(ctx, hipMemcpyAsync(fb->display.get(), src, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
 }
@@ -2332,16 +2173,9 @@ MCRT_API mcrt_status mcrt_postprocess(mcrt_framebuffer fb, const mcrt_postproces
 // ---------------------------------------------------------------------------
 // Guided denoiser: guides, moments, a-trous filter (mcrt_denoise.hip)
 // ---------------------------------------------------------------------------
-// Allocates *p (bytes, zero-filled on the context stream) when it does not exist yet.
-static hipError_t ensure_plane(mcrt_ctx ctx, void** p, size_t bytes) {
-    if (*p) return hipSuccess;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes, ctx->stream);
-    return e;
-}
 static hipError_t ensure_guides(mcrt_framebuffer fb) {
-    hipError_t e = ensure_plane(fb->ctx, (void**)&fb->guideNormal, 16 * fb->N);
-    if (e == hipSuccess) e = ensure_plane(fb->ctx, (void**)&fb->guideAlbedo, 16 * fb->N);
+    hipError_t e = ensure_plane(fb, fb->guideNormal);
+    if (e == hipSuccess) e = ensure_plane(fb, fb->guideAlbedo);
     return e;
 }
 
@@ -2359,20 +2193,22 @@ MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     HIPCHK(ctx, ensure_guides(fb));
-    ctx_wait_slots(fb);   // as mcrt_render_aov: the bound slot's camera and primary-hit buffers are reused
-    mcrt_camera* dCam = reinterpret_cast<mcrt_camera*>(fb->counters + 128);
+    FrameSlot& slot = cur_slot(fb);   // as mcrt_render_aov: its camera and primary-hit buffers are reused
+    if (!slot.counters) return fail(ctx, MCRT_ERROR_NOT_READY, kNoSlotBuffers);
+    ctx_wait_slots(fb);
+    mcrt_camera* dCam = slot.cameras();
     HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera), hipMemcpyHostToDevice, st));
     if (!ensure_spill(s, std::max((size_t)f.numTiles * 64, 2 * fb->N + 64)))
         return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "traversal spill buffer");
     const TraceCtx tcs = packet_ctx(s);
-    mcrt::launch_primary(tcs, f, dCam, fb->hitsP, st);
+    mcrt::launch_primary(tcs, f, dCam, slot.hitsP.get(), st);
     {
         Timed t(ctx, K_GUIDES, nullptr, (int64_t)f.numTiles * 64);
-        mcrt::launch_guides(scene_args(s), f, dCam, fb->hitsP, fb->guideNormal, fb->guideAlbedo, st);
+        mcrt::launch_guides(scene_args(s), f, dCam, slot.hitsP.get(), fb->guideNormal.get(), fb->guideAlbedo.get(), st);
     }
     HIPCHK(ctx, hipGetLastError());
     // the slot's next render (its own stream) may overwrite those buffers only after this pass
-    HIPCHK(ctx, hipEventRecord(fb->slot[fb->cur].free, st));
+    HIPCHK(ctx, hipEventRecord(slot.free, st));
     fb->haveGuides = true;
     return MCRT_OK;
 }
@@ -2383,8 +2219,8 @@ MCRT_API mcrt_status mcrt_framebuffer_set_guides(mcrt_framebuffer fb, const void
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
     HIPCHK(ctx, ensure_guides(fb));
-    HIPCHK(ctx, hipMemcpyAsync(fb->guideNormal, d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->guideAlbedo, d_albedo_depth, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->guideNormal.get(), d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->guideAlbedo.get(), d_albedo_depth, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     fb->haveGuides = true;
     return MCRT_OK;
 }
@@ -2394,7 +2230,7 @@ MCRT_API mcrt_status mcrt_framebuffer_set_moments_enabled(mcrt_framebuffer fb, i
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
     if (on && !fb->moments) {
-        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->moments, 8 * fb->N));
+        HIPCHK(ctx, ensure_plane(fb, fb->moments));
         fb->momentFrames = 0;
     }
     fb->momentsOn = on != 0;
@@ -2405,8 +2241,8 @@ MCRT_API mcrt_status mcrt_framebuffer_set_moments(mcrt_framebuffer fb, const voi
     if (!fb || !d_m1m2 || frames < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
-    HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->moments, 8 * fb->N));
-    HIPCHK(ctx, hipMemcpyAsync(fb->moments, d_m1m2, 8 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, ensure_plane(fb, fb->moments));
+    HIPCHK(ctx, hipMemcpyAsync(fb->moments.get(), d_m1m2, 8 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     fb->momentFrames = frames;
     return MCRT_OK;
 }
@@ -2415,8 +2251,9 @@ MCRT_API mcrt_status mcrt_framebuffer_read_guides(mcrt_framebuffer fb, int which
                                                   uint64_t* needed) {
     if (!fb || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
-    const void* src = which == 0 ? (const void*)fb->guideNormal : which == 1 ? (const void*)fb->guideAlbedo
-                      : which == 2 ? (const void*)fb->moments : (const void*)fb->filteredVar;
+    const void* src = which == 0 ? (const void*)fb->guideNormal.get() : which == 1 ? (const void*)fb->guideAlbedo.get()
+                      : which == 2 ? (const void*)fb->moments.get()
+                      : fb->filteredVar < 0 ? nullptr : (const void*)fb->atrousV[fb->filteredVar].get();
     const uint64_t need = (which < 2 ? 16 : which == 2 ? 8 : 4) * (uint64_t)fb->N;
     if (needed) *needed = need;
     if (!host_dst) return MCRT_OK;
@@ -2432,54 +2269,90 @@ MCRT_API mcrt_status mcrt_framebuffer_read_guides(mcrt_framebuffer fb, int which
 // their taps from memory.  MCRT_ATROUS_LDS_MAX_STEP overrides it (0: never stage) for measurements
 // and the test that both kernels agree bit for bit.
 static int atrous_lds_max_step() {
-    const char* e = std::getenv("MCRT_ATROUS_LDS_MAX_STEP");
-    const int v = e ? std::atoi(e) : 4;
-    return std::min(std::max(v, 0), 8);   // step 8: 48 x 48 x 36 B = 81 KB does not fit 64 KB
+    return env_int("MCRT_ATROUS_LDS_MAX_STEP", 4, 0, 8);   // step 8: 48 x 48 x 36 B = 81 KB does not fit 64 KB
 }
 
-MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p) {
-    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+// the two scratch colour / variance planes the levels ping-pong between
+static hipError_t ensure_atrous(mcrt_framebuffer fb) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = ensure_plane(fb, fb->atrousC[i]);
+        if (e == hipSuccess) e = ensure_plane(fb, fb->atrousV[i]);
+    }
+    return e;
+}
+
+// The a-trous chain of mcrt_denoise_guided and mcrt_denoise_guided_temporal: the checks they share
+// (in their order), then `begin` -- the caller's own checks and whatever makes level 0's input --
+// then the levels, ping-ponging between the scratch planes, and the tone-map tail.  The output of
+// level `feedback_level` (-1: none) becomes the colour history.
+static mcrt_status atrous_chain(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, int feedback_level,
+                                AtrousBegin begin) {
     mcrt_ctx ctx = fb->ctx;
+    const int demod = p->demodulate_albedo ? 1 : 0;
     if (p->levels < 1 || p->levels > MCRT_ATROUS_MAX_LEVELS)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "levels must be 1 .. 8");
     if (!(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f) || !(p->sigma_luminance > 0.0f))
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "sigmas must be positive");
+    if (feedback_level < -1 || feedback_level > p->levels - 2)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "feedback_level must be -1 .. levels - 2");
     if (!fb->haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
     if (fb->bdptPendingGather)
         return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
     hipSetDevice(ctx->device);
+    AtrousIn in;
+    const mcrt_status bs = begin(fb, p, in);
+    if (bs != MCRT_OK) return bs;
+    HIPCHK(ctx, ensure_atrous(fb));
     hipStream_t st = ctx->stream;
     const int W = (int)fb->W, H = (int)fb->H;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->atrousC[i], 16 * fb->N));
-        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->atrousV[i], 4 * fb->N));
-    }
-    const bool useVar = p->use_variance && fb->moments && fb->momentFrames >= 2;
-    const int demod = p->demodulate_albedo ? 1 : 0;
-    {
-        Timed t(ctx, K_ATROUS_PREP, nullptr, (int64_t)fb->N);
-        mcrt::launch_atrous_prep((int)fb->N, fb->image, fb->guideAlbedo, useVar ? fb->moments : nullptr, fb->momentFrames,
-                                 demod, fb->atrousC[0], fb->atrousV[0], st);
-    }
     const int ldsMax = atrous_lds_max_step();
-    int src = 0;
+    const float4* cIn = in.colour;
+    const float* vIn = in.var;
+    int dst = cIn == fb->atrousC[0].get() ? 1 : 0;   // never the plane level 0 reads
     for (int i = 0; i < p->levels; ++i) {
         const int step = 1 << i;
         const bool last = i + 1 == p->levels;
-        // the last level writes the display image, or the other scratch plane when k_tonemap follows
-        float4* cOut = last && !p->use_tonemapping ? fb->display : fb->atrousC[src ^ 1];
-        const float sigmaLevel = useVar ? p->sigma_luminance : p->sigma_luminance * std::ldexp(1.0f, -i);
+        // the last level writes the display image, or a scratch plane when k_tonemap follows
+        float4* cOut = last && !p->use_tonemapping ? fb->display.get() : fb->atrousC[dst].get();
+        const float sigmaLevel = in.useVar ? p->sigma_luminance : p->sigma_luminance * std::ldexp(1.0f, -i);
         const bool lds = step <= ldsMax && mcrt::atrous_lds_bytes(step) <= 64 * 1024;
-        Timed t(ctx, K_ATROUS + i, nullptr, (int64_t)fb->N);
-        mcrt::launch_atrous(W, H, step, lds, p->sigma_normal, p->sigma_depth, sigmaLevel, useVar ? 1 : 0,
-                            last && demod ? 1 : 0, fb->atrousC[src], fb->guideNormal, fb->guideAlbedo, fb->atrousV[src],
-                            cOut, fb->atrousV[src ^ 1], st);
-        src ^= 1;
+        {
+            Timed t(ctx, K_ATROUS + i, nullptr, (int64_t)fb->N);
+            mcrt::launch_atrous(W, H, step, lds, p->sigma_normal, p->sigma_depth, sigmaLevel, in.useVar,
+                                last && demod ? 1 : 0, cIn, fb->guideNormal.get(), fb->guideAlbedo.get(), vIn, cOut,
+                                fb->atrousV[dst].get(), st);
+        }
+        if (i == feedback_level) {
+            // this level's output (never the last level's: a scratch plane) becomes the colour history
+            // by exchanging the two planes; the old history plane, which only level 0 read, is scratch
+            // from now on, and no later level writes the new history plane
+            std::swap(fb->tColour[fb->tCur], fb->atrousC[dst]);
+            fb->tFedBack = true;
+        }
+        cIn = cOut;
+        vIn = fb->atrousV[dst].get();
+        dst ^= 1;
     }
-    fb->filteredVar = fb->atrousV[src];
-    if (p->use_tonemapping) mcrt::launch_tonemap(W * H, p->min_luminance, fb->atrousC[src], fb->display, st);
+    fb->filteredVar = dst ^ 1;
+    if (p->use_tonemapping) mcrt::launch_tonemap(W * H, p->min_luminance, cIn, fb->display.get(), st);
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p) {
+    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    return atrous_chain(fb, p, -1, [](mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, AtrousIn& in) {
+        mcrt_ctx ctx = fb->ctx;
+        HIPCHK(ctx, ensure_atrous(fb));   // k_atrous_prep writes level 0's input to the first scratch planes
+        const bool useVar = p->use_variance && fb->moments && fb->momentFrames >= 2;
+        Timed t(ctx, K_ATROUS_PREP, nullptr, (int64_t)fb->N);
+        mcrt::launch_atrous_prep((int)fb->N, fb->image.get(), fb->guideAlbedo.get(), useVar ? fb->moments.get() : nullptr,
+                                 fb->momentFrames, p->demodulate_albedo ? 1 : 0, fb->atrousC[0].get(),
+                                 fb->atrousV[0].get(), ctx->stream);
+        in = {fb->atrousC[0].get(), fb->atrousV[0].get(), useVar ? 1 : 0};
+        return MCRT_OK;
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -2488,11 +2361,11 @@ MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_
 static hipError_t ensure_temporal(mcrt_framebuffer fb) {
     hipError_t e = hipSuccess;
     for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = ensure_plane(fb->ctx, (void**)&fb->tColour[i], 16 * fb->N);
-        if (e == hipSuccess) e = ensure_plane(fb->ctx, (void**)&fb->tMoments[i], 16 * fb->N);
-        if (e == hipSuccess) e = ensure_plane(fb->ctx, (void**)&fb->tNormal[i], 16 * fb->N);
+        e = ensure_plane(fb, fb->tColour[i]);
+        if (e == hipSuccess) e = ensure_plane(fb, fb->tMoments[i]);
+        if (e == hipSuccess) e = ensure_plane(fb, fb->tNormal[i]);
     }
-    if (e == hipSuccess) e = ensure_plane(fb->ctx, (void**)&fb->tVar, 4 * fb->N);
+    if (e == hipSuccess) e = ensure_plane(fb, fb->tVar);
     return e;
 }
 
@@ -2536,23 +2409,23 @@ MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_ca
     t.planeThr = p->plane_threshold;
     t.cam = cam;
     t.prev = fb->tHaveHistory ? &fb->tPrevCam : cam;
-    t.image = fb->image;
-    t.albedoDepth = fb->guideAlbedo;
-    t.normalPlane = fb->guideNormal;
-    t.colourOld = fb->tColour[old];
-    t.momentsOld = fb->tMoments[old];
-    t.normalOld = fb->tNormal[old];
-    t.colourNew = fb->tColour[now];
-    t.momentsNew = fb->tMoments[now];
-    t.normalNew = fb->tNormal[now];
+    t.image = fb->image.get();
+    t.albedoDepth = fb->guideAlbedo.get();
+    t.normalPlane = fb->guideNormal.get();
+    t.colourOld = fb->tColour[old].get();
+    t.momentsOld = fb->tMoments[old].get();
+    t.normalOld = fb->tNormal[old].get();
+    t.colourNew = fb->tColour[now].get();
+    t.momentsNew = fb->tMoments[now].get();
+    t.normalNew = fb->tNormal[now].get();
     {
         Timed tm(ctx, K_TEMPORAL, nullptr, (int64_t)fb->N);
         mcrt::launch_temporal(t, temporal_eager_loads(), st);
     }
     {
         Timed tm(ctx, K_TEMPORAL_VAR, nullptr, (int64_t)fb->N);
-        mcrt::launch_temporal_var(W, H, p->min_history, p->normal_threshold, p->plane_threshold, fb->tMoments[now],
-                                  fb->tNormal[now], fb->tVar, st);
+        mcrt::launch_temporal_var(W, H, p->min_history, p->normal_threshold, p->plane_threshold, fb->tMoments[now].get(),
+                                  fb->tNormal[now].get(), fb->tVar.get(), st);
     }
     HIPCHK(ctx, hipGetLastError());
     fb->tCur = now;
@@ -2581,9 +2454,9 @@ MCRT_API mcrt_status mcrt_framebuffer_set_temporal_history(mcrt_framebuffer fb, 
     hipSetDevice(ctx->device);
     HIPCHK(ctx, ensure_temporal(fb));
     const int cur = fb->tCur;
-    HIPCHK(ctx, hipMemcpyAsync(fb->tColour[cur], d_colour, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->tMoments[cur], d_moments, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->tNormal[cur], d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->tColour[cur].get(), d_colour, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->tMoments[cur].get(), d_moments, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->tNormal[cur].get(), d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     fb->tPrevCam = *prev_camera;
     fb->tHaveHistory = true;
     return MCRT_OK;
@@ -2594,8 +2467,8 @@ MCRT_API mcrt_status mcrt_framebuffer_read_temporal(mcrt_framebuffer fb, int whi
     if (!fb || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
     const int cur = fb->tCur;
-    const void* src = which == 0 ? (const void*)fb->tColour[cur] : which == 1 ? (const void*)fb->tMoments[cur]
-                      : which == 2 ? (const void*)fb->tVar : (const void*)fb->tNormal[cur];
+    const void* src = which == 0 ? (const void*)fb->tColour[cur].get() : which == 1 ? (const void*)fb->tMoments[cur].get()
+                      : which == 2 ? (const void*)fb->tVar.get() : (const void*)fb->tNormal[cur].get();
     const uint64_t need = (which == 2 ? 4 : 16) * (uint64_t)fb->N;
     if (needed) *needed = need;
     if (!host_dst) return MCRT_OK;
@@ -2610,71 +2483,26 @@ MCRT_API mcrt_status mcrt_framebuffer_read_temporal(mcrt_framebuffer fb, int whi
 MCRT_API mcrt_status mcrt_denoise_guided_temporal(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p,
                                                   int32_t feedback_level) {
     if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    if (p->levels < 1 || p->levels > MCRT_ATROUS_MAX_LEVELS)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "levels must be 1 .. 8");
-    if (!(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f) || !(p->sigma_luminance > 0.0f))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "sigmas must be positive");
-    if (feedback_level < -1 || feedback_level > p->levels - 2)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "feedback_level must be -1 .. levels - 2");
-    if (!fb->haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
-    if (fb->bdptPendingGather)
-        return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
-    if (!fb->tAccumulated) return fail(ctx, MCRT_ERROR_NOT_READY, "no mcrt_temporal_accumulate yet");
-    if (fb->tFedBack)
-        return fail(ctx, MCRT_ERROR_NOT_READY, "the colour history already holds a filtered level of this accumulate");
-    const int demod = p->demodulate_albedo ? 1 : 0;
-    if (demod != fb->tDemod)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "demodulate_albedo differs from the last mcrt_temporal_accumulate");
-    hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    const int W = (int)fb->W, H = (int)fb->H;
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->atrousC[i], 16 * fb->N));
-        HIPCHK(ctx, ensure_plane(ctx, (void**)&fb->atrousV[i], 4 * fb->N));
-    }
-    const int useVar = p->use_variance ? 1 : 0;
-    const int ldsMax = atrous_lds_max_step();
-    // level 0 reads the colour history (already in filter space) and the variance plane; the levels
-    // then ping-pong between the scratch planes as in mcrt_denoise_guided
-    const float4* cIn = fb->tColour[fb->tCur];
-    const float* vIn = fb->tVar;
-    int dst = 0;
-    for (int i = 0; i < p->levels; ++i) {
-        const int step = 1 << i;
-        const bool last = i + 1 == p->levels;
-        float4* cOut = last && !p->use_tonemapping ? fb->display : fb->atrousC[dst];
-        const float sigmaLevel = useVar ? p->sigma_luminance : p->sigma_luminance * std::ldexp(1.0f, -i);
-        const bool lds = step <= ldsMax && mcrt::atrous_lds_bytes(step) <= 64 * 1024;
-        {
-            Timed t(ctx, K_ATROUS + i, nullptr, (int64_t)fb->N);
-            mcrt::launch_atrous(W, H, step, lds, p->sigma_normal, p->sigma_depth, sigmaLevel, useVar,
-                                last && demod ? 1 : 0, cIn, fb->guideNormal, fb->guideAlbedo, vIn, cOut, fb->atrousV[dst],
-                                st);
-        }
-        if (i == feedback_level) {
-            // this level's output (never the last level's: a scratch plane) becomes the colour history
-            // by exchanging the two planes; the old history plane, which only level 0 read, is scratch
-            // from now on, and no later level writes the new history plane
-            std::swap(fb->tColour[fb->tCur], fb->atrousC[dst]);
-            fb->tFedBack = true;
-        }
-        cIn = cOut;
-        vIn = fb->atrousV[dst];
-        dst ^= 1;
-    }
-    fb->filteredVar = fb->atrousV[dst ^ 1];
-    if (p->use_tonemapping) mcrt::launch_tonemap(W * H, p->min_luminance, cIn, fb->display, st);
-    HIPCHK(ctx, hipGetLastError());
-    return MCRT_OK;
+    return atrous_chain(fb, p, feedback_level, [](mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, AtrousIn& in) {
+        mcrt_ctx ctx = fb->ctx;
+        const int demod = p->demodulate_albedo ? 1 : 0;
+        if (!fb->tAccumulated) return fail(ctx, MCRT_ERROR_NOT_READY, "no mcrt_temporal_accumulate yet");
+        if (fb->tFedBack)
+            return fail(ctx, MCRT_ERROR_NOT_READY, "the colour history already holds a filtered level of this accumulate");
+        if (demod != fb->tDemod)
+            return fail(ctx, MCRT_ERROR_INVALID_ARG, "demodulate_albedo differs from the last mcrt_temporal_accumulate");
+        // level 0 reads the colour history (already in filter space) and the variance plane
+        in = {fb->tColour[fb->tCur].get(), fb->tVar.get(), p->use_variance ? 1 : 0};
+        return MCRT_OK;
+    });
 }
 
 MCRT_API mcrt_status mcrt_framebuffer_read(mcrt_framebuffer fb, int which, float* host_rgba) {
     if (!fb || !host_rgba || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
-    const void* src = which == 0 ? (const void*)fb->radiance : which == 1 ? (const void*)fb->wsum
-                      : which == 2 ? (const void*)fb->image : (const void*)fb->display;
+    const void* src = which == 0 ? (const void*)cur_slot(fb).radiance.get() : which == 1 ? (const void*)fb->wsum.get()
+                      : which == 2 ? (const void*)fb->image.get() : (const void*)fb->display.get();
     HIPCHK(ctx, fb_sync(fb));
     HIPCHK(ctx, hipMemcpy(host_rgba, src, 16 * fb->N, hipMemcpyDeviceToHost));
     return check_device_flags(ctx);
@@ -2683,12 +2511,12 @@ MCRT_API mcrt_status mcrt_framebuffer_read(mcrt_framebuffer fb, int which, float
 MCRT_API mcrt_status mcrt_framebuffer_read_frame(mcrt_framebuffer fb, int32_t k, float* host_rgba) {
     if (!fb || !host_rgba) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
-    const int batch = fb->slot[fb->cur].lastBatch;
+    const int batch = cur_slot(fb).lastBatch;
     if (k < 0 || k >= std::max(batch, 1))
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame index outside the last mcrt_render_frames batch");
     hipSetDevice(ctx->device);
     HIPCHK(ctx, fb_sync(fb));
-    HIPCHK(ctx, hipMemcpy(host_rgba, fb->radiance + (size_t)k * fb->N, 16 * fb->N, hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(host_rgba, cur_slot(fb).radiance.get() + (size_t)k * fb->N, 16 * fb->N, hipMemcpyDeviceToHost));
     return check_device_flags(ctx);
 }
 
@@ -2696,12 +2524,12 @@ MCRT_API mcrt_status mcrt_framebuffer_copy_device(mcrt_framebuffer fb, int which
     if (!fb || !d_dst || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
-    const void* src = which == 0 ? (const void*)fb->radiance : which == 1 ? (const void*)fb->wsum
-                      : which == 2 ? (const void*)fb->image : (const void*)fb->wts;
+    const void* src = which == 0 ? (const void*)cur_slot(fb).radiance.get() : which == 1 ? (const void*)fb->wsum.get()
+                      : which == 2 ? (const void*)fb->image.get() : (const void*)fb->wts.get();
     if (which == 0) ctx_wait_slots(fb);
     HIPCHK(ctx, hipMemcpyAsync(d_dst, src, (which == 3 ? 4 : 16) * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     // the slot may take its next frame only after this copy has read its radiance
-    if (which == 0) HIPCHK(ctx, hipEventRecord(fb->slot[fb->cur].free, ctx->stream));
+    if (which == 0) HIPCHK(ctx, hipEventRecord(cur_slot(fb).free, ctx->stream));
     return MCRT_OK;
 }
 
@@ -2709,9 +2537,9 @@ MCRT_API mcrt_status mcrt_framebuffer_set_accumulation(mcrt_framebuffer fb, cons
     if (!fb || !d_wsum || !d_wts) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
-    HIPCHK(ctx, hipMemcpyAsync(fb->wsum, d_wsum, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->wts, d_wts, 4 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    mcrt::launch_resolve(fb->W, fb->H, fb->wsum, fb->wts, fb->image, ctx->stream);
+    HIPCHK(ctx, hipMemcpyAsync(fb->wsum.get(), d_wsum, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->wts.get(), d_wts, 4 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    mcrt::launch_resolve(fb->W, fb->H, fb->wsum.get(), fb->wts.get(), fb->image.get(), ctx->stream);
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
 }
@@ -2721,7 +2549,7 @@ MCRT_API mcrt_status mcrt_framebuffer_bands_pack(mcrt_framebuffer fb, void* d_ds
     if (!fb->haveBands) return fail(fb->ctx, MCRT_ERROR_NOT_READY, "no frame rendered");
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
-    mcrt::launch_band_pack(fb->bands, fb->wsum, fb->wts, static_cast<float*>(d_dst), ctx->stream);
+    mcrt::launch_band_pack(fb->bands, fb->wsum.get(), fb->wts.get(), static_cast<float*>(d_dst), ctx->stream);
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
 }
@@ -2752,7 +2580,7 @@ MCRT_API mcrt_status mcrt_framebuffer_bands_unpack(mcrt_framebuffer fb, const vo
         return fail(fb->ctx, MCRT_ERROR_INVALID_ARG, "max_rows below the largest rank's row count");
     mcrt_ctx ctx = fb->ctx;
     hipSetDevice(ctx->device);
-    mcrt::launch_band_unpack(f, max_rows, static_cast<const float*>(d_recv), fb->wsum, fb->wts, fb->image,
+    mcrt::launch_band_unpack(f, max_rows, static_cast<const float*>(d_recv), fb->wsum.get(), fb->wts.get(), fb->image.get(),
                              ctx->stream);
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
@@ -2762,24 +2590,25 @@ MCRT_API mcrt_status mcrt_framebuffer_stats(mcrt_framebuffer fb, int64_t* closes
                                             int64_t* shaded_paths) {
     if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
     mcrt_ctx ctx = fb->ctx;
+    const FrameSlot& slot = cur_slot(fb);
     hipSetDevice(ctx->device);
     HIPCHK(ctx, fb_sync(fb));
     int c[64];
     if (fb->lastIntegrator == MCRT_INTEGRATOR_BDPT) {   // closest: all subpath rays; any: connection rays
-        HIPCHK(ctx, hipMemcpy(c, fb->bdptCounters, sizeof(c), hipMemcpyDeviceToHost));
+        HIPCHK(ctx, hipMemcpy(c, cur_bset(fb).bdptCounters.get(), sizeof(c), hipMemcpyDeviceToHost));
         int64_t cl = 0;
-        for (int d = 0; d <= fb->lastMaxDepth; ++d) cl += c[d];
+        for (int d = 0; d <= slot.lastMaxDepth; ++d) cl += c[d];
         cl += c[BDPT_CNT_CAM0];
         if (closest_rays) *closest_rays = cl;
         if (any_rays) *any_rays = c[BDPT_CNT_CONN];
         if (shaded_paths) *shaded_paths = cl;
         return MCRT_OK;
     }
-    HIPCHK(ctx, hipMemcpy(c, fb->counters, sizeof(c), hipMemcpyDeviceToHost));
-    int64_t cl = fb->lastPixels, an = 0, sh = fb->lastPixels;
-    for (int b = 0; b < fb->lastMaxDepth; ++b) {
+    HIPCHK(ctx, hipMemcpy(c, slot.counters.get(), sizeof(c), hipMemcpyDeviceToHost));
+    int64_t cl = slot.lastPixels, an = 0, sh = slot.lastPixels;
+    for (int b = 0; b < slot.lastMaxDepth; ++b) {
         an += c[b];
-        if (b + 1 < fb->lastMaxDepth) { cl += c[32 + b]; sh += c[32 + b]; }
+        if (b + 1 < slot.lastMaxDepth) { cl += c[32 + b]; sh += c[32 + b]; }
     }
     if (closest_rays) *closest_rays = cl;
     if (any_rays) *any_rays = an;
@@ -2790,14 +2619,15 @@ MCRT_API mcrt_status mcrt_framebuffer_stats(mcrt_framebuffer fb, int64_t* closes
 MCRT_API mcrt_status mcrt_framebuffer_queue_counts(mcrt_framebuffer fb, int32_t* shadow, int32_t* extension, int max) {
     if (!fb || max < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
+    const FrameSlot& slot = cur_slot(fb);
     hipSetDevice(ctx->device);
     HIPCHK(ctx, fb_sync(fb));
     int c[64];
-    HIPCHK(ctx, hipMemcpy(c, fb->counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(c, slot.counters.get(), sizeof(c), hipMemcpyDeviceToHost));
     for (int b = 0; b < max && b < 32; ++b) {
-        const bool live = b < fb->lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
+        const bool live = b < slot.lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
         if (shadow) shadow[b] = live ? c[b] : 0;
-        if (extension) extension[b] = live && b + 1 < fb->lastMaxDepth ? c[32 + b] : 0;
+        if (extension) extension[b] = live && b + 1 < slot.lastMaxDepth ? c[32 + b] : 0;
     }
     return MCRT_OK;
 }
@@ -2805,12 +2635,13 @@ MCRT_API mcrt_status mcrt_framebuffer_queue_counts(mcrt_framebuffer fb, int32_t*
 MCRT_API mcrt_status mcrt_framebuffer_hint_counts(mcrt_framebuffer fb, int32_t* hits, int max) {
     if (!fb || max < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
+    const FrameSlot& slot = cur_slot(fb);
     hipSetDevice(ctx->device);
     HIPCHK(ctx, fb_sync(fb));
     int c[128];
-    HIPCHK(ctx, hipMemcpy(c, fb->counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(c, slot.counters.get(), sizeof(c), hipMemcpyDeviceToHost));
     for (int b = 0; b < max && b < 32; ++b) {
-        const bool live = b < fb->lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
+        const bool live = b < slot.lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
         if (hits) hits[b] = live ? c[64 + b] : 0;
     }
     return MCRT_OK;
@@ -2819,12 +2650,13 @@ MCRT_API mcrt_status mcrt_framebuffer_hint_counts(mcrt_framebuffer fb, int32_t* 
 MCRT_API mcrt_status mcrt_framebuffer_retrace_counts(mcrt_framebuffer fb, int32_t* retraces, int max) {
     if (!fb || max < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
+    const FrameSlot& slot = cur_slot(fb);
     hipSetDevice(ctx->device);
     HIPCHK(ctx, fb_sync(fb));
     int c[128];
-    HIPCHK(ctx, hipMemcpy(c, fb->counters, sizeof(c), hipMemcpyDeviceToHost));
+    HIPCHK(ctx, hipMemcpy(c, slot.counters.get(), sizeof(c), hipMemcpyDeviceToHost));
     for (int b = 0; b < max && b < 32; ++b) {
-        const bool live = b + 1 < fb->lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
+        const bool live = b + 1 < slot.lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
         if (retraces) retraces[b] = live ? c[96 + b] : 0;
     }
     return MCRT_OK;
@@ -2834,12 +2666,12 @@ MCRT_API mcrt_status mcrt_framebuffer_wave_clock(mcrt_framebuffer fb, int which,
                                                  int64_t* blocks) {
     if (!fb || which < 0 || which > 2 || !blocks) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
-    *blocks = (int64_t)fb->waveClkBlocks[which];
-    if (!host_out || !fb->waveClk[which]) return MCRT_OK;
+    *blocks = (int64_t)(fb->waveClk[which].size() / 2);
+    if (!host_out || !fb->waveClk[which].get()) return MCRT_OK;
     hipSetDevice(ctx->device);
     HIPCHK(ctx, fb_sync(fb));
-    const size_t n = std::min((size_t)std::max<int64_t>(max_blocks, 0), fb->waveClkBlocks[which]);
-    HIPCHK(ctx, hipMemcpy(host_out, fb->waveClk[which], 8 * n, hipMemcpyDeviceToHost));
+    const size_t n = std::min((size_t)std::max<int64_t>(max_blocks, 0), fb->waveClk[which].size() / 2);
+    HIPCHK(ctx, hipMemcpy(host_out, fb->waveClk[which].get(), 8 * n, hipMemcpyDeviceToHost));
     return MCRT_OK;
 }
 
@@ -2847,21 +2679,22 @@ MCRT_API mcrt_status mcrt_framebuffer_read_queue(mcrt_framebuffer fb, int which,
                                                  int64_t max_records, int32_t* count) {
     if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
     mcrt_ctx ctx = fb->ctx;
+    const FrameSlot& slot = cur_slot(fb);
     if (which != 0 && which != 1) return fail(ctx, MCRT_ERROR_INVALID_ARG, "which must be 0 (shadow) or 1 (extension)");
     if (max_records < 0 || (max_records > 0 && !host_dst)) return fail(ctx, MCRT_ERROR_INVALID_ARG, "bad destination");
-    if (fb->lastMaxDepth <= 0) return fail(ctx, MCRT_ERROR_INVALID_ARG, "nothing rendered yet");
+    if (slot.lastMaxDepth <= 0) return fail(ctx, MCRT_ERROR_INVALID_ARG, "nothing rendered yet");
     hipSetDevice(ctx->device);
     HIPCHK(ctx, fb_sync(fb));
     int c[64];
-    HIPCHK(ctx, hipMemcpy(c, fb->counters, sizeof(c), hipMemcpyDeviceToHost));
-    const int b = which == 0 ? fb->lastMaxDepth - 1 : fb->lastMaxDepth - 2;   // last shadow / last extension queue
+    HIPCHK(ctx, hipMemcpy(c, slot.counters.get(), sizeof(c), hipMemcpyDeviceToHost));
+    const int b = which == 0 ? slot.lastMaxDepth - 1 : slot.lastMaxDepth - 2;   // last shadow / last extension queue
     const int n = b < 0 ? 0 : (which == 0 ? c[b] : c[32 + b]);
     if (count) *count = n;
     const int64_t m = std::min<int64_t>(n, max_records);
     if (m == 0) return MCRT_OK;
     const float4* src[3];
-    if (which == 0) { src[0] = fb->sO; src[1] = fb->sD; src[2] = fb->sL; }
-    else { src[0] = fb->eO[b & 1]; src[1] = fb->eD[b & 1]; src[2] = fb->eT[b & 1]; }   // b >= 0 here
+    if (which == 0) { src[0] = slot.sO.get(); src[1] = slot.sD.get(); src[2] = slot.sL.get(); }
+    else { src[0] = slot.eO[b & 1].get(); src[1] = slot.eD[b & 1].get(); src[2] = slot.eT[b & 1].get(); }   // b >= 0 here
     for (int k = 0; k < 3; ++k)
         HIPCHK(ctx, hipMemcpy(static_cast<char*>(host_dst) + (size_t)k * 16 * max_records, src[k], 16 * (size_t)m,
                               hipMemcpyDeviceToHost));
@@ -2909,21 +2742,21 @@ MCRT_API mcrt_status mcrt_bdpt_splats_sparse(mcrt_framebuffer fb, void* d_dst, i
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame rendered with the dense splat exchange (mcrt_bdpt_splats_copy)");
     if (bands > 64) return fail(ctx, MCRT_ERROR_INVALID_ARG, "sparse splat exchange: at most 64 bands");
     hipSetDevice(ctx->device);
-    BdptSet& bs = fb->bset[fb->bdptSet];
-    hipStream_t st = fb->slot[fb->cur].stream;
+    BdptSet& bs = cur_bset(fb);
+    hipStream_t st = cur_slot(fb).stream;
     BdptArgs b{};
-    b.splatList = bs.splatList;
-    b.splatListCount = fb->bdptCounters + BDPT_CNT_SPLATS;
-    b.splatListCap = (int)std::min(bs.splatListCap, (size_t)INT32_MAX);
+    b.splatList = bs.splatList.get();
+    b.splatListCount = bs.bdptCounters.get() + BDPT_CNT_SPLATS;
+    b.splatListCap = (int)std::min(bs.splatList.size(), (size_t)INT32_MAX);
     b.splatW = (int)fb->bands.W;
     b.splatN0 = (int)(fb->bands.W * fb->bands.H);
     b.splatBpb = fb->bands.bandRows / 8;
     b.splatBands = bands;
     b.splatBand = fb->bands.bandIndex;
     int h[64];
-    HIPCHK(ctx, hipMemsetAsync(bs.splatAux, 0, 128 * sizeof(int), st));
-    mcrt::launch_splat_hist(b, bs.splatAux, st);
-    HIPCHK(ctx, hipMemcpyAsync(h, bs.splatAux, sizeof(int) * bands, hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemsetAsync(bs.splatAux.get(), 0, 128 * sizeof(int), st));
+    mcrt::launch_splat_hist(b, bs.splatAux.get(), st);
+    HIPCHK(ctx, hipMemcpyAsync(h, bs.splatAux.get(), sizeof(int) * bands, hipMemcpyDeviceToHost, st));
     HIPCHK(ctx, hipStreamSynchronize(st));   // the sizes go to the host (an all-to-all's split sizes)
     mcrt::SplatOffsets off{};
     int64_t total = 0;
@@ -2939,7 +2772,7 @@ MCRT_API mcrt_status mcrt_bdpt_splats_sparse(mcrt_framebuffer fb, void* d_dst, i
     // for every other slot's completed frame, as mcrt_bdpt_splats_copy does
     for (auto& k : fb->slot)
         if (k.stream && k.stream != st) HIPCHK(ctx, hipStreamWaitEvent(st, k.done, 0));
-    mcrt::launch_splat_group(b, off, bs.splatAux + 64, (float4*)d_dst, st);
+    mcrt::launch_splat_group(b, off, bs.splatAux.get() + 64, (float4*)d_dst, st);
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;   // grouping enqueued on the frame's stream
 }
@@ -2952,16 +2785,17 @@ MCRT_API mcrt_status mcrt_bdpt_gather_sparse(mcrt_framebuffer fb, const void* d_
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame rendered with the dense splat exchange (mcrt_bdpt_gather)");
     if (records < 0 || records > INT32_MAX) return fail(ctx, MCRT_ERROR_INVALID_ARG, "bad record count");
     hipSetDevice(ctx->device);
-    FrameSlot& slot = fb->slot[fb->cur];
+    FrameSlot& slot = cur_slot(fb);
+    const BdptSet& bs = cur_bset(fb);
     hipStream_t st = slot.stream;
-    mcrt::launch_splat_unpack((const float4*)d_recv, (int)records, fb->splat, st);
+    mcrt::launch_splat_unpack((const float4*)d_recv, (int)records, bs.splat.get(), st);
     BdptArgs b{};
-    b.slots = fb->slots;
-    b.splat = fb->splat;
+    b.slots = bs.slots.get();
+    b.splat = bs.splat.get();
     b.ownSlots = bdpt_max_connections(fb->bdptDepth) - fb->bdptDepth;
     {
         Timed t(ctx, K_BDPT_GATHER, nullptr, (int64_t)fb->bands.numTiles * 64 * fb->bands.batch, st);
-        mcrt::launch_bdpt_gather(fb->bands, b, fb->radiance, nullptr, 0, st);   // the rank's own plane
+        mcrt::launch_bdpt_gather(fb->bands, b, slot.radiance.get(), nullptr, 0, st);   // the rank's own plane
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(slot.done, st));
@@ -2978,21 +2812,21 @@ MCRT_API mcrt_status mcrt_bdpt_splats_copy(mcrt_framebuffer fb, void* d_dst) {
     hipSetDevice(ctx->device);
     const size_t chunk = splat_chunk_pixels(fb->bands);   // per frame; a rank's chunk holds batch of them
     const size_t total = chunk * (size_t)std::max(fb->bands.batch, 1) * (size_t)fb->bands.numBands;
-    FrameSlot& slot = fb->slot[fb->cur];
+    FrameSlot& slot = cur_slot(fb);
     hipStream_t st = slot.stream ? slot.stream : ctx->stream;
     // the caller's buffer may still be read by an earlier frame's gather on another slot's stream
     for (auto& k : fb->slot)
         if (k.stream && k.stream != st) HIPCHK(ctx, hipStreamWaitEvent(st, k.done, 0));
     HIPCHK(ctx, hipMemsetAsync(d_dst, 0, sizeof(float) * MCRT_SPLAT_CHANNELS * total, st));
     if (fb->bdptPendingGather)   // (else, e.g. a scene without lights: the frame is complete, no splats)
-        mcrt::launch_bdpt_splat_pack(fb->bands, chunk, fb->splat, (float*)d_dst, st);
+        mcrt::launch_bdpt_splat_pack(fb->bands, chunk, cur_bset(fb).splat.get(), (float*)d_dst, st);
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;   // enqueued on the frame's stream (mcrt_framebuffer_stream): no host sync
 }
 
 MCRT_API mcrt_status mcrt_framebuffer_stream(mcrt_framebuffer fb, void** stream) {
     if (!fb || !stream) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    const FrameSlot& slot = fb->slot[fb->cur];
+    const FrameSlot& slot = cur_slot(fb);
     *stream = (void*)(slot.stream ? slot.stream : fb->ctx->stream);
     return MCRT_OK;
 }
@@ -3004,15 +2838,15 @@ MCRT_API mcrt_status mcrt_bdpt_gather(mcrt_framebuffer fb, const void* d_own_chu
     if (fb->splatExchange == MCRT_SPLAT_EXCHANGE_SPARSE)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame rendered with the sparse splat exchange (mcrt_bdpt_gather_sparse)");
     hipSetDevice(ctx->device);
-    FrameSlot& slot = fb->slot[fb->cur];
+    FrameSlot& slot = cur_slot(fb);
     hipStream_t st = slot.stream;
     BdptArgs b{};
-    b.slots = fb->slots;
-    b.splat = fb->splat;
+    b.slots = cur_bset(fb).slots.get();
+    b.splat = cur_bset(fb).splat.get();
     b.ownSlots = bdpt_max_connections(fb->bdptDepth) - fb->bdptDepth;
     {
         Timed t(ctx, K_BDPT_GATHER, nullptr, (int64_t)fb->bands.numTiles * 64 * fb->bands.batch, st);
-        mcrt::launch_bdpt_gather(fb->bands, b, fb->radiance, (const float*)d_own_chunk,
+        mcrt::launch_bdpt_gather(fb->bands, b, slot.radiance.get(), (const float*)d_own_chunk,
                                  splat_chunk_pixels(fb->bands), st);
     }
     HIPCHK(ctx, hipGetLastError());
@@ -3029,16 +2863,17 @@ MCRT_API mcrt_status mcrt_framebuffer_read_bdpt(mcrt_framebuffer fb, int which, 
     // the planes of the last BDPT call's batch (plane stride N x batch)
     const size_t N = fb->N * (size_t)fb->bdptBatch, D = (size_t)fb->bdptDepth;
     const size_t C = (size_t)bdpt_max_connections(fb->bdptDepth);
+    const BdptSet& bs = cur_bset(fb);
     const void* src = nullptr;
     size_t sz = 0;
     switch (which) {
-    case 0: src = fb->camV; sz = 16 * N * BDPT_VERTEX_PLANES * (D + 2); break;
-    case 1: src = fb->lightV; sz = 16 * N * BDPT_VERTEX_PLANES * (D + 1); break;
-    case 2: src = fb->camCount; sz = 4 * N; break;
-    case 3: src = fb->lightCount; sz = 4 * N; break;
-    case 4: src = fb->slots; sz = 16 * N * (C - D); break;
-    case 5: src = fb->sampLight; sz = 16 * fb->N * D; break;   // per pixel, carried across frames
-    case 6: src = fb->splat; sz = 16 * N; break;
+    case 0: src = bs.camV.get(); sz = 16 * N * BDPT_VERTEX_PLANES * (D + 2); break;
+    case 1: src = bs.lightV.get(); sz = 16 * N * BDPT_VERTEX_PLANES * (D + 1); break;
+    case 2: src = bs.camCount.get(); sz = 4 * N; break;
+    case 3: src = bs.lightCount.get(); sz = 4 * N; break;
+    case 4: src = bs.slots.get(); sz = 16 * N * (C - D); break;
+    case 5: src = fb->sampLight.get(); sz = 16 * fb->N * D; break;   // per pixel, carried across frames
+    case 6: src = bs.splat.get(); sz = 16 * N; break;
     default: return fail(ctx, MCRT_ERROR_INVALID_ARG, "which must be 0..6");
     }
     if (needed) *needed = sz;

@@ -1,7 +1,7 @@
 // Sanitizer run of the host-side code (no GPU): OBJ/MTL ingestion (mcrt_objload.cpp), the host camera
 // (mcrt_camera.cpp), the host Bvh2 restatement (mcrt_bvh.cpp) and the oracle (oracle/mcrt_oracle.c:
 // BVH build, closest / any-hit traversal against brute force, one PT and one BDPT frame, accumulate,
-// denoise, tone map), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
+// denoise, tone map) and the runtime's owning device-buffer type (mcrt_devbuf.h, over malloc / free), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
 // every check held and the sanitizers reported nothing (they abort on the first finding).
 #include <unistd.h>
 
@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "../../monte-carlo-raytracer_amd/csrc/mcrt_devbuf.h"
 #include "../../monte-carlo-raytracer_amd/csrc/mcrt_internal.h"
 extern "C" {
 #include "../../oracle/mcrt_oracle.h"
@@ -33,6 +34,92 @@ void set_last_error(const std::string& m) { g_err = m; }
 }
 extern "C" const char* mcrt_last_error(mcrt_ctx) { return g_err.c_str(); }
 
+// DevBuf (mcrt_devbuf.h) over malloc / free: its three device functions count their calls, remember
+// the last synchronised stream and the order of the last synchronisation and free, and the
+// g_failAt-th allocation from now fails (0: none)
+static int g_allocs = 0, g_frees = 0, g_syncs = 0, g_failAt = 0, g_tick = 0, g_syncTick = 0, g_freeTick = 0;
+static void* g_lastStream = nullptr;
+namespace mcrt {
+int dev_alloc(void** p, size_t bytes) {
+    *p = nullptr;
+    if (g_failAt > 0 && --g_failAt == 0) return 2;   // any non-zero code
+    *p = std::malloc(bytes ? bytes : 1);
+    ++g_allocs;
+    return 0;
+}
+void dev_free(void* p) {
+    std::free(p);
+    ++g_frees;
+    g_freeTick = ++g_tick;
+}
+int dev_sync(void* stream) {
+    g_lastStream = stream;
+    ++g_syncs;
+    g_syncTick = ++g_tick;
+    return 0;
+}
+}  // namespace mcrt
+
+static int devbuf_checks() {
+    using mcrt::DevBuf;
+    struct Set {   // like the runtime's frame slots and BDPT sets
+        DevBuf<float> a, b[2];
+        DevBuf<int> c;
+        int frames = 0;
+    };
+    int streamA = 0, streamB = 0;
+    {
+        DevBuf<float> x;
+        CHECK(!x && x.size() == 0 && x.get() == nullptr);
+        CHECK(x.alloc(100) == 0 && x && x.size() == 100);
+        x.get()[99] = 1.0f;
+        // grow to a smaller or equal count: nothing allocated, nothing synchronised
+        const float* before = x.get();
+        CHECK(x.grow(100, &streamA) == 0 && x.grow(7, &streamA) == 0 && x.grow(0, &streamA) == 0);
+        CHECK(x.get() == before && x.size() == 100 && g_allocs == 1 && g_frees == 0 && g_syncs == 0);
+        // grow to a larger count: the given stream is synchronised before the old memory is freed
+        CHECK(x.grow(101, &streamB) == 0 && x.size() == 101);
+        x.get()[100] = 2.0f;
+        CHECK(g_lastStream == &streamB && g_syncs == 1 && g_allocs == 2 && g_frees == 1 && g_syncTick < g_freeTick);
+        // a failed grow: empty, size 0, every allocation so far freed
+        g_failAt = 1;
+        CHECK(x.grow(1000, &streamA) != 0);
+        CHECK(!x && x.size() == 0 && x.get() == nullptr && g_lastStream == &streamA && g_allocs == 2 && g_frees == 2);
+        // ... and usable again
+        CHECK(x.grow(10, &streamA) == 0 && x.size() == 10 && g_allocs == 3 && g_frees == 2);
+        // move-assigning over a full buffer frees the old memory exactly once
+        DevBuf<float> y;
+        CHECK(y.alloc(5) == 0 && g_allocs == 4);
+        const float* py = y.get();
+        x = std::move(y);
+        CHECK(g_frees == 3 && x.get() == py && x.size() == 5 && !y && y.size() == 0);
+        // swap frees nothing
+        CHECK(y.alloc(6) == 0 && g_allocs == 5);
+        const float* py2 = y.get();
+        std::swap(x, y);
+        CHECK(g_frees == 3 && x.get() == py2 && x.size() == 6 && y.get() == py && y.size() == 5);
+        swap(x, y);
+        CHECK(g_frees == 3 && x.get() == py && y.get() == py2);
+        // reset frees; a second reset and the destructor of an empty buffer do not
+        x.reset();
+        x.reset();
+        CHECK(g_frees == 4 && !x);
+        // a struct of buffers reassigned from a default-constructed one frees all of them
+        Set s;
+        CHECK(s.a.alloc(3) == 0 && s.b[0].alloc(4) == 0 && s.b[1].alloc(5) == 0 && s.c.alloc(6) == 0);
+        s.frames = 2;
+        const int freesBefore = g_frees;
+        s = Set();
+        CHECK(g_frees == freesBefore + 4 && !s.a && !s.b[0] && !s.b[1] && !s.c && s.frames == 0);
+        // a moved struct keeps its buffers; y and the struct free theirs at the end of the scope
+        CHECK(s.a.alloc(8) == 0);
+        Set t = std::move(s);
+        CHECK(t.a.size() == 8 && !s.a && g_frees == freesBefore + 4);
+    }
+    CHECK(g_allocs == g_frees && g_allocs == 10);
+    return 0;
+}
+
 static void write_file(const std::string& p, const char* text) {
     FILE* f = std::fopen(p.c_str(), "w");
     std::fputs(text, f);
@@ -40,6 +127,7 @@ static void write_file(const std::string& p, const char* text) {
 }
 
 int main() {
+    if (devbuf_checks() != 0) return 1;
     // a room (floor, back wall), a box, an emissive quad and a quad fan, with an MTL
     char tmpl[] = "/tmp/mcrt_asan_XXXXXX";
     const char* dir = mkdtemp(tmpl);

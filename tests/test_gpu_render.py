@@ -292,6 +292,103 @@ def test_batched_no_lights_after_lit_batch(hip_ctx, mixed):
     ds.close()
 
 
+def test_regrown_slots_and_sets_bit_exact(hip_ctx, mixed):
+    """One frame buffer taken through every way its frame slots and BDPT sets are allocated, regrown
+    and freed.  After each step its read-backs are compared with those of a fresh context and frame
+    buffer (one frame in flight) that ran the step alone -- a PT frame depends only on its
+    arguments -- or, for BDPT, the BDPT steps since the last depth change (the sampled-light planes
+    carry state between frames):
+      * PT: every frame's radiance, the image accumulated from the step's frames and the ray
+        statistics, bit for bit;
+      * BDPT: the sampled-light planes, both subpaths' vertex counts, the own-strategy slots and the
+        statistics bit for bit, and the radiance bit for bit wherever no light-tracing splat landed.
+        The splats are float atomics whose order varies from run to run of the same code (two runs
+        of the parent commit differ in 2 of 3200 words by one ulp), so elsewhere, and for the
+        image, test_gpu_bdpt.py's splat tolerance holds: 4e-6 relative, a few ulp of a sum of
+        <= ~30 non-negative terms.
+    40 x 20: the last tile column is full, the last tile row partial, and the slots' and sets'
+    sizes (whole 8 x 8 tiles) differ from the pixel count."""
+    from mcrt import lib
+    sc, _ = mixed
+    W, H = 40, 20
+    cams = [scene_camera("mixed", W, H, frame=f, jitter=True) for f in range(4)]
+    filt = T.make_filter(T.BOX)
+    pt, bd2, bd3 = dict(max_depth=3), dict(max_depth=2, integrator=T.INTEGRATOR_BDPT), \
+        dict(max_depth=3, integrator=T.INTEGRATOR_BDPT)
+    bands = dict(max_depth=3, band_rows=8, num_bands=2, band_index=1)
+    # (what the step exercises, frames in flight, calls: (cameras, first frame, render arguments))
+    steps = [("first frame", 1, [(cams[:1], 0, pt)]),
+             ("batch of 4: slot 0 regrown", 1, [(cams, 1, pt)]),
+             ("two frames in flight: second slot", 2, [(cams[f:f + 1], 5 + f, pt) for f in range(3)]),
+             ("two bands", 2, [(cams[:1], 8, bands)]),
+             ("BDPT, depth 2", 1, [(cams[:1], 0, bd2)]),
+             ("BDPT batch of 3: set regrown", 1, [(cams[1:], 1, bd2)]),
+             ("BDPT, depth 3: sets and sampled-light planes freed", 1, [(cams[:1], 4, bd3)]),
+             ("path tracer again", 1, [(cams[:2], 9, dict(max_depth=2))])]
+    exact_planes = ("sampled_light", "camera_counts", "light_counts", "slots")
+
+    def run(fb, ds, calls):
+        done = 0
+        for cs, frame, args in calls:
+            fb.render_frames(ds, cs, frame=frame, **args)
+            fb.accumulate(filt, done)   # index 0 restarts the accumulators: the image is this step's
+            done += len(cs)
+        B = len(calls[-1][0])
+        out = {"frames": [fb.read_frame(k) for k in range(B)] + [fb.read(0)], "img": fb.read(2), "stats": fb.stats()}
+        if "integrator" in calls[-1][2]:
+            out["planes"] = {k: fb.read_bdpt(k) for k in exact_planes}
+            splat = fb.read_bdpt("splat").view(np.float32).reshape(B, H, W, 4)
+            out["nosplat"] = [(splat[k][..., :3] == 0).all(-1) for k in range(B)] + [(splat[0][..., :3] == 0).all(-1)]
+        return out
+
+    def close(a, b):
+        a, b = a[..., :3], b[..., :3]
+        return (np.abs(a - b) <= 4e-6 * (np.abs(a) + np.abs(b)) + 1e-30).all()
+
+    ds = lib.DeviceScene(hip_ctx, sc)
+    fb = lib.FrameBuffer(hip_ctx, W, H)
+    replay = []   # the BDPT steps since the last depth change
+    for what, fif, calls in steps:
+        fb.set_frames_in_flight(fif)
+        got = run(fb, ds, calls)
+        args = calls[-1][2]
+        bdpt = "integrator" in args
+        if bdpt:
+            if replay and replay[-1][-1][2] is not args:
+                replay = []
+            replay.append(calls)
+        ctx2 = lib.Context(0)
+        ds2 = lib.DeviceScene(ctx2, sc)
+        fb2 = lib.FrameBuffer(ctx2, W, H)
+        fb2.set_frames_in_flight(1)
+        for earlier in (replay[:-1] if bdpt else []):
+            run(fb2, ds2, earlier)
+        want = run(fb2, ds2, calls)
+        fb2.close()
+        ds2.close()
+        ctx2.close()
+        # a band's frame writes its own rows only: the other rows keep what the buffer held
+        nb, bi = args.get("num_bands", 1), args.get("band_index", 0)
+        rows = [y for y in range(H) if (y // 8) % nb == bi]
+        for k, (g, w) in enumerate(zip(got["frames"], want["frames"])):
+            assert np.isfinite(g).all(), what
+            same = g[rows].view(np.uint32) == w[rows].view(np.uint32)
+            if bdpt:
+                assert same[(got["nosplat"][k] & want["nosplat"][k])[rows]].all() and close(g, w), (what, k)
+            else:
+                assert same.all(), (what, k)
+        if bdpt:
+            for k in exact_planes:
+                np.testing.assert_array_equal(got["planes"][k], want["planes"][k], err_msg=f"{what}: {k}")
+            assert close(got["img"], want["img"]), what
+        else:
+            np.testing.assert_array_equal(got["img"][rows].view(np.uint32), want["img"][rows].view(np.uint32), err_msg=what)
+        assert got["img"][rows][..., :3].max() > 0, what
+        assert got["stats"] == want["stats"] and got["stats"]["closest_rays"] > 0, what
+    fb.close()
+    ds.close()
+
+
 @pytest.mark.parametrize("ranks,W,H,BR", [(1, 64, 40, 8), (2, 96, 80, 8), (3, 96, 84, 8), (3, 96, 84, 16),
                                          (8, 64, 140, 8)])
 def test_band_pack_unpack_through_product(hip_ctx, mixed, ranks, W, H, BR):
