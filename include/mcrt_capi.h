@@ -641,9 +641,10 @@ MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_
  * Everything is enqueued on the context stream after the last accumulate and the guides, as
  * mcrt_denoise_guided; mcrt_framebuffer_read_temporal synchronises.
  *
- * Not covered: per-object motion vectors.  A moved instance's history is rejected by the plane
- * test, or ghosts when the instance slides within its own plane.  Band-split or multi-rank history
- * is not kept either: run this on the gathering rank. */
+ * mcrt_temporal_accumulate assumes a static world: a moved instance's history is rejected by the
+ * plane test, or ghosts when the instance slides within its own plane.  The per-object motion
+ * section below reprojects through each shape's own motion.  Band-split or multi-rank history is
+ * not kept: run this on the gathering rank. */
 typedef struct {
     float   alpha;              /* weight floor of the new frame's colour, 0..1, default 0.2 */
     float   alpha_moments;      /* same for the luminance moments, default 0.2 */
@@ -663,6 +664,70 @@ MCRT_API mcrt_status mcrt_framebuffer_set_temporal_history(mcrt_framebuffer fb, 
                                                            const mcrt_camera* prev_camera);
 MCRT_API mcrt_status mcrt_framebuffer_read_temporal(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
                                                     uint64_t* needed);
+
+/* ---- Per-object motion for the temporal history -------------------------------------------------
+ * Reprojects the history through the motion of the shape each pixel sees, so that an object moved
+ * with mcrt_accel_update_transforms (or mcrt_scene_update_shapes + mcrt_accel_build) keeps its
+ * history.  Opt-in like the sections above: without these calls no launch, buffer, kernel argument
+ * or output of any other call changes.  Per displayed frame:
+ *   1. mcrt_scene_motion_snapshot(scene)          -- the poses of the frame just shown,
+ *   2. mcrt_accel_update_transforms(scene, ...)   -- this frame's poses,
+ *   3. render 1..k frames and accumulate them starting at frame_index 0,
+ *   4. mcrt_render_guides_motion(scene, fb, camera, params),
+ *   5. mcrt_temporal_accumulate_motion(fb, camera, params),
+ *   6. mcrt_denoise_guided_temporal(fb, params, feedback_level)   -- unchanged.
+ *
+ * mcrt_scene_motion_snapshot records, for every shape, the current toWorldTransform,
+ * toWorldInverseTranspose and mesh key (startIdx, startVertex, numTriangles) as its previous pose:
+ * a device table owned by the scene, 144 B per shape, allocated by the first snapshot and copied
+ * out of the scene's shape array on the context stream.  It sees every mcrt_scene_update_shapes /
+ * mcrt_accel_update_transforms made before it and none made after, and needs no mcrt_accel_build.
+ *
+ * mcrt_render_guides_motion is mcrt_render_guides (the same host path, the same two guide planes,
+ * bit for bit) whose one guide launch also writes two more float4 planes owned by the frame buffer
+ * (allocated on first use), for the rows the band fields select:
+ *   motion           (P_prev - P, flag), P the hit point, P_prev the same surface point under the
+ *                    shape's previous pose: the hit's three object-space vertices through the
+ *                    table's toWorldTransform and the same barycentric blend, then one subtraction
+ *                    per component.
+ *                    flag  0: static -- no snapshot yet, or all 32 matrix floats (compared as
+ *                             uint32) and the mesh key equal the table's; the record is exactly
+ *                             (0, 0, 0, 0).  A miss holds the same.
+ *                    flag  1: moved.
+ *                    flag -1: no previous pose -- the mesh key differs; the record is (0, 0, 0, -1).
+ *   previous normal  (n_prev, 0) where flag is 1, (0, 0, 0, 0) elsewhere: the interpolated shading
+ *                    normal formed from the object-space normals through the table's
+ *                    toWorldInverseTranspose (so non-uniform scales and mirrors need no case),
+ *                    flipped exactly when the guide normal was: the same physical side.
+ * mcrt_framebuffer_set_motion installs both planes from device memory (tests, other renderers).
+ * The motion planes belong to one set of guides: mcrt_render_guides and mcrt_framebuffer_set_guides
+ * make them stale.  mcrt_framebuffer_read_motion: which 0 motion, 1 previous normal; needed /
+ * host_dst / bytes as mcrt_framebuffer_read_guides.
+ *
+ * mcrt_temporal_accumulate_motion is mcrt_temporal_accumulate (parameters, validation, plane swap,
+ * variance) with, per pixel, mv = motion[p]:
+ *   flag  1:  P - prev.pos becomes (P - prev.pos) + mv.xyz, and the normal test compares the
+ *             history tap with n_prev instead of the guide normal; the plane test, the clip
+ *             coordinates and the tolerance use the moved offset,
+ *   flag  0:  as mcrt_temporal_accumulate (with an all-zero motion plane every plane written is
+ *             bit-identical to it),
+ *   flag -1:  no tap is tested: N = 1 and the current values.
+ * The record written to the previous normal-plane history is the current guide record either way.
+ * A background pixel an object has uncovered (flag 0) reprojects onto where the object was and is
+ * rejected by the plane test, like a camera-move disocclusion.
+ *
+ * MCRT_ERROR_NOT_READY in addition to the calls they extend: mcrt_temporal_accumulate_motion without
+ * motion planes belonging to the current guides.
+ * Not covered: deforming geometry (a changed mesh key gives flag -1), moving lights and the shading
+ * lag of moved shadows and reflections, motion under a band split or across ranks. */
+MCRT_API mcrt_status mcrt_scene_motion_snapshot(mcrt_scene scene);
+MCRT_API mcrt_status mcrt_render_guides_motion(mcrt_scene scene, mcrt_framebuffer fb, const mcrt_camera* camera,
+                                               const mcrt_frame_params* params);
+MCRT_API mcrt_status mcrt_framebuffer_set_motion(mcrt_framebuffer fb, const void* d_motion, const void* d_prev_normal);
+MCRT_API mcrt_status mcrt_framebuffer_read_motion(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                  uint64_t* needed);
+MCRT_API mcrt_status mcrt_temporal_accumulate_motion(mcrt_framebuffer fb, const mcrt_camera* camera,
+                                                     const mcrt_temporal_params* params);
 /* Copies device -> host (RGBA32F, W*H*4 floats).  which: 0 radiance, 1 weighted sum, 2 image,
  * 3 display image (mcrt_postprocess, mcrt_denoise_guided). */
 MCRT_API mcrt_status mcrt_framebuffer_read(mcrt_framebuffer fb, int which, float* host_rgba);

@@ -46,7 +46,7 @@ enum KernelId {
     K_BDPT_START, K_BDPT_VERTEX, K_BDPT_CONNECT, K_BDPT_VIS, K_BDPT_GATHER, K_SHADOW_EXTEND,
     K_GUIDES, K_MOMENTS, K_ATROUS_PREP,
     K_ATROUS,   // one entry per level: K_ATROUS + i is the launch of step 2^i
-    K_TEMPORAL = K_ATROUS + MCRT_ATROUS_MAX_LEVELS, K_TEMPORAL_VAR,
+    K_TEMPORAL = K_ATROUS + MCRT_ATROUS_MAX_LEVELS, K_TEMPORAL_VAR, K_GUIDES_MOTION, K_TEMPORAL_MOTION,
     K_COUNT
 };
 const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN",       "k_shadow",   "k_extend",
@@ -55,7 +55,7 @@ const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN"
                                      "k_shadow_extend", "k_guides",      "k_moments",    "k_atrous_prep",
                                      "k_atrous_s1",   "k_atrous_s2",   "k_atrous_s4",  "k_atrous_s8",
                                      "k_atrous_s16",  "k_atrous_s32",  "k_atrous_s64", "k_atrous_s128",
-                                     "k_temporal",    "k_temporal_var"};
+                                     "k_temporal",    "k_temporal_var", "k_guides_motion", "k_temporal_motion"};
 
 }  // namespace
 
@@ -136,6 +136,9 @@ struct mcrt_scene_s {
     mcrt::TopBuildDev* topDev = nullptr;
     int updatePath = 0;
     double updateMs = 0.0;
+    // previous poses (mcrt_scene_motion_snapshot): one record per shape, allocated by the first
+    // snapshot; only k_guides_motion receives it
+    DevBuf<PrevPose> dPrevPose;
     ~mcrt_scene_s() { mcrt::top_build_destroy(topDev); }   // the buffers free themselves
 };
 
@@ -265,6 +268,11 @@ struct mcrt_framebuffer_s {
     bool tFedBack = false;           // the colour history already holds a filtered level of this accumulate
     int tDemod = 0;                  // demodulate_albedo of the last accumulate
     mcrt_camera tPrevCam = {};       // camera of the history planes
+    // Per-object motion (mcrt_render_guides_motion), allocated on first use; they belong to one set
+    // of guides, so whatever replaces the guides alone clears haveMotion
+    DevBuf<float4> motion;           // (P_prev - P, flag)
+    DevBuf<float4> motionNormal;     // (n_prev, 0) where flag is 1
+    bool haveMotion = false;
 };
 // The slot of the last rendered frame and the set of the last BDPT call: what the read-back entry
 // points show.  After a failed regrow their buffers are empty, never stale.
@@ -859,6 +867,18 @@ MCRT_API mcrt_status mcrt_scene_update_shapes(mcrt_scene s, const mcrt_shape* sh
     mcrt_status st = replace_array(s, s->dShapes, sh, n);
     if (st != MCRT_OK) return st;
     HIPCHK(s->ctx, build_surface_records(s));   // startVertex may have moved
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_scene_motion_snapshot(mcrt_scene s) {
+    if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
+    mcrt_ctx ctx = s->ctx;
+    const size_t n = s->shapes.size();
+    if (n == 0 || !s->dShapes) return fail(ctx, MCRT_ERROR_INVALID_ARG, "scene has no shapes");
+    hipSetDevice(ctx->device);
+    if (!s->dPrevPose) HIPCHK(ctx, s->dPrevPose.alloc(n));
+    mcrt::launch_pose_snapshot(s->dShapes.get(), s->dPrevPose.get(), (int)n, ctx->stream);
+    HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
 }
 
@@ -2179,8 +2199,16 @@ static hipError_t ensure_guides(mcrt_framebuffer fb) {
     return e;
 }
 
-MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
-                                        const mcrt_frame_params* p) {
+static hipError_t ensure_motion(mcrt_framebuffer fb) {
+    hipError_t e = ensure_plane(fb, fb->motion);
+    if (e == hipSuccess) e = ensure_plane(fb, fb->motionNormal);
+    return e;
+}
+
+// mcrt_render_guides and, with `motion`, mcrt_render_guides_motion: the same host path, one launch
+// of k_guides or of k_guides_motion
+static mcrt_status render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_frame_params* p,
+                                 bool motion) {
     if (!s || !fb || !cam || !p) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
     mcrt_ctx ctx = s->ctx;
     if (fb->ctx != ctx) return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame buffer belongs to another context");
@@ -2193,6 +2221,7 @@ MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     HIPCHK(ctx, ensure_guides(fb));
+    if (motion) HIPCHK(ctx, ensure_motion(fb));
     FrameSlot& slot = cur_slot(fb);   // as mcrt_render_aov: its camera and primary-hit buffers are reused
     if (!slot.counters) return fail(ctx, MCRT_ERROR_NOT_READY, kNoSlotBuffers);
     ctx_wait_slots(fb);
@@ -2202,7 +2231,11 @@ MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const
         return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "traversal spill buffer");
     const TraceCtx tcs = packet_ctx(s);
     mcrt::launch_primary(tcs, f, dCam, slot.hitsP.get(), st);
-    {
+    if (motion) {
+        Timed t(ctx, K_GUIDES_MOTION, nullptr, (int64_t)f.numTiles * 64);
+        mcrt::launch_guides_motion(scene_args(s), f, dCam, slot.hitsP.get(), fb->guideNormal.get(), fb->guideAlbedo.get(),
+                                   s->dPrevPose.get(), fb->motion.get(), fb->motionNormal.get(), st);
+    } else {
         Timed t(ctx, K_GUIDES, nullptr, (int64_t)f.numTiles * 64);
         mcrt::launch_guides(scene_args(s), f, dCam, slot.hitsP.get(), fb->guideNormal.get(), fb->guideAlbedo.get(), st);
     }
@@ -2210,7 +2243,18 @@ MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const
     // the slot's next render (its own stream) may overwrite those buffers only after this pass
     HIPCHK(ctx, hipEventRecord(slot.free, st));
     fb->haveGuides = true;
+    fb->haveMotion = motion;
     return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
+                                        const mcrt_frame_params* p) {
+    return render_guides(s, fb, cam, p, false);
+}
+
+MCRT_API mcrt_status mcrt_render_guides_motion(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
+                                               const mcrt_frame_params* p) {
+    return render_guides(s, fb, cam, p, true);
 }
 
 MCRT_API mcrt_status mcrt_framebuffer_set_guides(mcrt_framebuffer fb, const void* d_normal_plane,
@@ -2222,6 +2266,34 @@ MCRT_API mcrt_status mcrt_framebuffer_set_guides(mcrt_framebuffer fb, const void
     HIPCHK(ctx, hipMemcpyAsync(fb->guideNormal.get(), d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(fb->guideAlbedo.get(), d_albedo_depth, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     fb->haveGuides = true;
+    fb->haveMotion = false;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_motion(mcrt_framebuffer fb, const void* d_motion, const void* d_prev_normal) {
+    if (!fb || !d_motion || !d_prev_normal) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, ensure_motion(fb));
+    HIPCHK(ctx, hipMemcpyAsync(fb->motion.get(), d_motion, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(fb->motionNormal.get(), d_prev_normal, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    fb->haveMotion = true;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_read_motion(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                  uint64_t* needed) {
+    if (!fb || which < 0 || which > 1) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    mcrt_ctx ctx = fb->ctx;
+    const void* src = which == 0 ? fb->motion.get() : fb->motionNormal.get();
+    const uint64_t need = 16 * (uint64_t)fb->N;
+    if (needed) *needed = need;
+    if (!host_dst) return MCRT_OK;
+    if (!src) return fail(ctx, MCRT_ERROR_NOT_READY, "no motion planes yet");
+    if (bytes < need) return fail(ctx, MCRT_ERROR_INVALID_ARG, "destination too small");
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, fb_sync(fb));
+    HIPCHK(ctx, hipMemcpy(host_dst, src, need, hipMemcpyDeviceToHost));
     return MCRT_OK;
 }
 
@@ -2377,8 +2449,9 @@ static bool temporal_eager_loads() {
     return e && std::strcmp(e, "eager") == 0;
 }
 
-MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* cam,
-                                              const mcrt_temporal_params* p) {
+// mcrt_temporal_accumulate and, with `motion`, mcrt_temporal_accumulate_motion
+static mcrt_status temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_temporal_params* p,
+                                       bool motion) {
     if (!fb || !cam || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
     mcrt_ctx ctx = fb->ctx;
     if (!(p->alpha >= 0.0f && p->alpha <= 1.0f) || !(p->alpha_moments >= 0.0f && p->alpha_moments <= 1.0f))
@@ -2390,6 +2463,9 @@ MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_ca
     if (cam->width != fb->W || cam->height != fb->H)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
     if (!fb->haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
+    if (motion && !fb->haveMotion)
+        return fail(ctx, MCRT_ERROR_NOT_READY,
+                    "no motion planes for these guides (mcrt_render_guides_motion / mcrt_framebuffer_set_motion)");
     if (fb->bdptPendingGather)
         return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
     hipSetDevice(ctx->device);
@@ -2418,8 +2494,12 @@ MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_ca
     t.colourNew = fb->tColour[now].get();
     t.momentsNew = fb->tMoments[now].get();
     t.normalNew = fb->tNormal[now].get();
+    if (motion) {
+        t.motion = fb->motion.get();
+        t.prevNormal = fb->motionNormal.get();
+    }
     {
-        Timed tm(ctx, K_TEMPORAL, nullptr, (int64_t)fb->N);
+        Timed tm(ctx, motion ? K_TEMPORAL_MOTION : K_TEMPORAL, nullptr, (int64_t)fb->N);
         mcrt::launch_temporal(t, temporal_eager_loads(), st);
     }
     {
@@ -2435,6 +2515,16 @@ MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_ca
     fb->tDemod = t.demod;
     fb->tPrevCam = *cam;
     return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* cam,
+                                              const mcrt_temporal_params* p) {
+    return temporal_accumulate(fb, cam, p, false);
+}
+
+MCRT_API mcrt_status mcrt_temporal_accumulate_motion(mcrt_framebuffer fb, const mcrt_camera* cam,
+                                                     const mcrt_temporal_params* p) {
+    return temporal_accumulate(fb, cam, p, true);
 }
 
 MCRT_API mcrt_status mcrt_temporal_reset(mcrt_framebuffer fb) {

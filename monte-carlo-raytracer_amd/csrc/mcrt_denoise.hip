@@ -9,6 +9,8 @@
 //
 // Planes (W*H each): colour float4, normal-plane float4 (n.xyz, n.(P - cam.pos)), albedo-depth
 // float4 (Kd.rgb, |P - cam.pos|, -1 on a miss), variance float, moments float2 (sum l, sum l*l).
+#include <type_traits>
+
 #include "mcrt_shading.h"
 
 namespace {
@@ -251,6 +253,19 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_atrous(AtrousArgs
 //   colourNew[p] = (out.rgb, c.a);  momentsNew[p] = (mu1, mu2, N, ad.w);  normalNew[p] = g
 // EAGER = true issues the four taps' twelve 16-B records together; EAGER = false fetches the eight
 // validity records first and a tap's colour only when the tap is valid.  Same values, same bits.
+//
+// MOTION = true (mcrt_temporal_accumulate_motion) reprojects through the per-object motion of
+// k_guides_motion's planes; the lines that change:
+//   mv = motion[p]                                   (issued with image / albedoDepth / normalPlane)
+//   r  = m * k + dpos                                as above
+//   mv.w == 1:  r = r + mv.xyz (per component);  gp = prevNormal[p].xyz
+//   mv.w == 0:  gp = g.xyz                           (any other mv.w >= 0 likewise)
+//   mv.w <  0:  no taps are tested (have = false): N = 1, the current values, bit for bit
+//   cx, cy, cw, fx, fy, zr, tol from r as above;  dn = gp - pn.xyz;  res from r as above
+//   normalNew[p] = g                                 (the current record, as above)
+// prevNormal[p] is fetched where mv.w == 1 only: issued with the first batch instead it cost 7.7 %
+// more when nothing moved and the same when everything did.
+// With an all-zero motion plane the three planes written are those of MOTION = false, bit for bit.
 struct TemporalArgs {
     int W, H;
     int demod, haveHistory;
@@ -268,9 +283,13 @@ struct TemporalArgs {
     float4* momentsNew;
     float4* normalNew;
 };
+struct TemporalMotionArgs : TemporalArgs {
+    const float4* motion;       // (P_prev - P, flag)
+    const float4* prevNormal;   // (n_prev, 0) where flag is 1
+};
 
-template <bool EAGER>
-__global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal(TemporalArgs a) {
+template <bool EAGER, bool MOTION>
+__device__ __forceinline__ void temporalPixel(const typename std::conditional<MOTION, TemporalMotionArgs, TemporalArgs>::type& a) {
     const int W = a.W, H = a.H;
     const int x = blockIdx.x * ATROUS_TILE + (threadIdx.x & (ATROUS_TILE - 1));
     const int y = blockIdx.y * ATROUS_TILE + threadIdx.x / ATROUS_TILE;
@@ -279,6 +298,10 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal(Temporal
     float4 c = a.image[p];
     const float4 ad = a.albedoDepth[p];
     const float4 g = a.normalPlane[p];
+    float4 mv = make_float4(0.0f, 0.0f, 0.0f, 0.0f), gp = g;
+    if constexpr (MOTION) {
+        mv = a.motion[p];
+    }
     if (a.demod) {
         c.x = c.x / demodChannel(ad.x);
         c.y = c.y / demodChannel(ad.y);
@@ -288,7 +311,7 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal(Temporal
     const float ll = l * l;
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, s1 = 0.0f, s2 = 0.0f, sn = 0.0f;
     bool have = false;
-    if (a.haveHistory && ad.w > 0.0f) {
+    if (a.haveHistory && ad.w > 0.0f && !(MOTION && mv.w < 0.0f)) {
         const float u = (float)x / (float)W, v = (float)y / (float)H;
         float m[3], r[3];
 #pragma unroll
@@ -300,6 +323,14 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal(Temporal
         const float k = ad.w / sqrtf((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
 #pragma unroll
         for (int i = 0; i < 3; ++i) r[i] = m[i] * k + a.dpos[i];
+        if constexpr (MOTION) {
+            if (mv.w == 1.0f) {
+                r[0] = r[0] + mv.x;
+                r[1] = r[1] + mv.y;
+                r[2] = r[2] + mv.z;
+                gp = a.prevNormal[p];
+            }
+        }
         const float cx = (a.M0[0] * r[0] + a.M0[1] * r[1]) + a.M0[2] * r[2];
         const float cy = (a.M1[0] * r[0] + a.M1[1] * r[1]) + a.M1[2] * r[2];
         const float cw = (a.M3[0] * r[0] + a.M3[1] * r[1]) + a.M3[2] * r[2];
@@ -324,7 +355,7 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal(Temporal
                 }
 #pragma unroll
                 for (int t = 0; t < 4; ++t) {
-                    const float dnx = g.x - pn[t].x, dny = g.y - pn[t].y, dnz = g.z - pn[t].z;
+                    const float dnx = gp.x - pn[t].x, dny = gp.y - pn[t].y, dnz = gp.z - pn[t].z;
                     const float dn2 = (dnx * dnx + dny * dny) + dnz * dnz;
                     const float res = fabsf(((pn[t].x * r[0] + pn[t].y * r[1]) + pn[t].z * r[2]) - pn[t].w);
                     const bool valid = in[t] && hm[t].w > 0.0f && dn2 <= a.normalThr && res <= tol;
@@ -357,6 +388,16 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal(Temporal
     a.colourNew[p] = o;
     a.momentsNew[p] = make_float4(mu1, mu2, N, ad.w);
     a.normalNew[p] = g;
+}
+
+template <bool EAGER>
+__global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal(TemporalArgs a) {
+    temporalPixel<EAGER, false>(a);
+}
+
+template <bool EAGER>
+__global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal_motion(TemporalMotionArgs a) {
+    temporalPixel<EAGER, true>(a);
 }
 
 // The variance handed to the filter, from the planes k_temporal has just written; float32, each
@@ -451,7 +492,7 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal_var(int 
 namespace mcrt {
 
 void launch_temporal(const TemporalParams& t, bool eager, hipStream_t st) {
-    TemporalArgs a;
+    TemporalMotionArgs a;
     a.W = t.W;
     a.H = t.H;
     a.demod = t.demod;
@@ -489,10 +530,21 @@ void launch_temporal(const TemporalParams& t, bool eager, hipStream_t st) {
     a.momentsNew = t.momentsNew;
     a.normalNew = t.normalNew;
     const dim3 grid((t.W + ATROUS_TILE - 1) / ATROUS_TILE, (t.H + ATROUS_TILE - 1) / ATROUS_TILE);
+    const dim3 block(ATROUS_TILE * ATROUS_TILE);
+    if (t.motion) {
+        a.motion = t.motion;
+        a.prevNormal = t.prevNormal;
+        if (eager)
+            hipLaunchKernelGGL(k_temporal_motion<true>, grid, block, 0, st, a);
+        else
+            hipLaunchKernelGGL(k_temporal_motion<false>, grid, block, 0, st, a);
+        return;
+    }
+    const TemporalArgs& base = a;
     if (eager)
-        hipLaunchKernelGGL(k_temporal<true>, grid, dim3(ATROUS_TILE * ATROUS_TILE), 0, st, a);
+        hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, st, base);
     else
-        hipLaunchKernelGGL(k_temporal<false>, grid, dim3(ATROUS_TILE * ATROUS_TILE), 0, st, a);
+        hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, st, base);
 }
 
 void launch_temporal_var(int W, int H, int minHistory, float normalThr, float planeThr, const float4* moments,

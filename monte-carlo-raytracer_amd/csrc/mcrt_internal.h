@@ -55,6 +55,15 @@ struct FrameArgs {
 #define MCRT_MAX_BATCH_FRAMES 256
 #define MCRT_MAX_BDPT_BATCH_FRAMES 32
 
+// A shape's previous pose (mcrt_scene_motion_snapshot): the matrices and mesh key its mcrt_shape
+// record began with when the snapshot was taken, 144 B
+struct PrevPose {
+    mcrt_mat4 toWorldTransform;
+    mcrt_mat4 toWorldInverseTranspose;
+    uint32_t startIdx, startVertex, numTriangles, pad;
+};
+static_assert(sizeof(PrevPose) == 144 && offsetof(mcrt_shape, numTriangles) == 136, "PrevPose is the head of mcrt_shape");
+
 struct QueueArgs {
     int* shadowCount;
     float4 *sO, *sD, *sL;
@@ -184,6 +193,13 @@ void launch_aov(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, 
 // denoiser guides at the camera-ray hits (k_guides): the band's rows of the two W*H planes
 void launch_guides(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
                    float4* normalPlane, float4* albedoDepth, hipStream_t st);
+// the previous-pose table of n shapes, copied out of the scene's shape array (k_pose_snapshot)
+void launch_pose_snapshot(const mcrt_shape* shapes, PrevPose* out, int n, hipStream_t st);
+// k_guides_motion: k_guides' two planes and, from the previous poses (NULL: none), the motion and
+// previous-normal planes
+void launch_guides_motion(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
+                          float4* normalPlane, float4* albedoDepth, const PrevPose* prev, float4* motion,
+                          float4* prevNormal, hipStream_t st);
 // mcrt_denoise.hip: the luminance moments (sum l, sum l*l) of the frames k_accumulate just added
 void launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st);
 // the a-trous filter's level-0 input (moments NULL: variance 1) and one level of step `step`
@@ -206,6 +222,9 @@ struct TemporalParams {
     const float4 *image, *albedoDepth, *normalPlane;
     const float4 *colourOld, *momentsOld, *normalOld;
     float4 *colourNew, *momentsNew, *normalNew;
+    // mcrt_temporal_accumulate_motion: the motion and previous-normal planes (NULL: the static launch)
+    const float4* motion = nullptr;
+    const float4* prevNormal = nullptr;
 };
 void launch_temporal(const TemporalParams& t, bool eager, hipStream_t st);
 void launch_temporal_var(int W, int H, int minHistory, float normalThr, float planeThr, const float4* moments,

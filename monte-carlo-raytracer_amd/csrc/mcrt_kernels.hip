@@ -722,9 +722,21 @@ __global__ __launch_bounds__(256) void k_aov(SceneArgs s, FrameArgs f, const mcr
 //                 scene far from the origin keeps its precision
 //   albedoDepth = (MCRT_AOV_ALBEDO's Kd, |P - cam.pos|)
 // A miss writes (0, 0, 0, 0) and (0, 0, 0, -1).  Band rows only.
-__global__ __launch_bounds__(256) void k_guides(SceneArgs s, FrameArgs f, const mcrt_camera* __restrict__ camp,
-                                                const float4* __restrict__ hits, float4* __restrict__ normalPlane,
-                                                float4* __restrict__ albedoDepth) {
+//
+// MOTION (k_guides_motion, mcrt_render_guides_motion) writes the same two records and, from the
+// shape's previous pose `prev` (mcrt_scene_motion_snapshot; NULL: none yet), two more:
+//   motion     = (P_prev - P, flag).  flag 0: no table, or the table's 32 matrix words and mesh key
+//                equal the shape's -- (0, 0, 0, 0) without evaluating anything.  flag 1: P_prev is
+//                si.p's expression over the table's toWorldTransform (three transformPoint3 of the
+//                same surface-record vertices, the same blend), d = P_prev - si.p per component.
+//                flag -1: the mesh key differs, (0, 0, 0, -1).  A miss is (0, 0, 0, 0).
+//   prevNormal = (n_prev, 0) where flag is 1, zeros otherwise: si.sn's expression over the table's
+//                toWorldInverseTranspose, flipped when n was (the same physical side).
+template <bool MOTION>
+__device__ __forceinline__ void guidesPixel(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* __restrict__ camp,
+                                            const float4* __restrict__ hits, float4* __restrict__ normalPlane,
+                                            float4* __restrict__ albedoDepth, const PrevPose* __restrict__ prev,
+                                            float4* __restrict__ motion, float4* __restrict__ prevNormal) {
     const int lane = threadIdx.x & 63;
     const int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     int x, y;
@@ -735,6 +747,10 @@ __global__ __launch_bounds__(256) void k_guides(SceneArgs s, FrameArgs f, const 
     if (shapeIdx < 0) {
         normalPlane[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         albedoDepth[pix] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
+        if (MOTION) {
+            motion[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            prevNormal[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
         return;
     }
     const mcrt_camera& cam = *camp;
@@ -749,12 +765,75 @@ __global__ __launch_bounds__(256) void k_guides(SceneArgs s, FrameArgs f, const 
     const f3 v = si.p - ld3(cam.pos);
     f3 n = si.sn;
     float off = cl_dot(n, v);
-    if (off > 0.0f) {
+    const bool flipped = off > 0.0f;
+    if (flipped) {
         n = f3{-n.x, -n.y, -n.z};
         off = -off;
     }
     normalPlane[pix] = make_float4(n.x, n.y, n.z, off);
     albedoDepth[pix] = make_float4(kd.x, kd.y, kd.z, cl_length(v));
+    if (MOTION) {
+        float4 mv = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pn = mv;
+        if (prev) {
+            const mcrt_shape shape = tableEntry(s.shapes, shapeIdx);
+            const PrevPose pp = tableEntry(prev, shapeIdx);
+            if (pp.startIdx != shape.startIdx || pp.startVertex != shape.startVertex ||
+                pp.numTriangles != shape.numTriangles) {
+                mv.w = -1.0f;
+            } else {
+                const uint32_t* a = reinterpret_cast<const uint32_t*>(&shape);
+                const uint32_t* b = reinterpret_cast<const uint32_t*>(&pp);
+                uint32_t diff = 0;
+#pragma unroll
+                for (int w = 0; w < 32; ++w) diff |= a[w] ^ b[w];
+                if (diff) {
+                    const float4* R = s.surf + 8 * ((size_t)tableEntry(s.surfBase, shapeIdx) + (uint32_t)primIdx);
+                    const float4 r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3], r4 = R[4], r5 = R[5];
+                    const f2 barycentrics = f2{hit.x, hit.y};
+                    const f3 p0 = transformPoint3(pp.toWorldTransform, mk3(r0.x, r0.y, r0.z));
+                    const f3 p1 = transformPoint3(pp.toWorldTransform, mk3(r0.w, r1.x, r1.y));
+                    const f3 p2 = transformPoint3(pp.toWorldTransform, mk3(r1.z, r1.w, r2.x));
+                    const f3 n0 = transformVector3(pp.toWorldInverseTranspose, mk3(r3.w, r4.x, r4.y));
+                    const f3 n1 = transformVector3(pp.toWorldInverseTranspose, mk3(r4.z, r4.w, r5.x));
+                    const f3 n2 = transformVector3(pp.toWorldInverseTranspose, mk3(r5.y, r5.z, r5.w));
+                    const f3 pPrev = p0 * (1.0f - barycentrics.x - barycentrics.y) + p1 * barycentrics.x + p2 * barycentrics.y;
+                    f3 nPrev = cl_normalize(n0 * (1.0f - barycentrics.x - barycentrics.y) + n1 * barycentrics.x + n2 * barycentrics.y);
+                    if (flipped) nPrev = f3{-nPrev.x, -nPrev.y, -nPrev.z};
+                    mv = make_float4(pPrev.x - si.p.x, pPrev.y - si.p.y, pPrev.z - si.p.z, 1.0f);
+                    pn = make_float4(nPrev.x, nPrev.y, nPrev.z, 0.0f);
+                }
+            }
+        }
+        motion[pix] = mv;
+        prevNormal[pix] = pn;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_guides(SceneArgs s, FrameArgs f, const mcrt_camera* __restrict__ camp,
+                                                const float4* __restrict__ hits, float4* __restrict__ normalPlane,
+                                                float4* __restrict__ albedoDepth) {
+    guidesPixel<false>(s, f, camp, hits, normalPlane, albedoDepth, nullptr, nullptr, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_guides_motion(SceneArgs s, FrameArgs f, const mcrt_camera* __restrict__ camp,
+                                                       const float4* __restrict__ hits,
+                                                       float4* __restrict__ normalPlane,
+                                                       float4* __restrict__ albedoDepth,
+                                                       const PrevPose* __restrict__ prev, float4* __restrict__ motion,
+                                                       float4* __restrict__ prevNormal) {
+    guidesPixel<true>(s, f, camp, hits, normalPlane, albedoDepth, prev, motion, prevNormal);
+}
+
+// The previous-pose table (mcrt_scene_motion_snapshot): the first 35 words of every mcrt_shape --
+// both matrices and the mesh key -- and a zero, one word per thread.
+__global__ __launch_bounds__(256) void k_pose_snapshot(const mcrt_shape* __restrict__ shapes, PrevPose* __restrict__ out,
+                                                       int n) {
+    constexpr int WORDS = (int)(sizeof(PrevPose) / 4), SHAPE_WORDS = (int)(sizeof(mcrt_shape) / 4);
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * WORDS) return;
+    const int k = i / WORDS, w = i - k * WORDS;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(shapes);
+    reinterpret_cast<uint32_t*>(out)[i] = w < WORDS - 1 ? src[(size_t)k * SHAPE_WORDS + w] : 0u;
 }
 
 // ---------------------------------------------------------------------------
@@ -1289,6 +1368,17 @@ void launch_guides(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* ca
     const int blocks = (f.numTiles * 64 + 255) / 256;
     hipLaunchKernelGGL(k_guides, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, s, f, cam, hits, normalPlane,
                        albedoDepth);
+}
+void launch_guides_motion(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
+                          float4* normalPlane, float4* albedoDepth, const PrevPose* prev, float4* motion,
+                          float4* prevNormal, hipStream_t st) {
+    const int blocks = (f.numTiles * 64 + 255) / 256;
+    hipLaunchKernelGGL(k_guides_motion, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, s, f, cam, hits, normalPlane,
+                       albedoDepth, prev, motion, prevNormal);
+}
+void launch_pose_snapshot(const mcrt_shape* shapes, PrevPose* out, int n, hipStream_t st) {
+    const int words = n * (int)(sizeof(PrevPose) / 4);
+    hipLaunchKernelGGL(k_pose_snapshot, dim3((words + 255) / 256), dim3(256), 0, st, shapes, out, n);
 }
 void launch_accumulate(const FrameArgs& f, int frame, const mcrt_filter* filters, int filterStride, const float4* radiance,
                        float4* wsum, float* wts, float4* image, hipStream_t st) {

@@ -106,6 +106,11 @@ SIGNATURES = {
     "mcrt_denoise_guided_temporal": (_c.c_int, [_vp, _c.POINTER(T.GuidedDenoiseParams), _c.c_int32]),
     "mcrt_framebuffer_set_temporal_history": (_c.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "mcrt_framebuffer_read_temporal": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    "mcrt_scene_motion_snapshot": (_c.c_int, [_vp]),
+    "mcrt_render_guides_motion": (_c.c_int, [_vp, _vp, _vp, _vp]),
+    "mcrt_framebuffer_set_motion": (_c.c_int, [_vp, _vp, _vp]),
+    "mcrt_framebuffer_read_motion": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
+    "mcrt_temporal_accumulate_motion": (_c.c_int, [_vp, _vp, _c.POINTER(T.TemporalParams)]),
     "mcrt_framebuffer_read_bdpt": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     "mcrt_make_pinhole_camera": (_c.c_int, [_vp, _vp, _vp, _c.c_float, _c.c_float, _c.c_float, _c.c_uint32,
                                             _c.c_uint32, _vp, _vp]),
@@ -356,6 +361,11 @@ class DeviceScene:
         w2l = None if world_to_local is None else np.ascontiguousarray(world_to_local, np.float32)
         _check(lib().mcrt_accel_update_transforms(self.h, _p(self._shapes), len(self._shapes), _p(w2l)), self.ctx.h)
 
+    def motion_snapshot(self):
+        """mcrt_scene_motion_snapshot: the shapes' current poses become their previous poses (call it
+        before this frame's update_transforms / update_shapes)."""
+        _check(lib().mcrt_scene_motion_snapshot(self.h), self.ctx.h)
+
     def update_info(self):
         """The last update_transforms: path 0 none yet, 1 top level built on the device, 2 on the
         host, 3 full rebuild; ms its wall time (mcrt_accel_update_info)."""
@@ -452,6 +462,24 @@ class FrameBuffer:
         cam = np.ascontiguousarray(cam)
         _check(lib().mcrt_render_guides(dscene.h, self.h, _p(cam), _c.byref(p)), self.ctx.h)
 
+    def render_guides_motion(self, dscene, cam, texture_lod=False, band_rows=8, num_bands=1, band_index=0):
+        """mcrt_render_guides_motion: render_guides plus the motion and previous-normal planes of the
+        scene's last motion_snapshot."""
+        p = T.FrameParams(0, 1, T.SAMPLER_RANDOM, 0, 3, band_rows, num_bands, band_index, T.INTEGRATOR_PT,
+                          1 if texture_lod else 0)
+        cam = np.ascontiguousarray(cam)
+        _check(lib().mcrt_render_guides_motion(dscene.h, self.h, _p(cam), _c.byref(p)), self.ctx.h)
+
+    def set_motion(self, motion_ptr, prev_normal_ptr):
+        """mcrt_framebuffer_set_motion: both (H, W, 4) float32 planes from device memory."""
+        _check(lib().mcrt_framebuffer_set_motion(self.h, motion_ptr, prev_normal_ptr), self.ctx.h)
+
+    def read_motion(self, which):
+        """mcrt_framebuffer_read_motion: 0 motion (P_prev - P, flag), 1 previous normal, (H, W, 4)."""
+        out = np.zeros((self.H, self.W, 4), np.float32)
+        _check(lib().mcrt_framebuffer_read_motion(self.h, which, _p(out), out.nbytes, None), self.ctx.h)
+        return out
+
     def set_guides(self, normal_plane_ptr, albedo_depth_ptr):
         """mcrt_framebuffer_set_guides: both (H, W, 4) float32 planes from device memory."""
         _check(lib().mcrt_framebuffer_set_guides(self.h, normal_plane_ptr, albedo_depth_ptr), self.ctx.h)
@@ -489,6 +517,14 @@ class FrameBuffer:
                              1 if demodulate_albedo else 0)
         cam = np.ascontiguousarray(cam)
         _check(lib().mcrt_temporal_accumulate(self.h, _p(cam), _c.byref(p)), self.ctx.h)
+
+    def temporal_accumulate_motion(self, cam, alpha=0.2, alpha_moments=0.2, max_history=32, min_history=4,
+                                   normal_threshold=0.1, plane_threshold=0.01, demodulate_albedo=True):
+        """mcrt_temporal_accumulate_motion: temporal_accumulate reprojecting through the motion planes."""
+        p = T.TemporalParams(alpha, alpha_moments, max_history, min_history, normal_threshold, plane_threshold,
+                             1 if demodulate_albedo else 0)
+        cam = np.ascontiguousarray(cam)
+        _check(lib().mcrt_temporal_accumulate_motion(self.h, _p(cam), _c.byref(p)), self.ctx.h)
 
     def temporal_reset(self):
         """mcrt_temporal_reset: the next temporal_accumulate starts without history."""
