@@ -21,8 +21,7 @@
 #include <tuple>
 #include <vector>
 
-#include "mcrt_devbuf.h"
-#include "mcrt_internal.h"
+#include "mcrt_host.h"
 
 namespace {
 
@@ -35,20 +34,13 @@ int dev_alloc(void** p, size_t bytes) { return (int)hipMalloc(p, bytes); }
 void dev_free(void* p) { (void)hipFree(p); }
 int dev_sync(void* stream) { return (int)hipStreamSynchronize((hipStream_t)stream); }
 }  // namespace mcrt
-using mcrt::DevBuf;
+// the helpers mcrt_host.h declares for other host files; defined below among the file's own
+using mcrt::fail, mcrt::env_int, mcrt::fb_sync, mcrt::ctx_wait_slots, mcrt::frame_args, mcrt::ensure_spill,
+    mcrt::packet_ctx, mcrt::scene_args;
 namespace {
 
 #define MCRT_MAX_BOUNCES 32
-#define MCRT_ATROUS_MAX_LEVELS 8
 
-enum KernelId {
-    K_PRIMARY, K_SHADE0, K_SHADEN, K_SHADOW, K_EXTEND, K_ACCUM, K_TRACE_CLOSEST, K_TRACE_ANY,
-    K_BDPT_START, K_BDPT_VERTEX, K_BDPT_CONNECT, K_BDPT_VIS, K_BDPT_GATHER, K_SHADOW_EXTEND,
-    K_GUIDES, K_MOMENTS, K_ATROUS_PREP,
-    K_ATROUS,   // one entry per level: K_ATROUS + i is the launch of step 2^i
-    K_TEMPORAL = K_ATROUS + MCRT_ATROUS_MAX_LEVELS, K_TEMPORAL_VAR, K_GUIDES_MOTION, K_TEMPORAL_MOTION,
-    K_COUNT
-};
 const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN",       "k_shadow",   "k_extend",
                                      "k_accumulate", "k_trace_closest", "k_trace_any",  "k_bdpt_start",
                                      "k_bdpt_vertex", "k_bdpt_connect", "k_bdpt_vis",   "k_bdpt_gather",
@@ -59,226 +51,8 @@ const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN"
 
 }  // namespace
 
-struct mcrt_ctx_s {
-    int device = 0;
-    hipStream_t own = nullptr;
-    hipStream_t stream = nullptr;
-    int numCUs = 256;
-    bool profiling = false;
-    bool countHints = false;   // mcrt_ctx_set_profiling(2): occluder-hint counters (one atomic per wave)
-    int* dFlags = nullptr;          // device flags: [0] traversal-stack overflow (mcrt_traverse.h), set by any launch
-    std::string error;
-    struct Pending {
-        int kernel;
-        hipEvent_t a, b;
-        const int* countDev;   // device counter holding the item count (or nullptr)
-        const int* countDev2;  // a second counter added to it (fused launches), or nullptr
-        int64_t items;
-    };
-    std::vector<Pending> pending;
-    double totalMs[K_COUNT] = {};
-    int64_t launches[K_COUNT] = {};
-    int64_t items[K_COUNT] = {};
-};
-
-struct mcrt_scene_s {
-    mcrt_ctx ctx = nullptr;
-    // host copies needed for the BVH build and dynamic updates
-    std::vector<mcrt_shape> shapes;
-    std::vector<uint32_t> indices;
-    std::vector<mcrt_float4> positions;
-    // device arrays
-    DevBuf<mcrt_shape> dShapes;
-    DevBuf<uint32_t> dIndices;
-    DevBuf<float4> dPositions;
-    DevBuf<float2> dUvs;
-    DevBuf<float4> dNormals;
-    DevBuf<mcrt_texture_desc> dTextures;
-    DevBuf<uint8_t> dTexData;
-    DevBuf<uint32_t> dSobol;
-    DevBuf<mcrt_light> dLights;
-    DevBuf<mcrt_material> dMaterials;
-    DevBuf<float4> dSurf;           // surface records (SceneArgs::surf), 128 B per distinct mesh triangle
-    DevBuf<uint32_t> dSurfBase;     // per shape: its first surface record
-    DevBuf<uint32_t> dSurfMeshes;   // build scratch: startIdx | startVertex | base per distinct mesh
-    uint32_t numLights = 0, numMaterials = 0, numTextures = 0;
-    bool hasSobol = false;
-    // BVH
-    DevBuf<float4> dNodes;     // 4 float4 per record
-    bool packets = false;      // coherent launches as wave packets (finish_accel)
-    uint64_t numNodes = 0;
-    uint32_t numTris = 0;
-    double buildMs = 0.0;
-    int builder = 0;   // which builder made the flat structure: 0 host, 1 device LBVH, 2 device SAH
-    int bvhDepth = 0;
-    bool twoLevel = false;          // instanced scene: two-level records (mcrt_bvh2l.cpp)
-    int numMeshes = 0, numInstances = 0;
-    // traversal scratch
-    DevBuf<uint32_t> dSpill;   // spillCap words per ray (ensure_spill)
-    int spillCap = 0;
-    DevBuf<int> dScratch;      // work counters for API queries
-    float bbLo[3] = {0, 0, 0}, bbHi[3] = {0, 0, 0};   // world bounds (root record of the BVH)
-    // occluder hints of the shadow rays after bounce 0, by origin cell (TraceCtx::hint, flat trees):
-    // allocated on the first shadow launch that uses hints (ensure_hint_cell), 2^hintBits words
-    DevBuf<uint32_t> dHintCell;
-    int hintBits = 0;
-    // compact records of the flat tree (TraceCtx::qnodes; mcrt::build_qnodes), empty when not built
-    DevBuf<float4> dQNodes;
-    uint32_t qRoot = 0;
-    bool hintAllocFailed = false;   // no memory for the table: hints stay off for this scene
-    // transform updates (mcrt_accel_update_transforms): the options of the last mcrt_accel_build
-    // (without its world_to_local pointer), the two-level build's refit state, the device top-level
-    // builder's arrays (made by the first update that takes the device path)
-    mcrt_accel_opts lastOpts = {};
-    bool haveOpts = false;
-    mcrt::Bvh2lTop top2l;
-    uint64_t topNodes = 0;
-    mcrt::TopBuildDev* topDev = nullptr;
-    int updatePath = 0;
-    double updateMs = 0.0;
-    // previous poses (mcrt_scene_motion_snapshot): one record per shape, allocated by the first
-    // snapshot; only k_guides_motion receives it
-    DevBuf<PrevPose> dPrevPose;
-    ~mcrt_scene_s() { mcrt::top_build_destroy(topDev); }   // the buffers free themselves
-};
-
-// One frame in flight (PT): the per-frame buffers of mcrt_render_frame, its own stream and
-// spill columns.  Frame i renders in slot i mod S on that slot's stream while mcrt_accumulate
-// runs on the context stream in frame order (it waits for the slot's `done` event and records
-// `free` after reading the slot's radiance), so S frames overlap on the GPU -- each frame's
-// arithmetic and the per-pixel accumulation order are unchanged, so the image is the same bit
-// for bit.  Small per-rank frames (tile split over many GPUs) do not fill 256 CUs alone.
-#define SLOT_FILTER_OFFSET (512 + 176 * MCRT_MAX_BATCH_FRAMES)   // the batch's filters (mcrt_accumulate_frames)
-#define SLOT_COUNTER_BYTES (SLOT_FILTER_OFFSET + (int)sizeof(mcrt_filter) * MCRT_MAX_BATCH_FRAMES + 1536)
-struct FrameSlot {
-    DevBuf<float4> radiance;
-    DevBuf<float4> hitsP;        // primary hits (mcrt_kernels.hip hitSlot)
-    DevBuf<float4> hitsE;        // extension hits by queue slot
-    DevBuf<float4> eO[2], eD[2], eT[2];
-    DevBuf<float4> sO, sD, sL;
-    // [0..31] shadow counts, [32..63] ext counts, [64..127] work counters, then the batch's cameras
-    // (176 B each) from byte 512 and its filters from SLOT_FILTER_OFFSET
-    DevBuf<int> counters;
-    mcrt_camera* cameras() const { return reinterpret_cast<mcrt_camera*>(counters.get() + 128); }
-    mcrt_filter* filters() const {
-        return reinterpret_cast<mcrt_filter*>(reinterpret_cast<char*>(counters.get()) + SLOT_FILTER_OFFSET);
-    }
-    DevBuf<uint32_t> spill;      // per-ray traversal spill columns of this slot's launches
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;   // recorded after the slot's last render
-    hipEvent_t free = nullptr;   // recorded on the context stream after the slot's buffers were last read
-    int lastMaxDepth = 0;
-    int64_t lastPixels = 0;
-    int lastBatch = 1;           // frames of the slot's last render (mcrt_render_frames)
-    int frames = 1;              // radiance / primary-hit planes of W*H allocated (batch capacity)
-    size_t queueCap = 0;         // entries of each ray-queue buffer
-    // longest-first tile order (FrameArgs::tileOrder): the camera-wave cost of each tile recorded by
-    // this slot's last call, and the order made from it; stream-ordered on the slot's stream
-    DevBuf<uint32_t> tileCost, tileOrder;   // the same size
-    int costTiles = 0;           // tiles of the recorded costs (0: none)
-    // suspended extension walks (TraceCtx::walkCap): MCRT_SUSPEND_F4 float4 per queue entry, and
-    // one count per bounce (zeroed per call)
-    DevBuf<float4> suspend;
-    DevBuf<int> suspendCnt;
-};
-static_assert(SLOT_COUNTER_BYTES % sizeof(int) == 0, "the counter block is allocated as ints");
-
-// Per-frame BDPT arrays (RTBDPTPass::createBuffers, RTBDPTPass.cpp:442-479), one set per frame
-// slot so BDPT frames overlap like PT frames; layouts in mcrt_bdpt.hip.
-struct BdptSet {
-    DevBuf<float4> camV, lightV, slots, splat;
-    DevBuf<int> camCount, lightCount;
-    DevBuf<int> bdptCounters;    // 64 ints: the queue counters (BDPT_CNT_*)
-    DevBuf<float4> bqO[2], bqD[2], bqT[2], bHits;
-    DevBuf<float4> cO, cD, cL;   // connection queue
-    DevBuf<uint32_t> spill;      // traversal spill columns of this set's launches
-    // the light-start queue's sort (mcrt::bdpt_light_sort): keys, sorted keys, slots, permutation
-    DevBuf<uint32_t> lkey, lkey2, lslot, lperm;
-    // the traced bounce queues' sort (same routine; k_bdpt_vertex's keys over 2 N slots)
-    DevBuf<uint32_t> ekey, ekey2, eslot, eperm;
-    DevBuf<uint8_t> sortTmp;
-    int frames = 0;              // batch frames the per-frame arrays hold (plane stride N x frames)
-    // plane stride and band (rows, count, index) whose depth-0 frame-invariant planes k_bdpt_start
-    // wrote for every path of the band
-    size_t constStride = 0;
-    int constBand[3] = {0, 0, -1};
-    // band split, sparse splat exchange: the splats landing in other ranks' rows (BdptArgs::splatList)
-    // and 128 ints of grouping scratch (per-owner counts, cursors)
-    DevBuf<float4> splatList;
-    DevBuf<int> splatAux;
-    // suspended closest-hit walks (TraceCtx::walkCap): MCRT_SUSPEND_F4 float4 per queue entry, one
-    // count per traced queue (zeroed per call)
-    DevBuf<float4> suspend;
-    DevBuf<int> suspendCnt;
-};
-
-struct mcrt_framebuffer_s {
-    mcrt_ctx ctx = nullptr;
-    uint32_t W = 0, H = 0;
-    size_t N = 0;
-    std::vector<FrameSlot> slot;   // slot[0] always allocated; others on first use
-    int cur = 0, next = 0;         // slot of the last rendered frame / of the next one
-    int framesInFlight = 0;        // 0 = auto (mcrt_framebuffer_set_frames_in_flight)
-    DevBuf<float4> wsum;
-    DevBuf<float> wts;
-    DevBuf<float4> image;
-    DevBuf<float4> denoised;     // RTDenoisePass output (persistent: the reference keeps its image)
-    DevBuf<float4> display;      // post-processed image (mcrt_postprocess)
-    DevBuf<uint32_t> hintPix;    // occluder hint of each pixel's bounce-0 shadow ray (TraceCtx::hint)
-    FrameArgs bands{};      // band layout of the last mcrt_render_frame (used by mcrt_accumulate)
-    bool haveBands = false;
-    // BDPT state (allocated on the first BDPT frame for a max depth; mcrt_bdpt.hip has the layout):
-    // per-frame arrays per frame slot; the sampled-light-vertex planes carry state from frame to
-    // frame (BDPT.cl:585), so they are shared and the connect launches stay in frame order
-    int bdptDepth = 0;
-    BdptSet bset[MCRT_MAX_FRAMES_IN_FLIGHT];
-    hipEvent_t bdptConnect = nullptr;   // recorded after the last enqueued frame's connect launch
-    // diagnostics (MCRT_WAVE_CLOCK=1): per-workgroup (start, end) clocks of the last PT call's camera,
-    // shadow+extension and last shadow launches (mcrt_framebuffer_wave_clock)
-    DevBuf<uint32_t> waveClk[3];   // 2 words per workgroup
-    DevBuf<float4> sampLight;      // the sampled-light-vertex planes (D x N)
-    int lastIntegrator = MCRT_INTEGRATOR_PT;
-    int bdptBatch = 1;           // frames of the last BDPT call (plane stride N x bdptBatch)
-    bool bdptOneSet = false;     // a second BDPT set did not fit in HBM: BDPT frames use slot 0 only
-    bool bdptPendingGather = false;   // band-split BDPT frame waiting for the ranks' summed splats
-    int splatExchange = MCRT_SPLAT_EXCHANGE_DENSE;   // mcrt_framebuffer_set_splat_exchange
-    int bdptSet = 0;             // the BDPT set of the last BDPT call
-    // Guided denoiser (mcrt_denoise_guided), every plane allocated on first use: the guides of the
-    // camera-ray hits, the luminance moments k_moments keeps next to the image, and two scratch
-    // colour / variance planes the levels ping-pong between (fb->denoised stays mcrt_postprocess's)
-    DevBuf<float4> guideNormal;      // (n, n . (P - cam.pos))
-    DevBuf<float4> guideAlbedo;      // (Kd, |P - cam.pos|), -1 on a miss
-    bool haveGuides = false;
-    DevBuf<float2> moments;          // (sum l, sum l*l)
-    bool momentsOn = false;
-    int momentFrames = 0;            // frames in the moments (host side; restarts at frame_index 0)
-    DevBuf<float4> atrousC[2];
-    DevBuf<float> atrousV[2];
-    int filteredVar = -1;            // which of atrousV holds the last level's variance, -1 before a denoise
-    // Temporal history (mcrt_temporal_accumulate), allocated on first use.  Colour, moments and the
-    // previous normal-plane exist twice: k_temporal reads set tCur and writes the other, then tCur
-    // flips, so set tCur is always what the next accumulate (and mcrt_framebuffer_read_temporal) reads.
-    DevBuf<float4> tColour[2];       // integrated colour in filter space, alpha of the current image
-    DevBuf<float4> tMoments[2];      // (mu1, mu2, N, z)
-    DevBuf<float4> tNormal[2];       // the guide record the pixel had when written
-    DevBuf<float> tVar;              // the variance handed to the filter
-    int tCur = 0;
-    bool tHaveHistory = false;       // false: the next accumulate starts without history
-    bool tAccumulated = false;       // an accumulate has run: the planes feed mcrt_denoise_guided_temporal
-    bool tFedBack = false;           // the colour history already holds a filtered level of this accumulate
-    int tDemod = 0;                  // demodulate_albedo of the last accumulate
-    mcrt_camera tPrevCam = {};       // camera of the history planes
-    // Per-object motion (mcrt_render_guides_motion), allocated on first use; they belong to one set
-    // of guides, so whatever replaces the guides alone clears haveMotion
-    DevBuf<float4> motion;           // (P_prev - P, flag)
-    DevBuf<float4> motionNormal;     // (n_prev, 0) where flag is 1
-    bool haveMotion = false;
-};
-// The slot of the last rendered frame and the set of the last BDPT call: what the read-back entry
-// points show.  After a failed regrow their buffers are empty, never stale.
-static FrameSlot& cur_slot(mcrt_framebuffer fb) { return fb->slot[fb->cur]; }
+// The set of the last BDPT call, as cur_slot (mcrt_host.h) is the slot of the last rendered frame
 static BdptSet& cur_bset(mcrt_framebuffer fb) { return fb->bset[fb->bdptSet]; }
-static const char* const kNoSlotBuffers = "the frame slot has no buffers (its last allocation failed)";
 
 // BDPT queue counters (64 ints per frame set): [d] the subpath-ray queue of depth d (d <= 33;
 // at depth 0 the light rays only), then these
@@ -288,18 +62,11 @@ static int bdpt_max_connections(int D) { const int t = D + 2; return t * (t + 1)
 // ---------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------
-static mcrt_status fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg) {
+mcrt_status mcrt::fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg) {
     g_lastError = msg;
     if (ctx) ctx->error = msg;
     return code;
 }
-#define HIPCHK(ctx, expr)                                                                                   \
-    do {                                                                                                    \
-        hipError_t e_ = (hipError_t)(expr);   /* DevBuf reports the runtime's codes as int */               \
-        if (e_ != hipSuccess)                                                                               \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? MCRT_ERROR_OUT_OF_MEMORY : MCRT_ERROR_DEVICE,      \
-                        std::string(#expr) + ": " + hipGetErrorString(e_));                                 \
-    } while (0)
 
 // `count` host elements into the (empty) buffer; S is T or the C ABI's name for it
 template <class T, class S>
@@ -310,32 +77,6 @@ static hipError_t upload(DevBuf<T>& dst, const S* src, size_t count, hipStream_t
     if (e != hipSuccess) return e;
     return hipMemcpyAsync(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice, st);
 }
-
-struct Timed {
-    mcrt_ctx c;
-    int k;
-    hipEvent_t a = nullptr, b = nullptr;
-    const int* countDev;
-    int64_t items;
-    hipStream_t st;
-    const int* countDev2;
-    Timed(mcrt_ctx ctx, int kernel, const int* countDev_, int64_t items_, hipStream_t stream = nullptr,
-          const int* countDev2_ = nullptr)
-        : c(ctx), k(kernel), countDev(countDev_), items(items_), st(stream ? stream : ctx->stream),
-          countDev2(countDev2_) {
-        if (c->profiling) {
-            hipEventCreate(&a);
-            hipEventCreate(&b);
-            hipEventRecord(a, st);
-        }
-    }
-    ~Timed() {
-        if (c->profiling) {
-            hipEventRecord(b, st);
-            c->pending.push_back({k, a, b, countDev, countDev2, items});
-        }
-    }
-};
 
 static void drain_pending(mcrt_ctx ctx) {
     if (ctx->pending.empty()) return;
@@ -372,8 +113,7 @@ static inline void xformPoint(const mcrt_mat4& m, const mcrt_float4& p, float* o
     }
 }
 
-// Per-ray spill columns for `rays` rays (rounded up to whole waves); grown on demand.
-static bool ensure_spill(mcrt_scene s, size_t rays) {
+bool mcrt::ensure_spill(mcrt_scene s, size_t rays) {
     rays = (rays + 63) / 64 * 64;
     return s->dSpill.grow(rays * (size_t)s->spillCap, s->ctx->stream) == 0;
 }
@@ -392,8 +132,7 @@ static TraceCtx trace_ctx(mcrt_scene s) {
     return c;
 }
 
-// An integer environment variable clamped to lo .. hi, or `def` when it is not set.
-static int env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX) {
+int mcrt::env_int(const char* name, int def, int lo, int hi) {
     const char* e = std::getenv(name);
     return e ? (int)std::min<long>(hi, std::max<long>(lo, std::strtol(e, nullptr, 10))) : def;
 }
@@ -479,14 +218,13 @@ static int walk_max_bounce() { return env_int("MCRT_WALK_MAXB", 0); }
 static int bdpt_light_in_vertex() { return env_int("MCRT_BDPT_LIGHT_IN_VERTEX", 1) != 0; }
 static int walk_lanes() { return env_int("MCRT_WALK_LANES", 8, 0, 64); }
 
-// the coherent launches' view (camera rays, bounce-0 shadow rays): wave packets when the tree allows
-static TraceCtx packet_ctx(mcrt_scene s) {
+TraceCtx mcrt::packet_ctx(mcrt_scene s) {
     TraceCtx c = trace_ctx(s);
     c.packet = s->packets ? 1 : 0;
     return c;
 }
 
-static SceneArgs scene_args(mcrt_scene s) {
+SceneArgs mcrt::scene_args(mcrt_scene s) {
     SceneArgs a;
     a.shapes = s->dShapes.get();
     a.indices = s->dIndices.get();
@@ -505,6 +243,55 @@ static SceneArgs scene_args(mcrt_scene s) {
     return a;
 }
 
+hipError_t mcrt::fb_sync(mcrt_framebuffer fb) {
+    hipError_t e = hipSuccess;
+    for (auto& k : fb->slot)
+        if (k.stream && e == hipSuccess) e = hipStreamSynchronize(k.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(fb->ctx->stream);
+    return e;
+}
+
+void mcrt::ctx_wait_slots(mcrt_framebuffer fb) {
+    for (auto& k : fb->slot)
+        if (k.stream) hipStreamWaitEvent(fb->ctx->stream, k.done, 0);
+}
+
+bool mcrt::frame_args(mcrt_framebuffer fb, const mcrt_frame_params* p, FrameArgs& f, std::string& err) {
+    f.W = fb->W;
+    f.H = fb->H;
+    f.frame = p->frame_index;
+    f.maxDepth = p->max_depth;
+    f.sampler = p->sampler;
+    f.russianRoulette = p->russian_roulette;
+    f.rrStartDepth = p->rr_start_depth;
+    f.textureLod = p->texture_lod ? 1 : 0;
+    // batched frames: workgroups of the camera / first-bounce launches walk (tile, frame) with the
+    // frames of a tile adjacent, so one XCD traces a tile's batch of jittered frames back to back,
+    // and a camera / first-shading wave holds 64 consecutive (pixel, frame) paths of one tile
+    // (profiles/r02/ab/README.txt items 11, 14, 15); the order changes no result
+    f.tileMajor = 1;
+    f.primaryPack = 1;
+    f.shadePack = 1;
+    f.batch = 1;
+    f.tileOrder = nullptr;   // set per call by render_frames (longest-first)
+    f.tileCost = nullptr;
+    f.numBands = p->num_bands <= 0 ? 1 : p->num_bands;
+    f.bandIndex = p->band_index;
+    f.bandRows = f.numBands == 1 ? 8 : p->band_rows;
+    if (f.bandRows <= 0 || (f.bandRows & 7) != 0) { err = "band_rows must be a positive multiple of 8"; return false; }
+    if (f.bandIndex < 0 || f.bandIndex >= f.numBands) { err = "band_index out of range"; return false; }
+    f.tilesX = (int)((fb->W + 7) / 8);
+    // row-blocks (8 rows) of this band set inside the image
+    const int blocksTotal = (int)((fb->H + 7) / 8);
+    const int bpb = f.bandRows / 8;
+    int myBlocks = 0;
+    for (int gb = 0; gb < blocksTotal; ++gb)
+        if ((gb / bpb) % f.numBands == f.bandIndex) ++myBlocks;
+    // tile ids are dealt in the kernel as tb -> gb; count the band-local blocks that map inside
+    f.numTiles = myBlocks * f.tilesX;
+    return true;
+}
+
 // Replaces a scene array once the context stream has finished with the old one.
 template <class T>
 static mcrt_status replace_array(mcrt_scene s, DevBuf<T>& dst, const T* src, size_t count) {
@@ -518,23 +305,6 @@ static mcrt_status replace_array(mcrt_scene s, DevBuf<T>& dst, const T* src, siz
     }
     return MCRT_OK;
 }
-
-// Allocates the plane (one T per pixel, zero-filled on the context stream) when it does not exist yet.
-template <class T>
-static hipError_t ensure_plane(mcrt_framebuffer fb, DevBuf<T>& p) {
-    if (p) return hipSuccess;
-    hipError_t e = (hipError_t)p.alloc(fb->N);
-    if (e == hipSuccess) e = hipMemsetAsync(p.get(), 0, sizeof(T) * fb->N, fb->ctx->stream);
-    return e;
-}
-
-// Level 0's input of an a-trous chain: colour in filter space and its variance plane.
-struct AtrousIn {
-    const float4* colour = nullptr;
-    const float* var = nullptr;
-    int useVar = 0;
-};
-using AtrousBegin = mcrt_status (*)(mcrt_framebuffer, const mcrt_guided_denoise_params*, AtrousIn&);
 
 // ---------------------------------------------------------------------------
 // context
@@ -1446,22 +1216,6 @@ static hipError_t slot_alloc(FrameSlot& k, size_t N, size_t T, int frames = 1, s
     return e;
 }
 
-// Host reads and context-stream work that touch the slots: all slot streams first.
-static hipError_t fb_sync(mcrt_framebuffer fb) {
-    hipError_t e = hipSuccess;
-    for (auto& k : fb->slot)
-        if (k.stream && e == hipSuccess) e = hipStreamSynchronize(k.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(fb->ctx->stream);
-    return e;
-}
-
-// Makes the context stream wait for every slot's last render (work on the context stream
-// that reads or rewrites slot buffers: BDPT, AOVs, device copies).
-static void ctx_wait_slots(mcrt_framebuffer fb) {
-    for (auto& k : fb->slot)
-        if (k.stream) hipStreamWaitEvent(fb->ctx->stream, k.done, 0);
-}
-
 // NQ = the pixels of the whole 8x8 tiles covering the image (>= N): the start queues hold one slot
 // per lane of the tile walk.  Ray queues and hits hold 2 x NQ (the depth-1 camera and light halves).
 static hipError_t bset_alloc(BdptSet& b, size_t N, size_t NQ, int D, int frames, hipStream_t st) {
@@ -1586,42 +1340,6 @@ MCRT_API mcrt_status mcrt_framebuffer_destroy(mcrt_framebuffer fb) {
     fb_free(fb);
     delete fb;
     return MCRT_OK;
-}
-
-static bool frame_args(mcrt_framebuffer fb, const mcrt_frame_params* p, FrameArgs& f, std::string& err) {
-    f.W = fb->W;
-    f.H = fb->H;
-    f.frame = p->frame_index;
-    f.maxDepth = p->max_depth;
-    f.sampler = p->sampler;
-    f.russianRoulette = p->russian_roulette;
-    f.rrStartDepth = p->rr_start_depth;
-    f.textureLod = p->texture_lod ? 1 : 0;
-    // batched frames: workgroups of the camera / first-bounce launches walk (tile, frame) with the
-    // frames of a tile adjacent, so one XCD traces a tile's batch of jittered frames back to back,
-    // and a camera / first-shading wave holds 64 consecutive (pixel, frame) paths of one tile
-    // (profiles/r02/ab/README.txt items 11, 14, 15); the order changes no result
-    f.tileMajor = 1;
-    f.primaryPack = 1;
-    f.shadePack = 1;
-    f.batch = 1;
-    f.tileOrder = nullptr;   // set per call by render_frames (longest-first)
-    f.tileCost = nullptr;
-    f.numBands = p->num_bands <= 0 ? 1 : p->num_bands;
-    f.bandIndex = p->band_index;
-    f.bandRows = f.numBands == 1 ? 8 : p->band_rows;
-    if (f.bandRows <= 0 || (f.bandRows & 7) != 0) { err = "band_rows must be a positive multiple of 8"; return false; }
-    if (f.bandIndex < 0 || f.bandIndex >= f.numBands) { err = "band_index out of range"; return false; }
-    f.tilesX = (int)((fb->W + 7) / 8);
-    // row-blocks (8 rows) of this band set inside the image
-    const int blocksTotal = (int)((fb->H + 7) / 8);
-    const int bpb = f.bandRows / 8;
-    int myBlocks = 0;
-    for (int gb = 0; gb < blocksTotal; ++gb)
-        if ((gb / bpb) % f.numBands == f.bandIndex) ++myBlocks;
-    // tile ids are dealt in the kernel as tb -> gb; count the band-local blocks that map inside
-    f.numTiles = myBlocks * f.tilesX;
-    return true;
 }
 
 // Frames in flight for a render: the frame buffer's setting; auto = 2.  Each launch of a frame ends in a divergent tail of long rays that the next
@@ -2138,10 +1856,10 @@ static mcrt_status accumulate(mcrt_framebuffer fb, const mcrt_filter* filters, i
         mcrt::launch_accumulate(f, frame_index, dFilt, nfilters == 1 ? 0 : 1, slot.radiance.get(), fb->wsum.get(), fb->wts.get(),
                                 fb->image.get(), ctx->stream);
     }
-    if (fb->momentsOn) {   // the same frames' luminance moments, before the slot is released
+    if (fb->dn.momentsOn) {   // the same frames' luminance moments, before the slot is released
         Timed t(ctx, K_MOMENTS, nullptr, (int64_t)f.numTiles * 64 * batch);
-        mcrt::launch_moments(f, frame_index, slot.radiance.get(), fb->moments.get(), ctx->stream);
-        fb->momentFrames = frame_index == 0 ? batch : fb->momentFrames + batch;
+        mcrt::launch_moments(f, frame_index, slot.radiance.get(), fb->dn.moments.get(), ctx->stream);
+        fb->dn.momentFrames = frame_index == 0 ? batch : fb->dn.momentFrames + batch;
     }
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(slot.free, ctx->stream));   // the slot may take its next frame
@@ -2188,403 +1906,6 @@ MCRT_API mcrt_status mcrt_postprocess(mcrt_framebuffer fb, const mcrt_postproces
         HIPCHK(ctx, hipMemcpyAsync(fb->display.get(), src, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Guided denoiser: guides, moments, a-trous filter (mcrt_denoise.hip)
-// ---------------------------------------------------------------------------
-static hipError_t ensure_guides(mcrt_framebuffer fb) {
-    hipError_t e = ensure_plane(fb, fb->guideNormal);
-    if (e == hipSuccess) e = ensure_plane(fb, fb->guideAlbedo);
-    return e;
-}
-
-static hipError_t ensure_motion(mcrt_framebuffer fb) {
-    hipError_t e = ensure_plane(fb, fb->motion);
-    if (e == hipSuccess) e = ensure_plane(fb, fb->motionNormal);
-    return e;
-}
-
-// mcrt_render_guides and, with `motion`, mcrt_render_guides_motion: the same host path, one launch
-// of k_guides or of k_guides_motion
-static mcrt_status render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_frame_params* p,
-                                 bool motion) {
-    if (!s || !fb || !cam || !p) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = s->ctx;
-    if (fb->ctx != ctx) return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame buffer belongs to another context");
-    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
-    if (cam->width != fb->W || cam->height != fb->H)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
-    FrameArgs f;
-    std::string err;
-    if (!frame_args(fb, p, f, err)) return fail(ctx, MCRT_ERROR_INVALID_ARG, err);
-    hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, ensure_guides(fb));
-    if (motion) HIPCHK(ctx, ensure_motion(fb));
-    FrameSlot& slot = cur_slot(fb);   // as mcrt_render_aov: its camera and primary-hit buffers are reused
-    if (!slot.counters) return fail(ctx, MCRT_ERROR_NOT_READY, kNoSlotBuffers);
-    ctx_wait_slots(fb);
-    mcrt_camera* dCam = slot.cameras();
-    HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera), hipMemcpyHostToDevice, st));
-    if (!ensure_spill(s, std::max((size_t)f.numTiles * 64, 2 * fb->N + 64)))
-        return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "traversal spill buffer");
-    const TraceCtx tcs = packet_ctx(s);
-    mcrt::launch_primary(tcs, f, dCam, slot.hitsP.get(), st);
-    if (motion) {
-        Timed t(ctx, K_GUIDES_MOTION, nullptr, (int64_t)f.numTiles * 64);
-        mcrt::launch_guides_motion(scene_args(s), f, dCam, slot.hitsP.get(), fb->guideNormal.get(), fb->guideAlbedo.get(),
-                                   s->dPrevPose.get(), fb->motion.get(), fb->motionNormal.get(), st);
-    } else {
-        Timed t(ctx, K_GUIDES, nullptr, (int64_t)f.numTiles * 64);
-        mcrt::launch_guides(scene_args(s), f, dCam, slot.hitsP.get(), fb->guideNormal.get(), fb->guideAlbedo.get(), st);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    // the slot's next render (its own stream) may overwrite those buffers only after this pass
-    HIPCHK(ctx, hipEventRecord(slot.free, st));
-    fb->haveGuides = true;
-    fb->haveMotion = motion;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
-                                        const mcrt_frame_params* p) {
-    return render_guides(s, fb, cam, p, false);
-}
-
-MCRT_API mcrt_status mcrt_render_guides_motion(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
-                                               const mcrt_frame_params* p) {
-    return render_guides(s, fb, cam, p, true);
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_set_guides(mcrt_framebuffer fb, const void* d_normal_plane,
-                                                 const void* d_albedo_depth) {
-    if (!fb || !d_normal_plane || !d_albedo_depth) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, ensure_guides(fb));
-    HIPCHK(ctx, hipMemcpyAsync(fb->guideNormal.get(), d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->guideAlbedo.get(), d_albedo_depth, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    fb->haveGuides = true;
-    fb->haveMotion = false;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_set_motion(mcrt_framebuffer fb, const void* d_motion, const void* d_prev_normal) {
-    if (!fb || !d_motion || !d_prev_normal) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, ensure_motion(fb));
-    HIPCHK(ctx, hipMemcpyAsync(fb->motion.get(), d_motion, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->motionNormal.get(), d_prev_normal, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    fb->haveMotion = true;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_read_motion(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
-                                                  uint64_t* needed) {
-    if (!fb || which < 0 || which > 1) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    const void* src = which == 0 ? fb->motion.get() : fb->motionNormal.get();
-    const uint64_t need = 16 * (uint64_t)fb->N;
-    if (needed) *needed = need;
-    if (!host_dst) return MCRT_OK;
-    if (!src) return fail(ctx, MCRT_ERROR_NOT_READY, "no motion planes yet");
-    if (bytes < need) return fail(ctx, MCRT_ERROR_INVALID_ARG, "destination too small");
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, fb_sync(fb));
-    HIPCHK(ctx, hipMemcpy(host_dst, src, need, hipMemcpyDeviceToHost));
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_set_moments_enabled(mcrt_framebuffer fb, int on) {
-    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    if (on && !fb->moments) {
-        HIPCHK(ctx, ensure_plane(fb, fb->moments));
-        fb->momentFrames = 0;
-    }
-    fb->momentsOn = on != 0;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_set_moments(mcrt_framebuffer fb, const void* d_m1m2, int32_t frames) {
-    if (!fb || !d_m1m2 || frames < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, ensure_plane(fb, fb->moments));
-    HIPCHK(ctx, hipMemcpyAsync(fb->moments.get(), d_m1m2, 8 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    fb->momentFrames = frames;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_read_guides(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
-                                                  uint64_t* needed) {
-    if (!fb || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    const void* src = which == 0 ? (const void*)fb->guideNormal.get() : which == 1 ? (const void*)fb->guideAlbedo.get()
-                      : which == 2 ? (const void*)fb->moments.get()
-                      : fb->filteredVar < 0 ? nullptr : (const void*)fb->atrousV[fb->filteredVar].get();
-    const uint64_t need = (which < 2 ? 16 : which == 2 ? 8 : 4) * (uint64_t)fb->N;
-    if (needed) *needed = need;
-    if (!host_dst) return MCRT_OK;
-    if (!src) return fail(ctx, MCRT_ERROR_NOT_READY, "no such guide data yet");
-    if (bytes < need) return fail(ctx, MCRT_ERROR_INVALID_ARG, "destination too small");
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, fb_sync(fb));
-    HIPCHK(ctx, hipMemcpy(host_dst, src, need, hipMemcpyDeviceToHost));
-    return MCRT_OK;
-}
-
-// Largest step whose level runs the tile-staged kernel (36 KB of LDS at step 4); larger steps read
-// their taps from memory.  MCRT_ATROUS_LDS_MAX_STEP overrides it (0: never stage) for measurements
-// and the test that both kernels agree bit for bit.
-static int atrous_lds_max_step() {
-    return env_int("MCRT_ATROUS_LDS_MAX_STEP", 4, 0, 8);   // step 8: 48 x 48 x 36 B = 81 KB does not fit 64 KB
-}
-
-// the two scratch colour / variance planes the levels ping-pong between
-static hipError_t ensure_atrous(mcrt_framebuffer fb) {
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = ensure_plane(fb, fb->atrousC[i]);
-        if (e == hipSuccess) e = ensure_plane(fb, fb->atrousV[i]);
-    }
-    return e;
-}
-
-// The a-trous chain of mcrt_denoise_guided and mcrt_denoise_guided_temporal: the checks they share
-// (in their order), then `begin` -- the caller's own checks and whatever makes level 0's input --
-// then the levels, ping-ponging between the scratch planes, and the tone-map tail.  The output of
-// level `feedback_level` (-1: none) becomes the colour history.
-static mcrt_status atrous_chain(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, int feedback_level,
-                                AtrousBegin begin) {
-    mcrt_ctx ctx = fb->ctx;
-    const int demod = p->demodulate_albedo ? 1 : 0;
-    if (p->levels < 1 || p->levels > MCRT_ATROUS_MAX_LEVELS)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "levels must be 1 .. 8");
-    if (!(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f) || !(p->sigma_luminance > 0.0f))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "sigmas must be positive");
-    if (feedback_level < -1 || feedback_level > p->levels - 2)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "feedback_level must be -1 .. levels - 2");
-    if (!fb->haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
-    if (fb->bdptPendingGather)
-        return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
-    hipSetDevice(ctx->device);
-    AtrousIn in;
-    const mcrt_status bs = begin(fb, p, in);
-    if (bs != MCRT_OK) return bs;
-    HIPCHK(ctx, ensure_atrous(fb));
-    hipStream_t st = ctx->stream;
-    const int W = (int)fb->W, H = (int)fb->H;
-    const int ldsMax = atrous_lds_max_step();
-    const float4* cIn = in.colour;
-    const float* vIn = in.var;
-    int dst = cIn == fb->atrousC[0].get() ? 1 : 0;   // never the plane level 0 reads
-    for (int i = 0; i < p->levels; ++i) {
-        const int step = 1 << i;
-        const bool last = i + 1 == p->levels;
-        // the last level writes the display image, or a scratch plane when k_tonemap follows
-        float4* cOut = last && !p->use_tonemapping ? fb->display.get() : fb->atrousC[dst].get();
-        const float sigmaLevel = in.useVar ? p->sigma_luminance : p->sigma_luminance * std::ldexp(1.0f, -i);
-        const bool lds = step <= ldsMax && mcrt::atrous_lds_bytes(step) <= 64 * 1024;
-        {
-            Timed t(ctx, K_ATROUS + i, nullptr, (int64_t)fb->N);
-            mcrt::launch_atrous(W, H, step, lds, p->sigma_normal, p->sigma_depth, sigmaLevel, in.useVar,
-                                last && demod ? 1 : 0, cIn, fb->guideNormal.get(), fb->guideAlbedo.get(), vIn, cOut,
-                                fb->atrousV[dst].get(), st);
-        }
-        if (i == feedback_level) {
-            // this level's output (never the last level's: a scratch plane) becomes the colour history
-            // by exchanging the two planes; the old history plane, which only level 0 read, is scratch
-            // from now on, and no later level writes the new history plane
-            std::swap(fb->tColour[fb->tCur], fb->atrousC[dst]);
-            fb->tFedBack = true;
-        }
-        cIn = cOut;
-        vIn = fb->atrousV[dst].get();
-        dst ^= 1;
-    }
-    fb->filteredVar = dst ^ 1;
-    if (p->use_tonemapping) mcrt::launch_tonemap(W * H, p->min_luminance, cIn, fb->display.get(), st);
-    HIPCHK(ctx, hipGetLastError());
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p) {
-    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    return atrous_chain(fb, p, -1, [](mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, AtrousIn& in) {
-        mcrt_ctx ctx = fb->ctx;
-        HIPCHK(ctx, ensure_atrous(fb));   // k_atrous_prep writes level 0's input to the first scratch planes
-        const bool useVar = p->use_variance && fb->moments && fb->momentFrames >= 2;
-        Timed t(ctx, K_ATROUS_PREP, nullptr, (int64_t)fb->N);
-        mcrt::launch_atrous_prep((int)fb->N, fb->image.get(), fb->guideAlbedo.get(), useVar ? fb->moments.get() : nullptr,
-                                 fb->momentFrames, p->demodulate_albedo ? 1 : 0, fb->atrousC[0].get(),
-                                 fb->atrousV[0].get(), ctx->stream);
-        in = {fb->atrousC[0].get(), fb->atrousV[0].get(), useVar ? 1 : 0};
-        return MCRT_OK;
-    });
-}
-
-// ---------------------------------------------------------------------------
-// Temporal reprojection and history (k_temporal, k_temporal_var in mcrt_denoise.hip)
-// ---------------------------------------------------------------------------
-static hipError_t ensure_temporal(mcrt_framebuffer fb) {
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-        e = ensure_plane(fb, fb->tColour[i]);
-        if (e == hipSuccess) e = ensure_plane(fb, fb->tMoments[i]);
-        if (e == hipSuccess) e = ensure_plane(fb, fb->tNormal[i]);
-    }
-    if (e == hipSuccess) e = ensure_plane(fb, fb->tVar);
-    return e;
-}
-
-// MCRT_TEMPORAL_LOADS selects k_temporal's load form for measurements and the test that both agree
-// bit for bit: "eager" issues all twelve tap records together, anything else (the default, the
-// form measured faster) fetches the eight validity records first and a tap's colour only when valid.
-static bool temporal_eager_loads() {
-    const char* e = std::getenv("MCRT_TEMPORAL_LOADS");
-    return e && std::strcmp(e, "eager") == 0;
-}
-
-// mcrt_temporal_accumulate and, with `motion`, mcrt_temporal_accumulate_motion
-static mcrt_status temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_temporal_params* p,
-                                       bool motion) {
-    if (!fb || !cam || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f) || !(p->alpha_moments >= 0.0f && p->alpha_moments <= 1.0f))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "alpha and alpha_moments must be in 0 .. 1");
-    if (p->max_history < 1 || p->min_history < 1)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "max_history and min_history must be >= 1");
-    if (!(p->normal_threshold > 0.0f) || !(p->plane_threshold > 0.0f))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "thresholds must be positive");
-    if (cam->width != fb->W || cam->height != fb->H)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
-    if (!fb->haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
-    if (motion && !fb->haveMotion)
-        return fail(ctx, MCRT_ERROR_NOT_READY,
-                    "no motion planes for these guides (mcrt_render_guides_motion / mcrt_framebuffer_set_motion)");
-    if (fb->bdptPendingGather)
-        return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
-    hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    HIPCHK(ctx, ensure_temporal(fb));
-    const int W = (int)fb->W, H = (int)fb->H;
-    const int old = fb->tCur, now = old ^ 1;
-    mcrt::TemporalParams t;
-    t.W = W;
-    t.H = H;
-    t.demod = p->demodulate_albedo ? 1 : 0;
-    t.haveHistory = fb->tHaveHistory ? 1 : 0;
-    t.alpha = p->alpha;
-    t.alphaMoments = p->alpha_moments;
-    t.maxHistory = (float)p->max_history;
-    t.normalThr = p->normal_threshold;
-    t.planeThr = p->plane_threshold;
-    t.cam = cam;
-    t.prev = fb->tHaveHistory ? &fb->tPrevCam : cam;
-    t.image = fb->image.get();
-    t.albedoDepth = fb->guideAlbedo.get();
-    t.normalPlane = fb->guideNormal.get();
-    t.colourOld = fb->tColour[old].get();
-    t.momentsOld = fb->tMoments[old].get();
-    t.normalOld = fb->tNormal[old].get();
-    t.colourNew = fb->tColour[now].get();
-    t.momentsNew = fb->tMoments[now].get();
-    t.normalNew = fb->tNormal[now].get();
-    if (motion) {
-        t.motion = fb->motion.get();
-        t.prevNormal = fb->motionNormal.get();
-    }
-    {
-        Timed tm(ctx, motion ? K_TEMPORAL_MOTION : K_TEMPORAL, nullptr, (int64_t)fb->N);
-        mcrt::launch_temporal(t, temporal_eager_loads(), st);
-    }
-    {
-        Timed tm(ctx, K_TEMPORAL_VAR, nullptr, (int64_t)fb->N);
-        mcrt::launch_temporal_var(W, H, p->min_history, p->normal_threshold, p->plane_threshold, fb->tMoments[now].get(),
-                                  fb->tNormal[now].get(), fb->tVar.get(), st);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    fb->tCur = now;
-    fb->tHaveHistory = true;
-    fb->tAccumulated = true;
-    fb->tFedBack = false;
-    fb->tDemod = t.demod;
-    fb->tPrevCam = *cam;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* cam,
-                                              const mcrt_temporal_params* p) {
-    return temporal_accumulate(fb, cam, p, false);
-}
-
-MCRT_API mcrt_status mcrt_temporal_accumulate_motion(mcrt_framebuffer fb, const mcrt_camera* cam,
-                                                     const mcrt_temporal_params* p) {
-    return temporal_accumulate(fb, cam, p, true);
-}
-
-MCRT_API mcrt_status mcrt_temporal_reset(mcrt_framebuffer fb) {
-    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
-    fb->tHaveHistory = false;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_set_temporal_history(mcrt_framebuffer fb, const void* d_colour,
-                                                           const void* d_moments, const void* d_normal_plane,
-                                                           const mcrt_camera* prev_camera) {
-    if (!fb || !d_colour || !d_moments || !d_normal_plane || !prev_camera)
-        return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    if (prev_camera->width != fb->W || prev_camera->height != fb->H)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, ensure_temporal(fb));
-    const int cur = fb->tCur;
-    HIPCHK(ctx, hipMemcpyAsync(fb->tColour[cur].get(), d_colour, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->tMoments[cur].get(), d_moments, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->tNormal[cur].get(), d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    fb->tPrevCam = *prev_camera;
-    fb->tHaveHistory = true;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_read_temporal(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
-                                                    uint64_t* needed) {
-    if (!fb || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    const int cur = fb->tCur;
-    const void* src = which == 0 ? (const void*)fb->tColour[cur].get() : which == 1 ? (const void*)fb->tMoments[cur].get()
-                      : which == 2 ? (const void*)fb->tVar.get() : (const void*)fb->tNormal[cur].get();
-    const uint64_t need = (which == 2 ? 4 : 16) * (uint64_t)fb->N;
-    if (needed) *needed = need;
-    if (!host_dst) return MCRT_OK;
-    if (!src) return fail(ctx, MCRT_ERROR_NOT_READY, "no temporal history yet");
-    if (bytes < need) return fail(ctx, MCRT_ERROR_INVALID_ARG, "destination too small");
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, fb_sync(fb));
-    HIPCHK(ctx, hipMemcpy(host_dst, src, need, hipMemcpyDeviceToHost));
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_denoise_guided_temporal(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p,
-                                                  int32_t feedback_level) {
-    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    return atrous_chain(fb, p, feedback_level, [](mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, AtrousIn& in) {
-        mcrt_ctx ctx = fb->ctx;
-        const int demod = p->demodulate_albedo ? 1 : 0;
-        if (!fb->tAccumulated) return fail(ctx, MCRT_ERROR_NOT_READY, "no mcrt_temporal_accumulate yet");
-        if (fb->tFedBack)
-            return fail(ctx, MCRT_ERROR_NOT_READY, "the colour history already holds a filtered level of this accumulate");
-        if (demod != fb->tDemod)
-            return fail(ctx, MCRT_ERROR_INVALID_ARG, "demodulate_albedo differs from the last mcrt_temporal_accumulate");
-        // level 0 reads the colour history (already in filter space) and the variance plane
-        in = {fb->tColour[fb->tCur].get(), fb->tVar.get(), p->use_variance ? 1 : 0};
-        return MCRT_OK;
-    });
 }
 
 MCRT_API mcrt_status mcrt_framebuffer_read(mcrt_framebuffer fb, int which, float* host_rgba) {

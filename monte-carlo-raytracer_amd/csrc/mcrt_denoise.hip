@@ -1,5 +1,6 @@
 // mcrt_denoise.hip -- guide-driven edge-avoiding a-trous wavelet denoiser (mcrt_denoise_guided) and
-// the per-pixel luminance moments that steer it (k_moments).
+// the per-pixel luminance moments that steer it (k_moments), its temporal history, and below the
+// kernels the host entry points of all of it (each fills its kernel's argument struct and launches).
 //
 // Dammertz et al. 2010 ("Edge-Avoiding A-Trous Wavelet Transform for fast Global Illumination
 // Filtering") weights on a normal, a plane-offset and a luminance edge-stopping term, the luminance
@@ -9,8 +10,13 @@
 //
 // Planes (W*H each): colour float4, normal-plane float4 (n.xyz, n.(P - cam.pos)), albedo-depth
 // float4 (Kd.rgb, |P - cam.pos|, -1 on a miss), variance float, moments float2 (sum l, sum l*l).
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
+#include "mcrt_host.h"
 #include "mcrt_shading.h"
 
 namespace {
@@ -489,110 +495,459 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal_var(int 
 
 }  // namespace
 
-namespace mcrt {
-
-void launch_temporal(const TemporalParams& t, bool eager, hipStream_t st) {
-    TemporalMotionArgs a;
-    a.W = t.W;
-    a.H = t.H;
-    a.demod = t.demod;
-    a.haveHistory = t.haveHistory;
-    a.alpha = t.alpha;
-    a.alphaMoments = t.alphaMoments;
-    a.maxHistory = t.maxHistory;
-    a.normalThr = t.normalThr;
-    a.planeThr = t.planeThr;
-    const mcrt_camera& c = *t.cam;
-    const mcrt_camera& o = *t.prev;
-    const float cp[3] = {c.pos.x, c.pos.y, c.pos.z}, op[3] = {o.pos.x, o.pos.y, o.pos.z};
-    const mcrt_float3* corner[4] = {&c.r00, &c.r10, &c.r11, &c.r01};
-    float* dst[4] = {a.r00, a.r10, a.r11, a.r01};
-    for (int i = 0; i < 4; ++i) {
-        dst[i][0] = corner[i]->x;
-        dst[i][1] = corner[i]->y;
-        dst[i][2] = corner[i]->z;
-    }
-    for (int i = 0; i < 3; ++i) a.dpos[i] = cp[i] - op[i];
-    const mcrt_float4* row[3] = {&o.worldToClip.m0, &o.worldToClip.m1, &o.worldToClip.m3};
-    float* rdst[3] = {a.M0, a.M1, a.M3};
-    for (int i = 0; i < 3; ++i) {
-        rdst[i][0] = row[i]->x;
-        rdst[i][1] = row[i]->y;
-        rdst[i][2] = row[i]->z;
-    }
-    a.image = t.image;
-    a.albedoDepth = t.albedoDepth;
-    a.normalPlane = t.normalPlane;
-    a.colourOld = t.colourOld;
-    a.momentsOld = t.momentsOld;
-    a.normalOld = t.normalOld;
-    a.colourNew = t.colourNew;
-    a.momentsNew = t.momentsNew;
-    a.normalNew = t.normalNew;
-    const dim3 grid((t.W + ATROUS_TILE - 1) / ATROUS_TILE, (t.H + ATROUS_TILE - 1) / ATROUS_TILE);
-    const dim3 block(ATROUS_TILE * ATROUS_TILE);
-    if (t.motion) {
-        a.motion = t.motion;
-        a.prevNormal = t.prevNormal;
-        if (eager)
-            hipLaunchKernelGGL(k_temporal_motion<true>, grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL(k_temporal_motion<false>, grid, block, 0, st, a);
-        return;
-    }
-    const TemporalArgs& base = a;
-    if (eager)
-        hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, st, base);
-    else
-        hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, st, base);
-}
-
-void launch_temporal_var(int W, int H, int minHistory, float normalThr, float planeThr, const float4* moments,
-                         const float4* normalPlane, float* var, hipStream_t st) {
-    const dim3 grid((W + ATROUS_TILE - 1) / ATROUS_TILE, (H + ATROUS_TILE - 1) / ATROUS_TILE);
-    hipLaunchKernelGGL(k_temporal_var, grid, dim3(ATROUS_TILE * ATROUS_TILE), 0, st, W, H, (float)minHistory, normalThr,
-                       planeThr, moments, normalPlane, var);
-}
-
-void launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st) {
+// called by mcrt_accumulate (mcrt_capi.cpp) while fb->dn.momentsOn
+void mcrt::launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st) {
     const int blocks = (f.numTiles * 64 + 255) / 256;
     hipLaunchKernelGGL(k_moments, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, f, frame, radiance, moments);
 }
 
-void launch_atrous_prep(int n, const float4* image, const float4* albedoDepth, const float2* moments, int frames,
-                        int demod, float4* cOut, float* vOut, hipStream_t st) {
-    hipLaunchKernelGGL(k_atrous_prep, dim3((n + 255) / 256), dim3(256), 0, st, n, image, albedoDepth, moments,
-                       (float)frames, demod, cOut, vOut);
+// ---------------------------------------------------------------------------
+// Host entry points.  Their state is fb->dn (DenoiseState, mcrt_host.h); from the rest of the
+// runtime they take the accumulated image, the display plane, the current slot's camera and
+// primary-hit buffers and the context stream.
+// ---------------------------------------------------------------------------
+using mcrt::fail, mcrt::env_int, mcrt::ensure_plane, mcrt::fb_sync;
+
+static const dim3 kTileBlock(ATROUS_TILE * ATROUS_TILE);
+static dim3 tile_grid(int W, int H) { return dim3((W + ATROUS_TILE - 1) / ATROUS_TILE, (H + ATROUS_TILE - 1) / ATROUS_TILE); }
+
+static hipError_t ensure_guides(mcrt_framebuffer fb) {
+    hipError_t e = ensure_plane(fb, fb->dn.guideNormal);
+    if (e == hipSuccess) e = ensure_plane(fb, fb->dn.guideAlbedo);
+    return e;
 }
 
-size_t atrous_lds_bytes(int step) {
+static hipError_t ensure_motion(mcrt_framebuffer fb) {
+    hipError_t e = ensure_plane(fb, fb->dn.motion);
+    if (e == hipSuccess) e = ensure_plane(fb, fb->dn.motionNormal);
+    return e;
+}
+
+// mcrt_render_guides and, with `motion`, mcrt_render_guides_motion: the same host path, one launch
+// of k_guides or of k_guides_motion
+static mcrt_status render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_frame_params* p,
+                                 bool motion) {
+    if (!s || !fb || !cam || !p) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = s->ctx;
+    if (fb->ctx != ctx) return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame buffer belongs to another context");
+    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
+    if (cam->width != fb->W || cam->height != fb->H)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
+    FrameArgs f;
+    std::string err;
+    if (!mcrt::frame_args(fb, p, f, err)) return fail(ctx, MCRT_ERROR_INVALID_ARG, err);
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    DenoiseState& d = fb->dn;
+    HIPCHK(ctx, ensure_guides(fb));
+    if (motion) HIPCHK(ctx, ensure_motion(fb));
+    FrameSlot& slot = cur_slot(fb);   // as mcrt_render_aov: its camera and primary-hit buffers are reused
+    if (!slot.counters) return fail(ctx, MCRT_ERROR_NOT_READY, kNoSlotBuffers);
+    mcrt::ctx_wait_slots(fb);
+    mcrt_camera* dCam = slot.cameras();
+    HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera), hipMemcpyHostToDevice, st));
+    if (!mcrt::ensure_spill(s, std::max((size_t)f.numTiles * 64, 2 * fb->N + 64)))
+        return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "traversal spill buffer");
+    const TraceCtx tcs = mcrt::packet_ctx(s);
+    mcrt::launch_primary(tcs, f, dCam, slot.hitsP.get(), st);
+    if (motion) {
+        Timed t(ctx, K_GUIDES_MOTION, nullptr, (int64_t)f.numTiles * 64);
+        mcrt::launch_guides_motion(mcrt::scene_args(s), f, dCam, slot.hitsP.get(), d.guideNormal.get(), d.guideAlbedo.get(),
+                                   s->dPrevPose.get(), d.motion.get(), d.motionNormal.get(), st);
+    } else {
+        Timed t(ctx, K_GUIDES, nullptr, (int64_t)f.numTiles * 64);
+        mcrt::launch_guides(mcrt::scene_args(s), f, dCam, slot.hitsP.get(), d.guideNormal.get(), d.guideAlbedo.get(), st);
+    }
+    HIPCHK(ctx, hipGetLastError());
+    // the slot's next render (its own stream) may overwrite those buffers only after this pass
+    HIPCHK(ctx, hipEventRecord(slot.free, st));
+    d.haveGuides = true;
+    d.haveMotion = motion;
+    return MCRT_OK;
+}
+
+// The tail the plane read-backs share once `src` (NULL: not allocated yet) and its size are chosen:
+// *needed, then a NULL destination (a size query), not ready, too small, in that order; the copy
+// waits for every stream of the frame buffer
+static mcrt_status read_plane(mcrt_framebuffer fb, const void* src, uint64_t need, void* host_dst, uint64_t bytes,
+                              uint64_t* needed, const char* notReady) {
+    mcrt_ctx ctx = fb->ctx;
+    if (needed) *needed = need;
+    if (!host_dst) return MCRT_OK;
+    if (!src) return fail(ctx, MCRT_ERROR_NOT_READY, notReady);
+    if (bytes < need) return fail(ctx, MCRT_ERROR_INVALID_ARG, "destination too small");
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, fb_sync(fb));
+    HIPCHK(ctx, hipMemcpy(host_dst, src, need, hipMemcpyDeviceToHost));
+    return MCRT_OK;
+}
+
+// ---- temporal reprojection and history ----
+static hipError_t ensure_temporal(mcrt_framebuffer fb) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = ensure_plane(fb, fb->dn.tColour[i]);
+        if (e == hipSuccess) e = ensure_plane(fb, fb->dn.tMoments[i]);
+        if (e == hipSuccess) e = ensure_plane(fb, fb->dn.tNormal[i]);
+    }
+    if (e == hipSuccess) e = ensure_plane(fb, fb->dn.tVar);
+    return e;
+}
+
+// MCRT_TEMPORAL_LOADS selects k_temporal's load form for measurements and the test that both agree
+// bit for bit: "eager" issues all twelve tap records together, anything else (the default, the
+// form measured faster) fetches the eight validity records first and a tap's colour only when valid.
+static bool temporal_eager_loads() {
+    const char* e = std::getenv("MCRT_TEMPORAL_LOADS");
+    return e && std::strcmp(e, "eager") == 0;
+}
+
+static void copy3(float* dst, float x, float y, float z) { dst[0] = x; dst[1] = y; dst[2] = z; }
+
+// mcrt_temporal_accumulate and, with `motion`, mcrt_temporal_accumulate_motion: k_temporal (or
+// k_temporal_motion) reprojects the old history planes of the history's camera into the pixels of
+// `cam` and writes the new ones, k_temporal_var then derives the variance plane from them
+static mcrt_status temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_temporal_params* p,
+                                       bool motion) {
+    if (!fb || !cam || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    DenoiseState& d = fb->dn;
+    if (!(p->alpha >= 0.0f && p->alpha <= 1.0f) || !(p->alpha_moments >= 0.0f && p->alpha_moments <= 1.0f))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "alpha and alpha_moments must be in 0 .. 1");
+    if (p->max_history < 1 || p->min_history < 1)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "max_history and min_history must be >= 1");
+    if (!(p->normal_threshold > 0.0f) || !(p->plane_threshold > 0.0f))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "thresholds must be positive");
+    if (cam->width != fb->W || cam->height != fb->H)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
+    if (!d.haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
+    if (motion && !d.haveMotion)
+        return fail(ctx, MCRT_ERROR_NOT_READY,
+                    "no motion planes for these guides (mcrt_render_guides_motion / mcrt_framebuffer_set_motion)");
+    if (fb->bdptPendingGather)
+        return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
+    hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    HIPCHK(ctx, ensure_temporal(fb));
+    const int old = d.tCur, now = old ^ 1;
+    const mcrt_camera& c = *cam;
+    const mcrt_camera& o = d.tHaveHistory ? d.tPrevCam : *cam;
+    TemporalMotionArgs a;
+    a.W = (int)fb->W;
+    a.H = (int)fb->H;
+    a.demod = p->demodulate_albedo ? 1 : 0;
+    a.haveHistory = d.tHaveHistory ? 1 : 0;
+    a.alpha = p->alpha;
+    a.alphaMoments = p->alpha_moments;
+    a.maxHistory = (float)p->max_history;
+    a.normalThr = p->normal_threshold;
+    a.planeThr = p->plane_threshold;
+    copy3(a.r00, c.r00.x, c.r00.y, c.r00.z);
+    copy3(a.r10, c.r10.x, c.r10.y, c.r10.z);
+    copy3(a.r11, c.r11.x, c.r11.y, c.r11.z);
+    copy3(a.r01, c.r01.x, c.r01.y, c.r01.z);
+    copy3(a.dpos, c.pos.x - o.pos.x, c.pos.y - o.pos.y, c.pos.z - o.pos.z);
+    copy3(a.M0, o.worldToClip.m0.x, o.worldToClip.m0.y, o.worldToClip.m0.z);
+    copy3(a.M1, o.worldToClip.m1.x, o.worldToClip.m1.y, o.worldToClip.m1.z);
+    copy3(a.M3, o.worldToClip.m3.x, o.worldToClip.m3.y, o.worldToClip.m3.z);
+    a.image = fb->image.get();
+    a.albedoDepth = d.guideAlbedo.get();
+    a.normalPlane = d.guideNormal.get();
+    a.colourOld = d.tColour[old].get();
+    a.momentsOld = d.tMoments[old].get();
+    a.normalOld = d.tNormal[old].get();
+    a.colourNew = d.tColour[now].get();
+    a.momentsNew = d.tMoments[now].get();
+    a.normalNew = d.tNormal[now].get();
+    a.motion = d.motion.get();
+    a.prevNormal = d.motionNormal.get();
+    const dim3 grid = tile_grid(a.W, a.H);
+    const bool eager = temporal_eager_loads();
+    {
+        Timed tm(ctx, motion ? K_TEMPORAL_MOTION : K_TEMPORAL, nullptr, (int64_t)fb->N);
+        const TemporalArgs& base = a;
+        if (motion && eager)
+            hipLaunchKernelGGL(k_temporal_motion<true>, grid, kTileBlock, 0, st, a);
+        else if (motion)
+            hipLaunchKernelGGL(k_temporal_motion<false>, grid, kTileBlock, 0, st, a);
+        else if (eager)
+            hipLaunchKernelGGL(k_temporal<true>, grid, kTileBlock, 0, st, base);
+        else
+            hipLaunchKernelGGL(k_temporal<false>, grid, kTileBlock, 0, st, base);
+    }
+    {
+        Timed tm(ctx, K_TEMPORAL_VAR, nullptr, (int64_t)fb->N);
+        hipLaunchKernelGGL(k_temporal_var, grid, kTileBlock, 0, st, a.W, a.H, (float)p->min_history, p->normal_threshold,
+                           p->plane_threshold, a.momentsNew, a.normalNew, d.tVar.get());
+    }
+    HIPCHK(ctx, hipGetLastError());
+    d.tCur = now;
+    d.tHaveHistory = true;
+    d.tAccumulated = true;
+    d.tFedBack = false;
+    d.tDemod = a.demod;
+    d.tPrevCam = *cam;
+    return MCRT_OK;
+}
+
+// Largest step whose level runs the tile-staged kernel (36 KB of LDS at step 4); larger steps read
+// their taps from memory.  MCRT_ATROUS_LDS_MAX_STEP overrides it (0: never stage) for measurements
+// and the test that both kernels agree bit for bit.
+static int atrous_lds_max_step() {
+    return env_int("MCRT_ATROUS_LDS_MAX_STEP", 4, 0, 8);   // step 8: 48 x 48 x 36 B = 81 KB does not fit 64 KB
+}
+static size_t atrous_lds_bytes(int step) {
     const size_t tw = ATROUS_TILE + 4 * (size_t)step;
     return tw * tw * 36;
 }
 
-void launch_atrous(int W, int H, int step, bool lds, float sigmaNormal, float sigmaDepth, float sigmaLevel, int useVar,
-                   int remodulate, const float4* cIn, const float4* normalPlane, const float4* albedoDepth,
-                   const float* vIn, float4* cOut, float* vOut, hipStream_t st) {
-    AtrousArgs a;
-    a.W = W;
-    a.H = H;
-    a.step = step;
-    a.isn2 = 1.0f / (sigmaNormal * sigmaNormal);
-    a.sigmaD = sigmaDepth;
-    a.sl2 = sigmaLevel * sigmaLevel;
-    a.useVar = useVar;
-    a.remodulate = remodulate;
-    a.cIn = cIn;
-    a.normalPlane = normalPlane;
-    a.albedoDepth = albedoDepth;
-    a.vIn = vIn;
-    a.cOut = cOut;
-    a.vOut = vOut;
-    const dim3 grid((W + ATROUS_TILE - 1) / ATROUS_TILE, (H + ATROUS_TILE - 1) / ATROUS_TILE);
-    if (lds)
-        hipLaunchKernelGGL(k_atrous<true>, grid, dim3(ATROUS_TILE * ATROUS_TILE), atrous_lds_bytes(step), st, a);
-    else
-        hipLaunchKernelGGL(k_atrous<false>, grid, dim3(ATROUS_TILE * ATROUS_TILE), 0, st, a);
+// the two scratch colour / variance planes the levels ping-pong between
+static hipError_t ensure_atrous(mcrt_framebuffer fb) {
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 2 && e == hipSuccess; ++i) {
+        e = ensure_plane(fb, fb->dn.atrousC[i]);
+        if (e == hipSuccess) e = ensure_plane(fb, fb->dn.atrousV[i]);
+    }
+    return e;
 }
 
-}  // namespace mcrt
+// Level 0's input of an a-trous chain: colour in filter space and its variance plane.
+struct AtrousIn {
+    const float4* colour = nullptr;
+    const float* var = nullptr;
+    int useVar = 0;
+};
+using AtrousBegin = mcrt_status (*)(mcrt_framebuffer, const mcrt_guided_denoise_params*, AtrousIn&);
+
+// The a-trous chain of mcrt_denoise_guided and mcrt_denoise_guided_temporal: the checks they share
+// (in their order), then `begin` -- the caller's own checks and whatever makes level 0's input --
+// then the levels, ping-ponging between the scratch planes, and the tone-map tail.  The output of
+// level `feedback_level` (-1: none) becomes the colour history.
+static mcrt_status atrous_chain(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, int feedback_level,
+                                AtrousBegin begin) {
+    mcrt_ctx ctx = fb->ctx;
+    DenoiseState& d = fb->dn;
+    const int demod = p->demodulate_albedo ? 1 : 0;
+    if (p->levels < 1 || p->levels > MCRT_ATROUS_MAX_LEVELS)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "levels must be 1 .. 8");
+    if (!(p->sigma_normal > 0.0f) || !(p->sigma_depth > 0.0f) || !(p->sigma_luminance > 0.0f))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "sigmas must be positive");
+    if (feedback_level < -1 || feedback_level > p->levels - 2)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "feedback_level must be -1 .. levels - 2");
+    if (!d.haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
+    if (fb->bdptPendingGather)
+        return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
+    hipSetDevice(ctx->device);
+    AtrousIn in;
+    const mcrt_status bs = begin(fb, p, in);
+    if (bs != MCRT_OK) return bs;
+    HIPCHK(ctx, ensure_atrous(fb));
+    hipStream_t st = ctx->stream;
+    const int ldsMax = atrous_lds_max_step();
+    AtrousArgs a;
+    a.W = (int)fb->W;
+    a.H = (int)fb->H;
+    a.isn2 = 1.0f / (p->sigma_normal * p->sigma_normal);
+    a.sigmaD = p->sigma_depth;
+    a.useVar = in.useVar;
+    a.cIn = in.colour;
+    a.normalPlane = d.guideNormal.get();
+    a.albedoDepth = d.guideAlbedo.get();
+    a.vIn = in.var;
+    int dst = a.cIn == d.atrousC[0].get() ? 1 : 0;   // never the plane level 0 reads
+    for (int i = 0; i < p->levels; ++i) {
+        const bool last = i + 1 == p->levels;
+        a.step = 1 << i;
+        const float sigmaLevel = in.useVar ? p->sigma_luminance : p->sigma_luminance * std::ldexp(1.0f, -i);
+        a.sl2 = sigmaLevel * sigmaLevel;
+        a.remodulate = last && demod ? 1 : 0;
+        // the last level writes the display image, or a scratch plane when k_tonemap follows
+        a.cOut = last && !p->use_tonemapping ? fb->display.get() : d.atrousC[dst].get();
+        a.vOut = d.atrousV[dst].get();
+        {
+            Timed t(ctx, K_ATROUS + i, nullptr, (int64_t)fb->N);
+            if (a.step <= ldsMax && atrous_lds_bytes(a.step) <= 64 * 1024)
+                hipLaunchKernelGGL(k_atrous<true>, tile_grid(a.W, a.H), kTileBlock, atrous_lds_bytes(a.step), st, a);
+            else
+                hipLaunchKernelGGL(k_atrous<false>, tile_grid(a.W, a.H), kTileBlock, 0, st, a);
+        }
+        if (i == feedback_level) {
+            // this level's output (never the last level's: a scratch plane) becomes the colour history
+            // by exchanging the two planes; the old history plane, which only level 0 read, is scratch
+            // from now on, and no later level writes the new history plane
+            std::swap(d.tColour[d.tCur], d.atrousC[dst]);
+            d.tFedBack = true;
+        }
+        a.cIn = a.cOut;
+        a.vIn = a.vOut;
+        dst ^= 1;
+    }
+    d.filteredVar = dst ^ 1;
+    if (p->use_tonemapping) mcrt::launch_tonemap(a.W * a.H, p->min_luminance, a.cIn, fb->display.get(), st);
+    HIPCHK(ctx, hipGetLastError());
+    return MCRT_OK;
+}
+
+extern "C" {
+
+MCRT_API mcrt_status mcrt_render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
+                                        const mcrt_frame_params* p) {
+    return render_guides(s, fb, cam, p, false);
+}
+
+MCRT_API mcrt_status mcrt_render_guides_motion(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
+                                               const mcrt_frame_params* p) {
+    return render_guides(s, fb, cam, p, true);
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_guides(mcrt_framebuffer fb, const void* d_normal_plane,
+                                                 const void* d_albedo_depth) {
+    if (!fb || !d_normal_plane || !d_albedo_depth) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    DenoiseState& d = fb->dn;
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, ensure_guides(fb));
+    HIPCHK(ctx, hipMemcpyAsync(d.guideNormal.get(), d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d.guideAlbedo.get(), d_albedo_depth, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    d.haveGuides = true;
+    d.haveMotion = false;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_motion(mcrt_framebuffer fb, const void* d_motion, const void* d_prev_normal) {
+    if (!fb || !d_motion || !d_prev_normal) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    DenoiseState& d = fb->dn;
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, ensure_motion(fb));
+    HIPCHK(ctx, hipMemcpyAsync(d.motion.get(), d_motion, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d.motionNormal.get(), d_prev_normal, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    d.haveMotion = true;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_read_motion(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                  uint64_t* needed) {
+    if (!fb || which < 0 || which > 1) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    const void* src = which == 0 ? fb->dn.motion.get() : fb->dn.motionNormal.get();
+    return read_plane(fb, src, 16 * (uint64_t)fb->N, host_dst, bytes, needed, "no motion planes yet");
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_moments_enabled(mcrt_framebuffer fb, int on) {
+    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
+    mcrt_ctx ctx = fb->ctx;
+    DenoiseState& d = fb->dn;
+    hipSetDevice(ctx->device);
+    if (on && !d.moments) {
+        HIPCHK(ctx, ensure_plane(fb, d.moments));
+        d.momentFrames = 0;
+    }
+    d.momentsOn = on != 0;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_moments(mcrt_framebuffer fb, const void* d_m1m2, int32_t frames) {
+    if (!fb || !d_m1m2 || frames < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    mcrt_ctx ctx = fb->ctx;
+    DenoiseState& d = fb->dn;
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, ensure_plane(fb, d.moments));
+    HIPCHK(ctx, hipMemcpyAsync(d.moments.get(), d_m1m2, 8 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    d.momentFrames = frames;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_read_guides(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                  uint64_t* needed) {
+    if (!fb || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    const DenoiseState& d = fb->dn;
+    const void* src = which == 0 ? (const void*)d.guideNormal.get() : which == 1 ? (const void*)d.guideAlbedo.get()
+                      : which == 2 ? (const void*)d.moments.get()
+                      : d.filteredVar < 0 ? nullptr : (const void*)d.atrousV[d.filteredVar].get();
+    const uint64_t need = (which < 2 ? 16 : which == 2 ? 8 : 4) * (uint64_t)fb->N;
+    return read_plane(fb, src, need, host_dst, bytes, needed, "no such guide data yet");
+}
+
+MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p) {
+    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    return atrous_chain(fb, p, -1, [](mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, AtrousIn& in) {
+        mcrt_ctx ctx = fb->ctx;
+        DenoiseState& d = fb->dn;
+        HIPCHK(ctx, ensure_atrous(fb));   // k_atrous_prep writes level 0's input to the first scratch planes
+        const bool useVar = p->use_variance && d.moments && d.momentFrames >= 2;
+        const int n = (int)fb->N;
+        Timed t(ctx, K_ATROUS_PREP, nullptr, (int64_t)fb->N);
+        hipLaunchKernelGGL(k_atrous_prep, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, fb->image.get(),
+                           d.guideAlbedo.get(), useVar ? d.moments.get() : nullptr, (float)d.momentFrames,
+                           p->demodulate_albedo ? 1 : 0, d.atrousC[0].get(), d.atrousV[0].get());
+        in = {d.atrousC[0].get(), d.atrousV[0].get(), useVar ? 1 : 0};
+        return MCRT_OK;
+    });
+}
+
+MCRT_API mcrt_status mcrt_temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* cam,
+                                              const mcrt_temporal_params* p) {
+    return temporal_accumulate(fb, cam, p, false);
+}
+
+MCRT_API mcrt_status mcrt_temporal_accumulate_motion(mcrt_framebuffer fb, const mcrt_camera* cam,
+                                                     const mcrt_temporal_params* p) {
+    return temporal_accumulate(fb, cam, p, true);
+}
+
+MCRT_API mcrt_status mcrt_temporal_reset(mcrt_framebuffer fb) {
+    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
+    fb->dn.tHaveHistory = false;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_set_temporal_history(mcrt_framebuffer fb, const void* d_colour,
+                                                           const void* d_moments, const void* d_normal_plane,
+                                                           const mcrt_camera* prev_camera) {
+    if (!fb || !d_colour || !d_moments || !d_normal_plane || !prev_camera)
+        return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    mcrt_ctx ctx = fb->ctx;
+    DenoiseState& d = fb->dn;
+    if (prev_camera->width != fb->W || prev_camera->height != fb->H)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, ensure_temporal(fb));
+    const int cur = d.tCur;
+    HIPCHK(ctx, hipMemcpyAsync(d.tColour[cur].get(), d_colour, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d.tMoments[cur].get(), d_moments, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d.tNormal[cur].get(), d_normal_plane, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
+    d.tPrevCam = *prev_camera;
+    d.tHaveHistory = true;
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_read_temporal(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                    uint64_t* needed) {
+    if (!fb || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    const DenoiseState& d = fb->dn;
+    const int cur = d.tCur;
+    const void* src = which == 0 ? (const void*)d.tColour[cur].get() : which == 1 ? (const void*)d.tMoments[cur].get()
+                      : which == 2 ? (const void*)d.tVar.get() : (const void*)d.tNormal[cur].get();
+    const uint64_t need = (which == 2 ? 4 : 16) * (uint64_t)fb->N;
+    return read_plane(fb, src, need, host_dst, bytes, needed, "no temporal history yet");
+}
+
+MCRT_API mcrt_status mcrt_denoise_guided_temporal(mcrt_framebuffer fb, const mcrt_guided_denoise_params* p,
+                                                  int32_t feedback_level) {
+    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    return atrous_chain(fb, p, feedback_level, [](mcrt_framebuffer fb, const mcrt_guided_denoise_params* p, AtrousIn& in) {
+        mcrt_ctx ctx = fb->ctx;
+        const DenoiseState& d = fb->dn;
+        const int demod = p->demodulate_albedo ? 1 : 0;
+        if (!d.tAccumulated) return fail(ctx, MCRT_ERROR_NOT_READY, "no mcrt_temporal_accumulate yet");
+        if (d.tFedBack)
+            return fail(ctx, MCRT_ERROR_NOT_READY, "the colour history already holds a filtered level of this accumulate");
+        if (demod != d.tDemod)
+            return fail(ctx, MCRT_ERROR_INVALID_ARG, "demodulate_albedo differs from the last mcrt_temporal_accumulate");
+        // level 0 reads the colour history (already in filter space) and the variance plane
+        in = {d.tColour[d.tCur].get(), d.tVar.get(), p->use_variance ? 1 : 0};
+        return MCRT_OK;
+    });
+}
+
+}  // extern "C"

@@ -1,0 +1,313 @@
+// mcrt_host.h -- the host runtime's objects behind the opaque handles of include/mcrt_capi.h, and
+// the few helpers of mcrt_capi.cpp that host code in another file may call.  Not part of the ABI.
+//
+// This is the boundary for host code outside mcrt_capi.cpp: a subsystem with entry points of its
+// own (mcrt_denoise.hip) includes it, reaches the runtime through what is declared here and
+// nothing else, and keeps its state in one struct held by the frame buffer.  It compiles as plain
+// C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip translation unit.
+#pragma once
+#include <climits>
+#include <string>
+#include <vector>
+
+#include "mcrt_devbuf.h"
+#include "mcrt_internal.h"
+
+using mcrt::DevBuf;
+
+#define MCRT_ATROUS_MAX_LEVELS 8
+
+enum KernelId {
+    K_PRIMARY, K_SHADE0, K_SHADEN, K_SHADOW, K_EXTEND, K_ACCUM, K_TRACE_CLOSEST, K_TRACE_ANY,
+    K_BDPT_START, K_BDPT_VERTEX, K_BDPT_CONNECT, K_BDPT_VIS, K_BDPT_GATHER, K_SHADOW_EXTEND,
+    K_GUIDES, K_MOMENTS, K_ATROUS_PREP,
+    K_ATROUS,   // one entry per level: K_ATROUS + i is the launch of step 2^i
+    K_TEMPORAL = K_ATROUS + MCRT_ATROUS_MAX_LEVELS, K_TEMPORAL_VAR, K_GUIDES_MOTION, K_TEMPORAL_MOTION,
+    K_COUNT
+};
+
+struct mcrt_ctx_s {
+    int device = 0;
+    hipStream_t own = nullptr;
+    hipStream_t stream = nullptr;
+    int numCUs = 256;
+    bool profiling = false;
+    bool countHints = false;   // mcrt_ctx_set_profiling(2): occluder-hint counters (one atomic per wave)
+    int* dFlags = nullptr;          // device flags: [0] traversal-stack overflow (mcrt_traverse.h), set by any launch
+    std::string error;
+    struct Pending {
+        int kernel;
+        hipEvent_t a, b;
+        const int* countDev;   // device counter holding the item count (or nullptr)
+        const int* countDev2;  // a second counter added to it (fused launches), or nullptr
+        int64_t items;
+    };
+    std::vector<Pending> pending;
+    double totalMs[K_COUNT] = {};
+    int64_t launches[K_COUNT] = {};
+    int64_t items[K_COUNT] = {};
+};
+
+struct mcrt_scene_s {
+    mcrt_ctx ctx = nullptr;
+    // host copies needed for the BVH build and dynamic updates
+    std::vector<mcrt_shape> shapes;
+    std::vector<uint32_t> indices;
+    std::vector<mcrt_float4> positions;
+    // device arrays
+    DevBuf<mcrt_shape> dShapes;
+    DevBuf<uint32_t> dIndices;
+    DevBuf<float4> dPositions;
+    DevBuf<float2> dUvs;
+    DevBuf<float4> dNormals;
+    DevBuf<mcrt_texture_desc> dTextures;
+    DevBuf<uint8_t> dTexData;
+    DevBuf<uint32_t> dSobol;
+    DevBuf<mcrt_light> dLights;
+    DevBuf<mcrt_material> dMaterials;
+    DevBuf<float4> dSurf;           // surface records (SceneArgs::surf), 128 B per distinct mesh triangle
+    DevBuf<uint32_t> dSurfBase;     // per shape: its first surface record
+    DevBuf<uint32_t> dSurfMeshes;   // build scratch: startIdx | startVertex | base per distinct mesh
+    uint32_t numLights = 0, numMaterials = 0, numTextures = 0;
+    bool hasSobol = false;
+    // BVH
+    DevBuf<float4> dNodes;     // 4 float4 per record
+    bool packets = false;      // coherent launches as wave packets (finish_accel)
+    uint64_t numNodes = 0;
+    uint32_t numTris = 0;
+    double buildMs = 0.0;
+    int builder = 0;   // which builder made the flat structure: 0 host, 1 device LBVH, 2 device SAH
+    int bvhDepth = 0;
+    bool twoLevel = false;          // instanced scene: two-level records (mcrt_bvh2l.cpp)
+    int numMeshes = 0, numInstances = 0;
+    // traversal scratch
+    DevBuf<uint32_t> dSpill;   // spillCap words per ray (ensure_spill)
+    int spillCap = 0;
+    DevBuf<int> dScratch;      // work counters for API queries
+    float bbLo[3] = {0, 0, 0}, bbHi[3] = {0, 0, 0};   // world bounds (root record of the BVH)
+    // occluder hints of the shadow rays after bounce 0, by origin cell (TraceCtx::hint, flat trees):
+    // allocated on the first shadow launch that uses hints (ensure_hint_cell), 2^hintBits words
+    DevBuf<uint32_t> dHintCell;
+    int hintBits = 0;
+    // compact records of the flat tree (TraceCtx::qnodes; mcrt::build_qnodes), empty when not built
+    DevBuf<float4> dQNodes;
+    uint32_t qRoot = 0;
+    bool hintAllocFailed = false;   // no memory for the table: hints stay off for this scene
+    // transform updates (mcrt_accel_update_transforms): the options of the last mcrt_accel_build
+    // (without its world_to_local pointer), the two-level build's refit state, the device top-level
+    // builder's arrays (made by the first update that takes the device path)
+    mcrt_accel_opts lastOpts = {};
+    bool haveOpts = false;
+    mcrt::Bvh2lTop top2l;
+    uint64_t topNodes = 0;
+    mcrt::TopBuildDev* topDev = nullptr;
+    int updatePath = 0;
+    double updateMs = 0.0;
+    // previous poses (mcrt_scene_motion_snapshot): one record per shape, allocated by the first
+    // snapshot; only k_guides_motion receives it
+    DevBuf<PrevPose> dPrevPose;
+    ~mcrt_scene_s() { mcrt::top_build_destroy(topDev); }   // the buffers free themselves
+};
+
+// One frame in flight (PT): the per-frame buffers of mcrt_render_frame, its own stream and
+// spill columns.  Frame i renders in slot i mod S on that slot's stream while mcrt_accumulate
+// runs on the context stream in frame order (it waits for the slot's `done` event and records
+// `free` after reading the slot's radiance), so S frames overlap on the GPU -- each frame's
+// arithmetic and the per-pixel accumulation order are unchanged, so the image is the same bit
+// for bit.  Small per-rank frames (tile split over many GPUs) do not fill 256 CUs alone.
+#define SLOT_FILTER_OFFSET (512 + 176 * MCRT_MAX_BATCH_FRAMES)   // the batch's filters (mcrt_accumulate_frames)
+#define SLOT_COUNTER_BYTES (SLOT_FILTER_OFFSET + (int)sizeof(mcrt_filter) * MCRT_MAX_BATCH_FRAMES + 1536)
+struct FrameSlot {
+    DevBuf<float4> radiance;
+    DevBuf<float4> hitsP;        // primary hits (mcrt_kernels.hip hitSlot)
+    DevBuf<float4> hitsE;        // extension hits by queue slot
+    DevBuf<float4> eO[2], eD[2], eT[2];
+    DevBuf<float4> sO, sD, sL;
+    // [0..31] shadow counts, [32..63] ext counts, [64..127] work counters, then the batch's cameras
+    // (176 B each) from byte 512 and its filters from SLOT_FILTER_OFFSET
+    DevBuf<int> counters;
+    mcrt_camera* cameras() const { return reinterpret_cast<mcrt_camera*>(counters.get() + 128); }
+    mcrt_filter* filters() const {
+        return reinterpret_cast<mcrt_filter*>(reinterpret_cast<char*>(counters.get()) + SLOT_FILTER_OFFSET);
+    }
+    DevBuf<uint32_t> spill;      // per-ray traversal spill columns of this slot's launches
+    hipStream_t stream = nullptr;
+    hipEvent_t done = nullptr;   // recorded after the slot's last render
+    hipEvent_t free = nullptr;   // recorded on the context stream after the slot's buffers were last read
+    int lastMaxDepth = 0;
+    int64_t lastPixels = 0;
+    int lastBatch = 1;           // frames of the slot's last render (mcrt_render_frames)
+    int frames = 1;              // radiance / primary-hit planes of W*H allocated (batch capacity)
+    size_t queueCap = 0;         // entries of each ray-queue buffer
+    // longest-first tile order (FrameArgs::tileOrder): the camera-wave cost of each tile recorded by
+    // this slot's last call, and the order made from it; stream-ordered on the slot's stream
+    DevBuf<uint32_t> tileCost, tileOrder;   // the same size
+    int costTiles = 0;           // tiles of the recorded costs (0: none)
+    // suspended extension walks (TraceCtx::walkCap): MCRT_SUSPEND_F4 float4 per queue entry, and
+    // one count per bounce (zeroed per call)
+    DevBuf<float4> suspend;
+    DevBuf<int> suspendCnt;
+};
+static_assert(SLOT_COUNTER_BYTES % sizeof(int) == 0, "the counter block is allocated as ints");
+
+// Per-frame BDPT arrays (RTBDPTPass::createBuffers, RTBDPTPass.cpp:442-479), one set per frame
+// slot so BDPT frames overlap like PT frames; layouts in mcrt_bdpt.hip.
+struct BdptSet {
+    DevBuf<float4> camV, lightV, slots, splat;
+    DevBuf<int> camCount, lightCount;
+    DevBuf<int> bdptCounters;    // 64 ints: the queue counters (BDPT_CNT_*)
+    DevBuf<float4> bqO[2], bqD[2], bqT[2], bHits;
+    DevBuf<float4> cO, cD, cL;   // connection queue
+    DevBuf<uint32_t> spill;      // traversal spill columns of this set's launches
+    // the light-start queue's sort (mcrt::bdpt_light_sort): keys, sorted keys, slots, permutation
+    DevBuf<uint32_t> lkey, lkey2, lslot, lperm;
+    // the traced bounce queues' sort (same routine; k_bdpt_vertex's keys over 2 N slots)
+    DevBuf<uint32_t> ekey, ekey2, eslot, eperm;
+    DevBuf<uint8_t> sortTmp;
+    int frames = 0;              // batch frames the per-frame arrays hold (plane stride N x frames)
+    // plane stride and band (rows, count, index) whose depth-0 frame-invariant planes k_bdpt_start
+    // wrote for every path of the band
+    size_t constStride = 0;
+    int constBand[3] = {0, 0, -1};
+    // band split, sparse splat exchange: the splats landing in other ranks' rows (BdptArgs::splatList)
+    // and 128 ints of grouping scratch (per-owner counts, cursors)
+    DevBuf<float4> splatList;
+    DevBuf<int> splatAux;
+    // suspended closest-hit walks (TraceCtx::walkCap): MCRT_SUSPEND_F4 float4 per queue entry, one
+    // count per traced queue (zeroed per call)
+    DevBuf<float4> suspend;
+    DevBuf<int> suspendCnt;
+};
+
+// The denoiser's state (mcrt_denoise.hip), every plane allocated on first use.
+struct DenoiseState {
+    // Guided denoiser (mcrt_denoise_guided): the guides of the camera-ray hits, the luminance
+    // moments k_moments keeps next to the image, and two scratch colour / variance planes the
+    // levels ping-pong between (fb->denoised stays mcrt_postprocess's)
+    DevBuf<float4> guideNormal;      // (n, n . (P - cam.pos))
+    DevBuf<float4> guideAlbedo;      // (Kd, |P - cam.pos|), -1 on a miss
+    bool haveGuides = false;
+    DevBuf<float2> moments;          // (sum l, sum l*l)
+    bool momentsOn = false;
+    int momentFrames = 0;            // frames in the moments (host side; restarts at frame_index 0)
+    DevBuf<float4> atrousC[2];
+    DevBuf<float> atrousV[2];
+    int filteredVar = -1;            // which of atrousV holds the last level's variance, -1 before a denoise
+    // Temporal history (mcrt_temporal_accumulate).  Colour, moments and the previous normal-plane
+    // exist twice: k_temporal reads set tCur and writes the other, then tCur flips, so set tCur is
+    // always what the next accumulate (and mcrt_framebuffer_read_temporal) reads.
+    DevBuf<float4> tColour[2];       // integrated colour in filter space, alpha of the current image
+    DevBuf<float4> tMoments[2];      // (mu1, mu2, N, z)
+    DevBuf<float4> tNormal[2];       // the guide record the pixel had when written
+    DevBuf<float> tVar;              // the variance handed to the filter
+    int tCur = 0;
+    bool tHaveHistory = false;       // false: the next accumulate starts without history
+    bool tAccumulated = false;       // an accumulate has run: the planes feed mcrt_denoise_guided_temporal
+    bool tFedBack = false;           // the colour history already holds a filtered level of this accumulate
+    int tDemod = 0;                  // demodulate_albedo of the last accumulate
+    mcrt_camera tPrevCam = {};       // camera of the history planes
+    // Per-object motion (mcrt_render_guides_motion); the planes belong to one set of guides, so
+    // whatever replaces the guides alone clears haveMotion
+    DevBuf<float4> motion;           // (P_prev - P, flag)
+    DevBuf<float4> motionNormal;     // (n_prev, 0) where flag is 1
+    bool haveMotion = false;
+};
+
+struct mcrt_framebuffer_s {
+    mcrt_ctx ctx = nullptr;
+    uint32_t W = 0, H = 0;
+    size_t N = 0;
+    std::vector<FrameSlot> slot;   // slot[0] always allocated; others on first use
+    int cur = 0, next = 0;         // slot of the last rendered frame / of the next one
+    int framesInFlight = 0;        // 0 = auto (mcrt_framebuffer_set_frames_in_flight)
+    DevBuf<float4> wsum;
+    DevBuf<float> wts;
+    DevBuf<float4> image;
+    DevBuf<float4> denoised;     // RTDenoisePass output (persistent: the reference keeps its image)
+    DevBuf<float4> display;      // post-processed image (mcrt_postprocess)
+    DevBuf<uint32_t> hintPix;    // occluder hint of each pixel's bounce-0 shadow ray (TraceCtx::hint)
+    FrameArgs bands{};      // band layout of the last mcrt_render_frame (used by mcrt_accumulate)
+    bool haveBands = false;
+    // BDPT state (allocated on the first BDPT frame for a max depth; mcrt_bdpt.hip has the layout):
+    // per-frame arrays per frame slot; the sampled-light-vertex planes carry state from frame to
+    // frame (BDPT.cl:585), so they are shared and the connect launches stay in frame order
+    int bdptDepth = 0;
+    BdptSet bset[MCRT_MAX_FRAMES_IN_FLIGHT];
+    hipEvent_t bdptConnect = nullptr;   // recorded after the last enqueued frame's connect launch
+    // diagnostics (MCRT_WAVE_CLOCK=1): per-workgroup (start, end) clocks of the last PT call's camera,
+    // shadow+extension and last shadow launches (mcrt_framebuffer_wave_clock)
+    DevBuf<uint32_t> waveClk[3];   // 2 words per workgroup
+    DevBuf<float4> sampLight;      // the sampled-light-vertex planes (D x N)
+    int lastIntegrator = MCRT_INTEGRATOR_PT;
+    int bdptBatch = 1;           // frames of the last BDPT call (plane stride N x bdptBatch)
+    bool bdptOneSet = false;     // a second BDPT set did not fit in HBM: BDPT frames use slot 0 only
+    bool bdptPendingGather = false;   // band-split BDPT frame waiting for the ranks' summed splats
+    int splatExchange = MCRT_SPLAT_EXCHANGE_DENSE;   // mcrt_framebuffer_set_splat_exchange
+    int bdptSet = 0;             // the BDPT set of the last BDPT call
+    DenoiseState dn;
+};
+// The slot of the last rendered frame: what the read-back entry points show.  After a failed
+// regrow its buffers are empty, never stale.
+inline FrameSlot& cur_slot(mcrt_framebuffer fb) { return fb->slot[fb->cur]; }
+static const char* const kNoSlotBuffers = "the frame slot has no buffers (its last allocation failed)";
+
+// mcrt_capi.cpp's helpers that host code in other files may call
+namespace mcrt {
+// records msg as the thread's and the context's (may be NULL) last error; returns code
+mcrt_status fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg);
+// An integer environment variable clamped to lo .. hi, or `def` when it is not set.
+int env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX);
+// Host reads and context-stream work that touch the slots: all slot streams first.
+hipError_t fb_sync(mcrt_framebuffer fb);
+// Makes the context stream wait for every slot's last render (work on the context stream
+// that reads or rewrites slot buffers: BDPT, AOVs, device copies).
+void ctx_wait_slots(mcrt_framebuffer fb);
+bool frame_args(mcrt_framebuffer fb, const mcrt_frame_params* p, FrameArgs& f, std::string& err);
+// Per-ray spill columns for `rays` rays (rounded up to whole waves); grown on demand.
+bool ensure_spill(mcrt_scene s, size_t rays);
+// the coherent launches' view (camera rays, bounce-0 shadow rays): wave packets when the tree allows
+TraceCtx packet_ctx(mcrt_scene s);
+SceneArgs scene_args(mcrt_scene s);
+// Allocates the plane (one T per pixel, zero-filled on the context stream) when it does not exist yet.
+template <class T>
+hipError_t ensure_plane(mcrt_framebuffer fb, DevBuf<T>& p) {
+    if (p) return hipSuccess;
+    hipError_t e = (hipError_t)p.alloc(fb->N);
+    if (e == hipSuccess) e = hipMemsetAsync(p.get(), 0, sizeof(T) * fb->N, fb->ctx->stream);
+    return e;
+}
+}  // namespace mcrt
+
+#define HIPCHK(ctx, expr)                                                                                   \
+    do {                                                                                                    \
+        hipError_t e_ = (hipError_t)(expr);   /* DevBuf reports the runtime's codes as int */               \
+        if (e_ != hipSuccess)                                                                               \
+            return mcrt::fail(ctx, e_ == hipErrorOutOfMemory ? MCRT_ERROR_OUT_OF_MEMORY : MCRT_ERROR_DEVICE, \
+                              std::string(#expr) + ": " + hipGetErrorString(e_));                           \
+    } while (0)
+
+struct Timed {
+    mcrt_ctx c;
+    int k;
+    hipEvent_t a = nullptr, b = nullptr;
+    const int* countDev;
+    int64_t items;
+    hipStream_t st;
+    const int* countDev2;
+    Timed(mcrt_ctx ctx, int kernel, const int* countDev_, int64_t items_, hipStream_t stream = nullptr,
+          const int* countDev2_ = nullptr)
+        : c(ctx), k(kernel), countDev(countDev_), items(items_), st(stream ? stream : ctx->stream),
+          countDev2(countDev2_) {
+        if (c->profiling) {
+            hipEventCreate(&a);
+            hipEventCreate(&b);
+            hipEventRecord(a, st);
+        }
+    }
+    ~Timed() {
+        if (c->profiling) {
+            hipEventRecord(b, st);
+            c->pending.push_back({k, a, b, countDev, countDev2, items});
+        }
+    }
+};

@@ -202,33 +202,6 @@ void launch_guides_motion(const SceneArgs& s, const FrameArgs& f, const mcrt_cam
                           float4* prevNormal, hipStream_t st);
 // mcrt_denoise.hip: the luminance moments (sum l, sum l*l) of the frames k_accumulate just added
 void launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st);
-// the a-trous filter's level-0 input (moments NULL: variance 1) and one level of step `step`
-// (lds: the tile-staged kernel, for steps whose atrous_lds_bytes fit; same bits either way)
-void launch_atrous_prep(int n, const float4* image, const float4* albedoDepth, const float2* moments, int frames,
-                        int demod, float4* cOut, float* vOut, hipStream_t st);
-size_t atrous_lds_bytes(int step);
-void launch_atrous(int W, int H, int step, bool lds, float sigmaNormal, float sigmaDepth, float sigmaLevel, int useVar,
-                   int remodulate, const float4* cIn, const float4* normalPlane, const float4* albedoDepth,
-                   const float* vIn, float4* cOut, float* vOut, hipStream_t st);
-// temporal history (mcrt_temporal_accumulate): k_temporal reprojects the old history planes of the
-// camera `prev` into the pixels of `cam` and writes the new ones (eager: all twelve tap records
-// issued together; otherwise a tap's colour is fetched only when the tap is valid; same bits),
-// k_temporal_var then derives the variance plane from the new moments and normal-plane records
-struct TemporalParams {
-    int W, H, demod, haveHistory;
-    float alpha, alphaMoments, maxHistory, normalThr, planeThr;
-    const mcrt_camera* cam;    // host copies
-    const mcrt_camera* prev;
-    const float4 *image, *albedoDepth, *normalPlane;
-    const float4 *colourOld, *momentsOld, *normalOld;
-    float4 *colourNew, *momentsNew, *normalNew;
-    // mcrt_temporal_accumulate_motion: the motion and previous-normal planes (NULL: the static launch)
-    const float4* motion = nullptr;
-    const float4* prevNormal = nullptr;
-};
-void launch_temporal(const TemporalParams& t, bool eager, hipStream_t st);
-void launch_temporal_var(int W, int H, int minHistory, float normalThr, float planeThr, const float4* moments,
-                         const float4* normalPlane, float* var, hipStream_t st);
 // filters: the reconstruction filter of each batch frame in device memory (KRN/kernel_data.h:63-80), k_accumulate
 // evaluates its weight like ReconstructionPass (reconstruction.cl:21-42); filterStride 0 = one filter for all frames
 void launch_accumulate(const FrameArgs& f, int frame, const mcrt_filter* filters, int filterStride, const float4* radiance, float4* wsum, float* wts,

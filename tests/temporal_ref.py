@@ -1,6 +1,6 @@
-"""numpy restatement of the temporal history kernels (k_temporal, k_temporal_var in
-csrc/mcrt_denoise.hip; mcrt_temporal_accumulate in include/mcrt_capi.h) and a float64 analytic
-scene that makes consistent guides for any camera.
+"""numpy restatement of the temporal history kernels (k_temporal in both its forms, k_temporal_var
+in csrc/mcrt_denoise.hip; mcrt_temporal_accumulate and mcrt_temporal_accumulate_motion in
+include/mcrt_capi.h) and a float64 analytic scene that makes consistent guides for any camera.
 
 Every array is float32 and every line is one float32 operation in the order the comments above the
 two kernels fix; division and square root are IEEE on both sides and no transcendental is involved,
@@ -35,18 +35,21 @@ def pixel_dirs(cam, W, H, dtype=F):
     return a + (b - a) * v
 
 
-def reproject(ad, cam, prev):
-    """(r, fx, fy, ok): r = P - prev.pos per pixel, the history position in pixels, and whether the
-    pixel gets as far as the taps (a hit, in front of prev, inside the guard band)."""
+def reproject(ad, cam, prev, motion=None):
+    """(r, fx, fy, ok): r = P - prev.pos per pixel (through the motion records where their flag is
+    1), the history position in pixels, and whether the pixel gets as far as the taps (a hit, no
+    negative motion flag, in front of prev, inside the guard band)."""
     ad = np.asarray(ad, F)
     H, W = ad.shape[:2]
+    mv = np.zeros((H, W, 4), F) if motion is None else np.asarray(motion, F)
     m = pixel_dirs(cam, W, H)
     depth = ad[..., 3]
-    hit = depth > 0
+    hit = (depth > 0) & ~(mv[..., 3] < F(0))
     with np.errstate(all="ignore"):
         k = depth / np.sqrt(_dot3(m, m))
         dpos = _cam3(cam, "pos") - _cam3(prev, "pos")
         r = m * k[..., None] + dpos
+        r = np.where((mv[..., 3] == F(1))[..., None], r + mv[..., :3], r)
         M = np.asarray(prev["worldToClip"], F).reshape(4, 4)
         cx = (M[0, 0] * r[..., 0] + M[0, 1] * r[..., 1]) + M[0, 2] * r[..., 2]
         cy = (M[1, 0] * r[..., 0] + M[1, 1] * r[..., 1]) + M[1, 2] * r[..., 2]
@@ -58,15 +61,24 @@ def reproject(ad, cam, prev):
     return r, fx, fy, ok
 
 
-def accumulate(image, normal_plane, albedo_depth, cam, history=None, alpha=0.2, alpha_moments=0.2, max_history=32,
-               normal_threshold=0.1, plane_threshold=0.01, demodulate_albedo=False, info=None, **_ignored):
-    """k_temporal.  history = (colour, moments, normal_plane, prev_cam) or None.  Returns the new
-    (colour, moments, normal_plane) planes; `info` (a dict) receives per pixel the number of valid
+def accumulate(image, normal_plane, albedo_depth, cam, history=None, motion=None, prev_normal=None, alpha=0.2,
+               alpha_moments=0.2, max_history=32, normal_threshold=0.1, plane_threshold=0.01, demodulate_albedo=False,
+               info=None, use_prev_normal=True, **_ignored):
+    """k_temporal, both forms.  history = (colour, moments, normal_plane, prev_cam) or None; motion =
+    (H, W, 4) records (P_prev - P, flag) and prev_normal = (H, W, 4) records (n_prev, 0) restate
+    MOTION = true, motion=None is MOTION = false and behaves as an all-zero plane: the motion record
+    is added to r where its flag is 1, the normal test then compares the history tap with the
+    previous normal, and a negative flag tests no tap.  use_prev_normal=False keeps gp = g on moved
+    pixels too (what the rule would do without the previous-normal plane; tests only).  Returns the
+    new (colour, moments, normal_plane) planes; `info` (a dict) receives per pixel the number of valid
     taps, the tap corner (ix, iy), the history position and the reprojection flag."""
     img = np.asarray(image, F)
     g = np.asarray(normal_plane, F)
     ad = np.asarray(albedo_depth, F)
     H, W = ad.shape[:2]
+    gp = g[..., :3]
+    if motion is not None and use_prev_normal:
+        gp = np.where((np.asarray(motion, F)[..., 3] == F(1))[..., None], np.asarray(prev_normal, F)[..., :3], gp)
     c = img.copy()
     if demodulate_albedo:
         c[..., :3] = c[..., :3] / _demod(ad)
@@ -80,20 +92,20 @@ def accumulate(image, normal_plane, albedo_depth, cam, history=None, alpha=0.2, 
     if history is not None:
         hc, hm, hn, prev = history
         hc, hm, hn = np.asarray(hc, F), np.asarray(hm, F), np.asarray(hn, F)
-        r, fx, fy, ok = reproject(ad, cam, prev)
+        r, fx, fy, ok = reproject(ad, cam, prev, motion)
         fxs, fys = np.where(ok, fx, F(0)), np.where(ok, fy, F(0))
         ix, iy = np.floor(fxs).astype(np.int64), np.floor(fys).astype(np.int64)
         tx, ty = fxs - ix.astype(F), fys - iy.astype(F)
-        zr = np.sqrt(_dot3(r, r))
-        tol = F(plane_threshold) * zr
         with np.errstate(all="ignore"):
+            zr = np.sqrt(_dot3(r, r))
+            tol = F(plane_threshold) * zr
             for j in (0, 1):
                 for i in (0, 1):
                     qx, qy = ix + i, iy + j
                     inside = ok & (qx >= 0) & (qx < W) & (qy >= 0) & (qy < H)
                     cqx, cqy = np.clip(qx, 0, W - 1), np.clip(qy, 0, H - 1)
                     m_q, n_q, c_q = hm[cqy, cqx], hn[cqy, cqx], hc[cqy, cqx]
-                    dn = g[..., :3] - n_q[..., :3]
+                    dn = gp - n_q[..., :3]
                     res = np.abs(_dot3(n_q, r) - n_q[..., 3])
                     valid = inside & (m_q[..., 3] > 0) & (_dot3(dn, dn) <= F(normal_threshold)) & (res <= tol)
                     w = (tx if i else F(1) - tx) * (ty if j else F(1) - ty)

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import atrous_ref as ar
+from denoise_harness import ATOL, RTOL, Installed, bits, tm_rmse
 from mcrt import scenes
 from mcrt import types as T
 from mcrt.camera import make_camera, scene_camera
@@ -19,13 +20,8 @@ from mcrt.camera import make_camera, scene_camera
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-RTOL, ATOL = 2e-5, 1e-7
 MOMENT_FRAMES = 6
 SIGMAS = dict(sigma_normal=0.1, sigma_depth=0.02, sigma_luminance=4.0)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def _synthetic(W, H, seed):
@@ -57,39 +53,11 @@ def _synthetic(W, H, seed):
     return img.astype(F), npl, ad, mom
 
 
-class _Installed:
-    """A frame buffer holding a synthetic image (unit weights), guides and moments."""
-
-    def __init__(self, ctx, img, npl, ad, mom=None, frames=0):
-        import torch
-        from mcrt import lib
-        H, W = img.shape[:2]
-        self.ctx = ctx
-        self.fb = lib.FrameBuffer(ctx, W, H)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, F).reshape(-1)).cuda()   # noqa: E731
-        self.keep = [dev(img), torch.ones(H * W, dtype=torch.float32, device="cuda"), dev(npl), dev(ad)]
-        if mom is not None:
-            self.keep.append(dev(mom))
-        torch.cuda.synchronize()
-        self.fb.set_accumulation(self.keep[0].data_ptr(), self.keep[1].data_ptr())
-        self.fb.set_guides(self.keep[2].data_ptr(), self.keep[3].data_ptr())
-        if mom is not None:
-            self.fb.set_moments(self.keep[4].data_ptr(), frames)
-        ctx.sync()
-
-    def run(self, **kw):
-        self.fb.denoise_guided(**kw)
-        return self.fb.read(3), self.fb.read_guides(T.GUIDE_FILTERED_VARIANCE)
-
-    def close(self):
-        self.fb.close()
-
-
 @pytest.fixture(scope="module", params=[(45, 37), (16, 16)], ids=["45x37", "16x16"])
 def synthetic(request, hip_ctx):
     W, H = request.param
     img, npl, ad, mom = _synthetic(W, H, seed=W)
-    inst = _Installed(hip_ctx, img, npl, ad, mom, MOMENT_FRAMES)
+    inst = Installed(hip_ctx, dict(img=img, npl=npl, ad=ad, mom=mom, frames=MOMENT_FRAMES))
     np.testing.assert_array_equal(inst.fb.read(2), img)   # image = sum / 1: the input, bit for bit
     yield inst, img, npl, ad, mom
     inst.close()
@@ -108,8 +76,8 @@ def test_each_level_matches_one_reference_level(synthetic, use_var):
         np.testing.assert_allclose(got_c, ref_c, rtol=RTOL, atol=ATOL, err_msg=f"colour, levels={L}")
         np.testing.assert_allclose(got_v, ref_v, rtol=RTOL, atol=ATOL, err_msg=f"variance, levels={L}")
         again_c, again_v = inst.run(levels=L, use_variance=use_var, demodulate_albedo=False, **SIGMAS)
-        np.testing.assert_array_equal(_bits(again_c), _bits(got_c))
-        np.testing.assert_array_equal(_bits(again_v), _bits(got_v))
+        np.testing.assert_array_equal(bits(again_c), bits(got_c))
+        np.testing.assert_array_equal(bits(again_v), bits(got_v))
         c, var = got_c, got_v   # the next level is judged on the GPU's own output
 
 
@@ -123,8 +91,8 @@ def test_staged_and_direct_kernels_agree_bit_for_bit(synthetic, monkeypatch):
     monkeypatch.setenv("MCRT_ATROUS_LDS_MAX_STEP", "1")   # the switch between levels 0 and 1
     mixed = inst.run(**kw)
     for a, b in ((staged, direct), (staged, mixed)):
-        np.testing.assert_array_equal(_bits(a[0]), _bits(b[0]))
-        np.testing.assert_array_equal(_bits(a[1]), _bits(b[1]))
+        np.testing.assert_array_equal(bits(a[0]), bits(b[0]))
+        np.testing.assert_array_equal(bits(a[1]), bits(b[1]))
 
 
 # ---- 2. demodulation, tone mapping -----------------------------------------------------------
@@ -140,12 +108,12 @@ def test_demodulation_and_tonemap(synthetic, hip_ctx):
     # tone mapping = k_tonemap over the untone-mapped output
     mapped, _ = inst.run(levels=1, use_variance=True, demodulate_albedo=True, tonemap=True, min_luminance=1.7,
                          **SIGMAS)
-    other = _Installed(hip_ctx, got_c, npl, ad)
-    np.testing.assert_array_equal(_bits(other.fb.read(2)), _bits(got_c))
+    other = Installed(hip_ctx, dict(img=got_c, npl=npl, ad=ad))
+    np.testing.assert_array_equal(bits(other.fb.read(2)), bits(got_c))
     other.fb.postprocess(tonemap=True, min_luminance=1.7)
     want = other.fb.read(3)
     other.close()
-    np.testing.assert_array_equal(_bits(mapped), _bits(want))
+    np.testing.assert_array_equal(bits(mapped), bits(want))
 
 
 # ---- 3. guides from a render -----------------------------------------------------------------
@@ -171,7 +139,7 @@ def test_guide_albedo_normals_and_misses(rendered_guides):
         fb.render_guides(ds, cam, texture_lod=lod)
         a = fb.read_guides(T.GUIDE_ALBEDO_DEPTH)
         aov = fb.render_aov(ds, cam, T.AOV_ALBEDO, texture_lod=lod)
-        np.testing.assert_array_equal(_bits(a[..., :3]), _bits(aov[..., :3]))
+        np.testing.assert_array_equal(bits(a[..., :3]), bits(aov[..., :3]))
     fb.render_guides(ds, cam)
     hit = ad[..., 3] >= 0
     assert hit.mean() > 0.5
@@ -270,8 +238,8 @@ def test_guide_bands_restrict_the_rows(rendered_guides, hip_ctx):
     fb.render_guides(ds, cam, band_rows=8, num_bands=2, band_index=1)
     n1, a1 = fb.read_guides(T.GUIDE_NORMAL_PLANE), fb.read_guides(T.GUIDE_ALBEDO_DEPTH)
     own = ((np.arange(GH) // 8) % 2) == 1
-    np.testing.assert_array_equal(_bits(n1[own]), _bits(npl[own]))
-    np.testing.assert_array_equal(_bits(a1[own]), _bits(ad[own]))
+    np.testing.assert_array_equal(bits(n1[own]), bits(npl[own]))
+    np.testing.assert_array_equal(bits(a1[own]), bits(ad[own]))
     np.testing.assert_array_equal(n1[~own], 7.5)
     np.testing.assert_array_equal(a1[~own], 7.5)
     fb.render_guides(ds, cam)   # whole image again for the other tests
@@ -294,32 +262,27 @@ def test_moments_follow_the_accumulated_frames(hip_ctx):
         frames.append(fb.read_frame(0))
         if f == 2:
             after3 = fb.read_guides(T.GUIDE_MOMENTS)
-    np.testing.assert_array_equal(_bits(fb.read_guides(T.GUIDE_MOMENTS)), _bits(ar.accumulate_moments(frames)))
+    np.testing.assert_array_equal(bits(fb.read_guides(T.GUIDE_MOMENTS)), bits(ar.accumulate_moments(frames)))
     assert fb.read_guides(T.GUIDE_MOMENTS)[..., 0].max() > 0
     # the image and the weighted sums do not notice the moments
     for which in (1, 2):
-        np.testing.assert_array_equal(_bits(fb.read(which)), _bits(plain.read(which)))
+        np.testing.assert_array_equal(bits(fb.read(which)), bits(plain.read(which)))
     # frame 0 resets
     fb.render(ds, cam, frame=0, max_depth=2)
     fb.accumulate(box, 0)
-    np.testing.assert_array_equal(_bits(fb.read_guides(T.GUIDE_MOMENTS)), _bits(ar.accumulate_moments(frames[:1])))
+    np.testing.assert_array_equal(bits(fb.read_guides(T.GUIDE_MOMENTS)), bits(ar.accumulate_moments(frames[:1])))
     # a batch of three frames = three single frames
     fb.render_frames(ds, [cam, cam, cam], frame=0, max_depth=2)
     fb.accumulate_frames([box, box, box], 0)
-    np.testing.assert_array_equal(_bits(fb.read_guides(T.GUIDE_MOMENTS)), _bits(after3))
+    np.testing.assert_array_equal(bits(fb.read_guides(T.GUIDE_MOMENTS)), bits(after3))
     for k in range(3):
-        np.testing.assert_array_equal(_bits(fb.read_frame(k)), _bits(frames[k]))
+        np.testing.assert_array_equal(bits(fb.read_frame(k)), bits(frames[k]))
     fb.close()
     plain.close()
     ds.close()
 
 
 # ---- 5. it denoises ----------------------------------------------------------------------------
-def _tm_rmse(a, truth):
-    a, truth = a[..., :3].astype(np.float64), truth[..., :3].astype(np.float64)
-    return float(np.sqrt(np.mean((a / (1 + a) - truth / (1 + truth)) ** 2)))
-
-
 def test_it_denoises_a_4spp_render(hip_ctx):
     """test_scene(), "mixed" camera, 64x48, depth 2: 4 frames accumulated with the box filter and
     the moments, denoised with the defaults; ground truth = the mean of frames 16..271.  The
@@ -347,15 +310,15 @@ def test_it_denoises_a_4spp_render(hip_ctx):
         fb.accumulate(box, f)
     fb.render_guides(ds, cam)
     noisy = fb.read(2)
-    base = _tm_rmse(noisy, truth)
+    base = tm_rmse(noisy, truth)
     for use_var in (True, False):
         fb.denoise_guided(use_variance=use_var)
         out = fb.read(3)
         assert np.isfinite(out).all()
-        e = _tm_rmse(out, truth)
+        e = tm_rmse(out, truth)
         print(f"tone-mapped RMSE: 4 spp {base:.4f} -> denoised {e:.4f} (use_variance={use_var})")
         assert e < base, (e, base)
-    np.testing.assert_array_equal(_bits(fb.read(2)), _bits(noisy))   # the image itself is not touched
+    np.testing.assert_array_equal(bits(fb.read(2)), bits(noisy))   # the image itself is not touched
     fb.close()
     ds.close()
 
@@ -379,7 +342,7 @@ def test_status_codes(hip_ctx):
     assert L.mcrt_framebuffer_read_guides(fb.h, 2, None, 0, ctypes.byref(need)) == OK and need.value == 16 * 16 * 8
     assert L.mcrt_framebuffer_read_guides(fb.h, 4, None, 0, None) == INVALID
     img, npl, ad, mom = _synthetic(16, 16, 1)
-    inst = _Installed(hip_ctx, img, npl, ad)
+    inst = Installed(hip_ctx, dict(img=img, npl=npl, ad=ad))
     for bad in (dict(levels=0), dict(levels=9), dict(sigma_normal=0.0), dict(sigma_depth=-1.0),
                 dict(sigma_luminance=0.0)):
         with pytest.raises(lib.MCRTError, match="status 1"):
@@ -387,10 +350,10 @@ def test_status_codes(hip_ctx):
     # use_variance without moments, or with fewer than two frames in them, degrades to var = 1
     want = inst.run(levels=2, use_variance=False, demodulate_albedo=False)
     got = inst.run(levels=2, use_variance=True, demodulate_albedo=False)
-    np.testing.assert_array_equal(_bits(got[0]), _bits(want[0]))
+    np.testing.assert_array_equal(bits(got[0]), bits(want[0]))
     inst.fb.enable_moments()
     got = inst.run(levels=2, use_variance=True, demodulate_albedo=False)
-    np.testing.assert_array_equal(_bits(got[0]), _bits(want[0]))
+    np.testing.assert_array_equal(bits(got[0]), bits(want[0]))
     inst.close()
     fb.close()
     # a band-split BDPT frame waiting for its gather: not ready until mcrt_bdpt_gather
@@ -436,17 +399,17 @@ def test_ordering_with_frames_in_flight_and_postprocess_untouched(hip_ctx):
 
     fb, out, var = sequence(False)
     fb2, out2, var2 = sequence(True)
-    np.testing.assert_array_equal(_bits(out), _bits(out2))
-    np.testing.assert_array_equal(_bits(var), _bits(var2))
+    np.testing.assert_array_equal(bits(out), bits(out2))
+    np.testing.assert_array_equal(bits(var), bits(var2))
     fb2.close()
     img = fb.read(2)
     assert np.abs(out - img).max() > 0
     fb.postprocess()
-    np.testing.assert_array_equal(_bits(fb.read(3)), _bits(img))   # the plain image, as before
+    np.testing.assert_array_equal(bits(fb.read(3)), bits(img))   # the plain image, as before
     fb.postprocess(denoise=True, radius=2, sigma_spatial=1.5, sigma_range=0.3)
     bilateral = fb.read(3)
     fb.denoise_guided()
     fb.postprocess(denoise=True, radius=0)   # writes nothing: shows the bilateral pass's own image
-    np.testing.assert_array_equal(_bits(fb.read(3)), _bits(bilateral))
+    np.testing.assert_array_equal(bits(fb.read(3)), bits(bilateral))
     fb.close()
     ds.close()

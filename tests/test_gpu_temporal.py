@@ -13,6 +13,7 @@ import pytest
 
 import atrous_ref as ar
 import temporal_ref as tr
+from denoise_harness import ATOL, RTOL, Installed, bits, compare_planes, pair_a, synth_planes, tm_rmse
 from mcrt import scenes
 from mcrt import types as T
 from mcrt.camera import make_camera, scene_camera
@@ -20,24 +21,8 @@ from mcrt.camera import make_camera, scene_camera
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-RTOL, ATOL = 2e-5, 1e-7
 SIGMAS = dict(sigma_normal=0.1, sigma_depth=0.02, sigma_luminance=4.0)
 FAR = (1000.0, 1000.0, 1000.0)
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def _ndiff(a, b):
-    return int((_bits(a) != _bits(b)).sum())
-
-
-def pair_a(W, H, offset=(0.0, 0.0, 0.0)):
-    o = np.asarray(offset, np.float64)
-    prev = make_camera(tuple(o + (0.0, 1.0, -4.0)), tuple(o + (0.0, 0.6, 0.0)), W, H, fovy=50.0)
-    cur = make_camera(tuple(o + (0.6, 1.1, -3.8)), tuple(o + (0.1, 0.6, 0.0)), W, H, fovy=50.0)
-    return prev, cur
 
 
 def _case(W, H, offset, seed):
@@ -48,64 +33,8 @@ def _case(W, H, offset, seed):
     prev, cur = pair_a(W, H, offset)
     sid, npl, depth = tr.scene_guides(cur, offset)
     _, pnpl, pdepth = tr.scene_guides(prev, offset)
-    ad = np.empty((H, W, 4), F)
-    ad[..., :3] = rng.uniform(0.05, 1.0, (H, W, 3))
-    ad[..., 0][rng.random((H, W)) < 0.1] = 0.0
-    ad[..., 1][rng.random((H, W)) < 0.1] = 5e-4
-    ad[sid == 0, :3] = 0.0
-    ad[..., 3] = depth
-    img = (np.linspace(0.5, 2.0, W)[None, :, None] * 10.0 ** rng.uniform(-0.05, 0.05, (H, W, 4))).astype(F)
-    img[..., 3] = rng.uniform(0, 1, (H, W))
-    hc = rng.uniform(0.3, 2.5, (H, W, 4)).astype(F)
-    wild = rng.random((H, W)) < 0.2
-    hc[wild] = (10.0 ** rng.uniform(-3, 3, (int(wild.sum()), 4))).astype(F)
-    mu1 = rng.uniform(0.2, 3.0, (H, W)).astype(F)
-    mu2 = (mu1 * mu1 + rng.uniform(0.0, 0.5, (H, W)).astype(F)).astype(F)
-    flat = rng.random((H, W)) < 0.15
-    mu2[flat] = (mu1 * mu1)[flat]              # zero variance
-    hm = np.stack([mu1, mu2, rng.integers(1, 41, (H, W)).astype(F), pdepth], -1).astype(F)
+    ad, img, hc, hm = synth_planes(rng, sid, depth, pdepth)
     return dict(prev=prev, cur=cur, sid=sid, npl=npl, ad=ad, img=img, hist=(hc, hm, pnpl))
-
-
-class _Installed:
-    """A frame buffer holding a synthetic image (unit weights), guides and, optionally, history."""
-
-    def __init__(self, ctx, case, history=True):
-        import torch
-        from mcrt import lib
-        H, W = case["img"].shape[:2]
-        self.fb = lib.FrameBuffer(ctx, W, H)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, F).reshape(-1)).cuda()   # noqa: E731
-        self.keep = [dev(case["img"]), torch.ones(H * W, dtype=torch.float32, device="cuda"), dev(case["npl"]),
-                     dev(case["ad"])] + [dev(a) for a in case["hist"]]
-        torch.cuda.synchronize()
-        self.fb.set_accumulation(self.keep[0].data_ptr(), self.keep[1].data_ptr())
-        self.fb.set_guides(self.keep[2].data_ptr(), self.keep[3].data_ptr())
-        if history:
-            self.fb.set_temporal_history(self.keep[4].data_ptr(), self.keep[5].data_ptr(), self.keep[6].data_ptr(),
-                                         case["prev"])
-        ctx.sync()
-
-    def planes(self):
-        return [self.fb.read_temporal(w) for w in (T.TEMPORAL_COLOUR, T.TEMPORAL_MOMENTS, T.TEMPORAL_VARIANCE,
-                                                   T.TEMPORAL_NORMAL_PLANE)]
-
-    def close(self):
-        self.fb.close()
-
-
-def _compare(got, ref, what):
-    colour, mom, var, nrm = got
-    rc, rm, rv, rn = ref
-    print(f"{what}: bit-different values: colour {_ndiff(colour, rc)}, moments {_ndiff(mom, rm)}, "
-          f"variance {_ndiff(var, rv)}, normal-plane {_ndiff(nrm, rn)} of {var.size} pixels")
-    assert all(np.isfinite(a).all() for a in got)
-    np.testing.assert_allclose(colour, rc, rtol=RTOL, atol=ATOL, err_msg="colour history")
-    np.testing.assert_allclose(mom, rm, rtol=RTOL, atol=ATOL, err_msg="moments history, N, depth")
-    np.testing.assert_array_equal(_bits(nrm), _bits(rn))
-    bound = 2e-5 * rm[..., 1].astype(np.float64) + 1e-7
-    err = np.abs(var.astype(np.float64) - rv.astype(np.float64))
-    assert (err <= bound).all(), (err.max(), np.max(err / bound))
 
 
 # ---- 1. one step against the reference --------------------------------------------------------
@@ -128,11 +57,11 @@ def test_one_step_matches_the_reference(hip_ctx, size, offset, demod, monkeypatc
     assert (rm[..., 2] < 4).sum() > 10 and (rm[..., 2] >= 4).sum() > 10
     for loads in ("eager", "lazy"):            # both load forms of k_temporal: the same bits
         monkeypatch.setenv("MCRT_TEMPORAL_LOADS", loads)
-        inst = _Installed(hip_ctx, case)
+        inst = Installed(hip_ctx, case)
         inst.fb.temporal_accumulate(case["cur"], **params)
         got = inst.planes()
         inst.close()
-        _compare(got, (rc, rm, rv, rn), f"{W}x{H} offset {offset[0]:g} demod {demod} {loads}")
+        compare_planes(got, (rc, rm, rv, rn), f"{W}x{H} offset {offset[0]:g} demod {demod} {loads}")
 
 
 # ---- 2. reset and first call --------------------------------------------------------------------
@@ -142,7 +71,7 @@ def test_reset_and_first_call_start_without_history(hip_ctx, demod):
     want, _ = ar.prepare(case["img"], case["ad"], demodulate=demod)
     lum = ar.luminance(want)
     for first in (True, False):
-        inst = _Installed(hip_ctx, case, history=not first)
+        inst = Installed(hip_ctx, case, history=not first)
         if not first:
             inst.fb.temporal_accumulate(case["cur"], demodulate_albedo=demod)
             assert (inst.fb.read_temporal(T.TEMPORAL_MOMENTS)[..., 2] > 1).any()
@@ -151,12 +80,12 @@ def test_reset_and_first_call_start_without_history(hip_ctx, demod):
         colour, mom, var, nrm = inst.planes()
         inst.close()
         np.testing.assert_array_equal(mom[..., 2], 1.0)
-        np.testing.assert_array_equal(_bits(colour), _bits(want))
-        np.testing.assert_array_equal(_bits(mom[..., 0]), _bits(lum))
-        np.testing.assert_array_equal(_bits(mom[..., 1]), _bits(lum * lum))
-        np.testing.assert_array_equal(_bits(mom[..., 3]), _bits(case["ad"][..., 3]))
-        np.testing.assert_array_equal(_bits(nrm), _bits(case["npl"]))
-        np.testing.assert_array_equal(_bits(var), _bits(tr.variance(mom, nrm, **tr.DEFAULTS)))
+        np.testing.assert_array_equal(bits(colour), bits(want))
+        np.testing.assert_array_equal(bits(mom[..., 0]), bits(lum))
+        np.testing.assert_array_equal(bits(mom[..., 1]), bits(lum * lum))
+        np.testing.assert_array_equal(bits(mom[..., 3]), bits(case["ad"][..., 3]))
+        np.testing.assert_array_equal(bits(nrm), bits(case["npl"]))
+        np.testing.assert_array_equal(bits(var), bits(tr.variance(mom, nrm, **tr.DEFAULTS)))
 
 
 # ---- 3. the filter chain ------------------------------------------------------------------------
@@ -166,7 +95,7 @@ def test_filter_chain_and_feedback(hip_ctx, size):
     case = _case(W, H, (0.0, 0.0, 0.0), seed=W + 1)
 
     def accumulated():
-        inst = _Installed(hip_ctx, case)
+        inst = Installed(hip_ctx, case)
         inst.fb.temporal_accumulate(case["cur"], demodulate_albedo=False)
         return inst
 
@@ -179,17 +108,17 @@ def test_filter_chain_and_feedback(hip_ctx, size):
     np.testing.assert_allclose(display, ref_c, rtol=RTOL, atol=ATOL)
     np.testing.assert_allclose(plain.fb.read_guides(T.GUIDE_FILTERED_VARIANCE), ref_v, rtol=RTOL, atol=ATOL)
     # nothing was fed back: the history is as it was, and the call may be repeated
-    np.testing.assert_array_equal(_bits(plain.fb.read_temporal(T.TEMPORAL_COLOUR)), _bits(colour))
+    np.testing.assert_array_equal(bits(plain.fb.read_temporal(T.TEMPORAL_COLOUR)), bits(colour))
     plain.fb.denoise_guided_temporal(levels=1, demodulate_albedo=False, feedback_level=-1, **SIGMAS)
-    np.testing.assert_array_equal(_bits(plain.fb.read(3)), _bits(display))
+    np.testing.assert_array_equal(bits(plain.fb.read(3)), bits(display))
     level0_var = plain.fb.read_guides(T.GUIDE_FILTERED_VARIANCE)
     plain.close()
     # level 0 fed back = the display of the feedback-less one-level run, bit for bit
     fed = accumulated()
     fed.fb.denoise_guided_temporal(levels=2, demodulate_albedo=False, feedback_level=0, **SIGMAS)
     two_levels = fed.fb.read(3)
-    np.testing.assert_array_equal(_bits(fed.fb.read_temporal(T.TEMPORAL_COLOUR)), _bits(display))
-    np.testing.assert_array_equal(_bits(fed.fb.read_temporal(T.TEMPORAL_MOMENTS)), _bits(mom))
+    np.testing.assert_array_equal(bits(fed.fb.read_temporal(T.TEMPORAL_COLOUR)), bits(display))
+    np.testing.assert_array_equal(bits(fed.fb.read_temporal(T.TEMPORAL_MOMENTS)), bits(mom))
     # the second level at single-pass accuracy: one reference level over the GPU's own level 0
     ref2, _ = ar.level(display, level0_var, case["npl"], case["ad"], 2, SIGMAS["sigma_normal"], SIGMAS["sigma_depth"],
                        ar.sigma_of_level(1, SIGMAS["sigma_luminance"], True), True)
@@ -200,7 +129,7 @@ def test_filter_chain_and_feedback(hip_ctx, size):
     fed.close()
     rc, rm, rn = tr.accumulate(case["img"], case["npl"], case["ad"], case["cur"], (display, mom, nrm, case["cur"]),
                                **tr.DEFAULTS)
-    _compare(got, (rc, rm, tr.variance(rm, rn, **tr.DEFAULTS), rn), f"{W}x{H} accumulate after feedback")
+    compare_planes(got, (rc, rm, tr.variance(rm, rn, **tr.DEFAULTS), rn), f"{W}x{H} accumulate after feedback")
 
 
 def test_remodulation_and_tonemap_as_the_single_frame_filter(hip_ctx):
@@ -208,7 +137,7 @@ def test_remodulation_and_tonemap_as_the_single_frame_filter(hip_ctx):
     like mcrt_denoise_guided: one level over the history equals mcrt_denoise_guided's one level over
     an image that demodulates to that history."""
     case = _case(45, 37, (0.0, 0.0, 0.0), seed=11)
-    inst = _Installed(hip_ctx, case, history=False)
+    inst = Installed(hip_ctx, case, history=False)
     inst.fb.temporal_accumulate(case["cur"], demodulate_albedo=True)   # no history: colour = image / albedo
     colour, mom, var, nrm = inst.planes()
     inst.fb.denoise_guided_temporal(levels=1, demodulate_albedo=True, feedback_level=-1, **SIGMAS)
@@ -220,21 +149,15 @@ def test_remodulation_and_tonemap_as_the_single_frame_filter(hip_ctx):
                                     min_luminance=1.7, **SIGMAS)
     mapped = inst.fb.read(3)
     inst.close()
-    other = _Installed(hip_ctx, dict(case, img=got), history=False)
+    other = Installed(hip_ctx, dict(case, img=got), history=False)
     other.fb.postprocess(tonemap=True, min_luminance=1.7)
     want = other.fb.read(3)
     other.close()
-    np.testing.assert_array_equal(_bits(mapped), _bits(want))
+    np.testing.assert_array_equal(bits(mapped), bits(want))
 
 
 # ---- 4. it helps a real render --------------------------------------------------------------------
 RW, RH = 64, 48
-
-
-def _tm_rmse(a, truth, mask=None):
-    a, truth = a[..., :3].astype(np.float64), truth[..., :3].astype(np.float64)
-    d = (a / (1 + a) - truth / (1 + truth)) ** 2
-    return float(np.sqrt(np.mean(d if mask is None else d[mask])))
 
 
 def _truth(ctx, ds, cam):
@@ -291,14 +214,14 @@ def test_it_helps_a_1spp_interactive_render(hip_ctx):
     cam = scene_camera("mixed", RW, RH)
     truth = _truth(hip_ctx, ds, cam)
     out, raw, single, N, hit = _displayed_frames(hip_ctx, ds, [cam] * 8)
-    e_t, e_s, e_r = _tm_rmse(out, truth), _tm_rmse(single, truth), _tm_rmse(raw, truth)
+    e_t, e_s, e_r = tm_rmse(out, truth), tm_rmse(single, truth), tm_rmse(raw, truth)
     print(f"static camera, frame 8: raw {e_r:.4f}, single-frame guided {e_s:.4f}, temporal + filter {e_t:.4f}")
     assert e_t < e_s and e_t < e_r, (e_t, e_s, e_r)
     cams = [_mixed_camera((0.04 * d, 0.0, 0.0)) for d in range(8)]
     truth_m = _truth(hip_ctx, ds, cams[-1])
     out, raw, single, N, hit = _displayed_frames(hip_ctx, ds, cams)
     kept = hit & (N >= 4)
-    e_t, e_s, e_r = (_tm_rmse(a, truth_m, kept) for a in (out, single, raw))
+    e_t, e_s, e_r = (tm_rmse(a, truth_m, kept) for a in (out, single, raw))
     print(f"moving camera, frame 8: {kept.sum()} of {hit.sum()} hit pixels with N >= 4; on them raw {e_r:.4f}, "
           f"single-frame guided {e_s:.4f}, temporal + filter {e_t:.4f}")
     assert kept.sum() >= 0.5 * hit.sum()
@@ -333,7 +256,7 @@ def test_existing_outputs_do_not_notice_the_temporal_calls(hip_ctx):
         return out
 
     for a, b in zip(sequence(True), sequence(False)):
-        np.testing.assert_array_equal(_bits(a), _bits(b))
+        np.testing.assert_array_equal(bits(a), bits(b))
     ds.close()
 
 
@@ -373,7 +296,7 @@ def test_status_codes(hip_ctx):
     assert L.mcrt_temporal_accumulate(fb.h, camp, ctypes.byref(good)) == NOT_READY
     assert L.mcrt_denoise_guided_temporal(fb.h, ctypes.byref(filt), 0) == NOT_READY
     fb.close()
-    inst = _Installed(hip_ctx, case)
+    inst = Installed(hip_ctx, case)
     fb = inst.fb
     # guides and an installed history, but no accumulate yet
     assert L.mcrt_denoise_guided_temporal(fb.h, ctypes.byref(filt), 0) == NOT_READY
@@ -463,5 +386,5 @@ def test_ordering_with_frames_in_flight(hip_ctx):
         return out
 
     for a, b in zip(sequence(False), sequence(True)):
-        np.testing.assert_array_equal(_bits(a), _bits(b))
+        np.testing.assert_array_equal(bits(a), bits(b))
     ds.close()

@@ -1,7 +1,8 @@
 """Per-object motion for the temporal history on the GPU: mcrt_scene_motion_snapshot,
 mcrt_render_guides_motion (k_guides_motion), mcrt_temporal_accumulate_motion (k_temporal's MOTION
 form) against tests/motion_truth.py (float64 truth with forward bounds) and
-tests/temporal_motion_ref.py (the numpy restatement, operation for operation).
+tests/temporal_ref.py (the numpy restatement, operation for operation; tests/temporal_motion_ref.py
+is its scene).
 
 The accumulate is compared as tests/test_gpu_temporal.py compares the static one: planes expected
 bit-equal, asserted at rtol 2e-5, atol 1e-7 (the variance: |d| <= 2e-5 mu2 + 1e-7), the number of
@@ -15,26 +16,18 @@ import pytest
 import motion_truth as mt
 import temporal_motion_ref as mr
 import temporal_ref as tr
+from denoise_harness import Installed, bits, compare_planes, pair_a, synth_planes, tm_rmse
 from mcrt import scenes
 from mcrt import types as T
-from mcrt.camera import make_camera, scene_camera
+from mcrt.camera import scene_camera
 from refit_util import translate, with_transforms
 
 pytestmark = pytest.mark.gpu
 
 F = np.float32
-RTOL, ATOL = 2e-5, 1e-7
 FAR = (1000.0, 1000.0, 1000.0)
 SIZES = [(45, 37), (16, 16)]
 SIZE_IDS = ["45x37", "16x16"]
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
-
-
-def _ndiff(a, b):
-    return int((_bits(a) != _bits(b)).sum())
 
 
 def _about(centre, M):
@@ -114,10 +107,10 @@ def test_guides_are_those_of_render_guides_and_no_snapshot_means_no_motion(hip_c
         fb.render_guides_motion(ds, cam, texture_lod=lod)
         got = [fb.read_guides(w) for w in (0, 1)]
         for a, b in zip(got, want):
-            np.testing.assert_array_equal(_bits(a), _bits(b))
+            np.testing.assert_array_equal(bits(a), bits(b))
         assert (want[1][..., 3] > 0).sum() > 50
         for w in (0, 1):
-            assert (_bits(fb.read_motion(w)) == 0).all()
+            assert (bits(fb.read_motion(w)) == 0).all()
     # with a snapshot, and with the shapes moved, the guide planes are still k_guides'
     ds.motion_snapshot()
     _apply(ds, moved, which == "two_level")
@@ -125,7 +118,7 @@ def test_guides_are_those_of_render_guides_and_no_snapshot_means_no_motion(hip_c
     want = [fb.read_guides(w) for w in (0, 1)]
     fb.render_guides_motion(ds, cam)
     for w in (0, 1):
-        np.testing.assert_array_equal(_bits(fb.read_guides(w)), _bits(want[w]))
+        np.testing.assert_array_equal(bits(fb.read_guides(w)), bits(want[w]))
     assert (fb.read_motion(0)[..., 3] == 1).any()
     fb.close()
     ds.close()
@@ -140,8 +133,8 @@ def _check_moved(sc, moved, cam, ids, depth, npl, motion, pnorm, moved_shapes, g
     np.testing.assert_array_equal(flag == 1, is_moved)
     np.testing.assert_array_equal(flag == -1, is_gone)
     still = ~is_moved
-    assert (_bits(motion[still][:, :3]) == 0).all() and (_bits(pnorm[still]) == 0).all()
-    assert (_bits(flag[~is_moved & ~is_gone]) == 0).all()
+    assert (bits(motion[still][:, :3]) == 0).all() and (bits(pnorm[still]) == 0).all()
+    assert (bits(flag[~is_moved & ~is_gone]) == 0).all()
     assert (pnorm[..., 3] == 0).all()
     worst_d = worst_n = 0.0
     for k in moved_shapes:
@@ -159,7 +152,7 @@ def _check_moved(sc, moved, cam, ids, depth, npl, motion, pnorm, moved_shapes, g
         length = np.linalg.norm(pnorm[sel][:, :3].astype(np.float64), axis=-1)
         np.testing.assert_allclose(length, 1.0, atol=8 * mt.U)     # 3 squares, 2 sums, rsqrt, a product: <= 8 roundings
         if np.array_equal(ITp[:3], ITc[:3]):    # a pure translation: the same normal, bit for bit
-            np.testing.assert_array_equal(_bits(pnorm[sel][:, :3]), _bits(npl[sel][:, :3]))
+            np.testing.assert_array_equal(bits(pnorm[sel][:, :3]), bits(npl[sel][:, :3]))
         else:
             want, e_n = mt.truth_normal(npl[..., :3], ITp, ITc)
             en = np.abs(pnorm[..., :3].astype(np.float64) - want).max(-1)
@@ -196,7 +189,7 @@ def test_motion_planes_of_moved_instances(hip_ctx, size):
     ds.motion_snapshot()
     fb.render_guides_motion(ds, cam)
     for w in (0, 1):
-        assert (_bits(fb.read_motion(w)) == 0).all()
+        assert (bits(fb.read_motion(w)) == 0).all()
     fb.close()
     ds.close()
 
@@ -223,19 +216,12 @@ def test_motion_planes_of_a_flat_scene_and_a_changed_mesh_key(hip_ctx, size):
     if W == 45:
         assert counts[4] > 0 and counts[5] > 0
         gone = hit & (ids == 5)
-        assert (_bits(motion[gone]) == _bits(np.array([0, 0, 0, -1], F))).all()
+        assert (bits(motion[gone]) == bits(np.array([0, 0, 0, -1], F))).all()
     fb.close()
     ds.close()
 
 
 # ---- 3. k_temporal's MOTION form against the restatement -------------------------------------------------
-def pair_a(W, H, offset=(0.0, 0.0, 0.0)):
-    o = np.asarray(offset, np.float64)
-    prev = make_camera(tuple(o + (0.0, 1.0, -4.0)), tuple(o + (0.0, 0.6, 0.0)), W, H, fovy=50.0)
-    cur = make_camera(tuple(o + (0.6, 1.1, -3.8)), tuple(o + (0.1, 0.6, 0.0)), W, H, fovy=50.0)
-    return prev, cur
-
-
 _CASES = {}
 
 
@@ -255,69 +241,11 @@ def _case(W, H, offset, seed):
     motion, pnorm = now["motion"].copy(), now["prev_normal"].copy()
     gone = (sid > 0) & (sid != mr.RECT_ID) & (rng.random((H, W)) < 1 / 7)
     motion[gone] = (0.0, 0.0, 0.0, -1.0)
-    ad = np.empty((H, W, 4), F)
-    ad[..., :3] = rng.uniform(0.05, 1.0, (H, W, 3))
-    ad[..., 0][rng.random((H, W)) < 0.1] = 0.0
-    ad[..., 1][rng.random((H, W)) < 0.1] = 5e-4
-    ad[sid == 0, :3] = 0.0
-    ad[..., 3] = depth
-    img = (np.linspace(0.5, 2.0, W)[None, :, None] * 10.0 ** rng.uniform(-0.05, 0.05, (H, W, 4))).astype(F)
-    img[..., 3] = rng.uniform(0, 1, (H, W))
-    hc = rng.uniform(0.3, 2.5, (H, W, 4)).astype(F)
-    wild = rng.random((H, W)) < 0.2
-    hc[wild] = (10.0 ** rng.uniform(-3, 3, (int(wild.sum()), 4))).astype(F)
-    mu1 = rng.uniform(0.2, 3.0, (H, W)).astype(F)
-    mu2 = (mu1 * mu1 + rng.uniform(0.0, 0.5, (H, W)).astype(F)).astype(F)
-    flat = rng.random((H, W)) < 0.15
-    mu2[flat] = (mu1 * mu1)[flat]
-    hm = np.stack([mu1, mu2, rng.integers(1, 41, (H, W)).astype(F), before["depth"]], -1).astype(F)
+    ad, img, hc, hm = synth_planes(rng, sid, depth, before["depth"])
     case = dict(prev=prev, cur=cur, sid=sid, npl=now["normal_plane"], ad=ad, img=img, motion=motion, pnorm=pnorm,
                 hist=(hc, hm, before["normal_plane"]), before_sid=before["sid"])
     _CASES[key] = case
     return case
-
-
-class _Installed:
-    """A frame buffer holding a synthetic image (unit weights), guides, motion planes and history."""
-
-    def __init__(self, ctx, case, history=True, motion=True):
-        import torch
-        from mcrt import lib
-        H, W = case["img"].shape[:2]
-        self.fb = lib.FrameBuffer(ctx, W, H)
-        dev = lambda a: torch.from_numpy(np.ascontiguousarray(a, F).reshape(-1)).cuda()   # noqa: E731
-        self.keep = [dev(case["img"]), torch.ones(H * W, dtype=torch.float32, device="cuda"), dev(case["npl"]),
-                     dev(case["ad"])] + [dev(a) for a in case["hist"]] + [dev(case["motion"]), dev(case["pnorm"])]
-        torch.cuda.synchronize()
-        self.fb.set_accumulation(self.keep[0].data_ptr(), self.keep[1].data_ptr())
-        self.fb.set_guides(self.keep[2].data_ptr(), self.keep[3].data_ptr())
-        if motion:
-            self.fb.set_motion(self.keep[7].data_ptr(), self.keep[8].data_ptr())
-        if history:
-            self.fb.set_temporal_history(self.keep[4].data_ptr(), self.keep[5].data_ptr(), self.keep[6].data_ptr(),
-                                         case["prev"])
-        ctx.sync()
-
-    def planes(self):
-        return [self.fb.read_temporal(w) for w in (T.TEMPORAL_COLOUR, T.TEMPORAL_MOMENTS, T.TEMPORAL_VARIANCE,
-                                                   T.TEMPORAL_NORMAL_PLANE)]
-
-    def close(self):
-        self.fb.close()
-
-
-def _compare(got, ref, what):
-    colour, mom, var, nrm = got
-    rc, rm, rv, rn = ref
-    print(f"{what}: bit-different values: colour {_ndiff(colour, rc)}, moments {_ndiff(mom, rm)}, "
-          f"variance {_ndiff(var, rv)}, normal-plane {_ndiff(nrm, rn)} of {var.size} pixels")
-    assert all(np.isfinite(a).all() for a in got)
-    np.testing.assert_allclose(colour, rc, rtol=RTOL, atol=ATOL, err_msg="colour history")
-    np.testing.assert_allclose(mom, rm, rtol=RTOL, atol=ATOL, err_msg="moments history, N, depth")
-    np.testing.assert_array_equal(_bits(nrm), _bits(rn))
-    bound = 2e-5 * rm[..., 1].astype(np.float64) + 1e-7
-    err = np.abs(var.astype(np.float64) - rv.astype(np.float64))
-    assert (err <= bound).all(), (err.max(), np.max(err / bound))
 
 
 @pytest.mark.parametrize("demod", [True, False], ids=["demodulated", "plain"])
@@ -328,7 +256,7 @@ def test_one_step_matches_the_reference(hip_ctx, size, offset, demod, monkeypatc
     case = _case(W, H, offset, seed=W)
     params = dict(tr.DEFAULTS, demodulate_albedo=demod)
     info = {}
-    rc, rm, rn = mr.accumulate(case["img"], case["npl"], case["ad"], case["cur"], case["hist"] + (case["prev"],),
+    rc, rm, rn = tr.accumulate(case["img"], case["npl"], case["ad"], case["cur"], case["hist"] + (case["prev"],),
                                case["motion"], case["pnorm"], info=info, **params)
     rv = tr.variance(rm, rn, **params)
     flag, taps, hit = case["motion"][..., 3], info["valid_taps"], case["sid"] > 0
@@ -342,11 +270,11 @@ def test_one_step_matches_the_reference(hip_ctx, size, offset, demod, monkeypatc
     assert (static["valid_taps"][flag == 1] < taps[flag == 1]).any()
     for loads in ("eager", "lazy"):            # both load forms of k_temporal: the same bits
         monkeypatch.setenv("MCRT_TEMPORAL_LOADS", loads)
-        inst = _Installed(hip_ctx, case)
+        inst = Installed(hip_ctx, case)
         inst.fb.temporal_accumulate_motion(case["cur"], **params)
         got = inst.planes()
         inst.close()
-        _compare(got, (rc, rm, rv, rn), f"{W}x{H} offset {offset[0]:g} demod {demod} {loads}")
+        compare_planes(got, (rc, rm, rv, rn), f"{W}x{H} offset {offset[0]:g} demod {demod} {loads}")
 
 
 # ---- 4. zero motion -----------------------------------------------------------------------------------------
@@ -359,11 +287,11 @@ def test_installed_zero_motion_is_temporal_accumulate(hip_ctx, size, monkeypatch
     for loads in ("eager", "lazy"):
         monkeypatch.setenv("MCRT_TEMPORAL_LOADS", loads)
         for history in (True, False):
-            a, b = _Installed(hip_ctx, case, history), _Installed(hip_ctx, case, history, motion=False)
+            a, b = Installed(hip_ctx, case, history), Installed(hip_ctx, case, history, motion=False)
             a.fb.temporal_accumulate_motion(case["cur"])
             b.fb.temporal_accumulate(case["cur"])
             for x, y in zip(a.planes(), b.planes()):
-                np.testing.assert_array_equal(_bits(x), _bits(y))
+                np.testing.assert_array_equal(bits(x), bits(y))
             a.close()
             b.close()
 
@@ -372,12 +300,6 @@ def test_installed_zero_motion_is_temporal_accumulate(hip_ctx, size, monkeypatch
 RW, RH = 64, 48
 FRAMES = 8
 MOVER = 1        # mesh A itself, in the middle of the image
-
-
-def _tm_rmse(a, truth, mask):
-    a, truth = a[..., :3].astype(np.float64), truth[..., :3].astype(np.float64)
-    d = (a / (1 + a) - truth / (1 + truth)) ** 2
-    return float(np.sqrt(np.mean(d[mask])))
 
 
 def _pose_at(sc, d):
@@ -439,7 +361,7 @@ def test_a_moving_instance_keeps_its_history_end_to_end(hip_ctx):
     s = _interactive(hip_ctx, sc, cam, False)
     on = s["on_mover"]
     np.testing.assert_array_equal(on, m["on_mover"])
-    e_m, e_s, e_1 = (_tm_rmse(a, s["truth"], on) for a in (m["display"], s["display"], s["single"]))
+    e_m, e_s, e_1 = (tm_rmse(a, s["truth"], on) for a in (m["display"], s["display"], s["single"]))
     n_m, n_s = int((m["moments"][..., 2][on] >= 4).sum()), int((s["moments"][..., 2][on] >= 4).sum())
     print(f"mover: {on.sum()} pixels; tone-mapped RMSE temporal with motion + filter {e_m:.4f}, static temporal + filter "
           f"{e_s:.4f}, single-frame guided {e_1:.4f}; pixels with N >= 4: with motion {n_m} ({n_m / on.sum():.0%}), "
@@ -460,7 +382,7 @@ def test_a_moving_instance_keeps_its_history_end_to_end(hip_ctx):
     far = ~g2
     assert far.sum() > 0.5 * RW * RH
     for k in ("colour", "moments"):
-        np.testing.assert_array_equal(_bits(m[k])[far], _bits(s[k])[far])
+        np.testing.assert_array_equal(bits(m[k])[far], bits(s[k])[far])
 
 
 # ---- 6. nothing existing moves ------------------------------------------------------------------------
@@ -500,7 +422,7 @@ def test_existing_outputs_do_not_notice_the_motion_calls(hip_ctx):
         return out
 
     for a, b in zip(sequence(True), sequence(False)):
-        np.testing.assert_array_equal(_bits(a), _bits(b))
+        np.testing.assert_array_equal(bits(a), bits(b))
 
 
 # ---- 7. status codes ------------------------------------------------------------------------------------
@@ -564,7 +486,7 @@ def test_status_codes(hip_ctx):
     fb.render_guides_motion(ds, scam)
     buf = np.zeros((H, W), F)
     assert L.mcrt_framebuffer_read_motion(fb.h, 0, buf.ctypes.data, buf.nbytes, None) == INVALID   # too small
-    inst = _Installed(hip_ctx, case)
+    inst = Installed(hip_ctx, case)
     assert L.mcrt_temporal_accumulate_motion(inst.fb.h, camp, ctypes.byref(good)) == OK
     inst.fb.set_guides(inst.keep[2].data_ptr(), inst.keep[3].data_ptr())
     assert L.mcrt_temporal_accumulate_motion(inst.fb.h, camp, ctypes.byref(good)) == NOT_READY
@@ -627,4 +549,4 @@ def test_ordering_with_frames_in_flight(hip_ctx):
     seq = sequence(False)
     assert (seq[5][..., 3] == 1).any()
     for a, b in zip(seq, sequence(True)):
-        np.testing.assert_array_equal(_bits(a), _bits(b))
+        np.testing.assert_array_equal(bits(a), bits(b))

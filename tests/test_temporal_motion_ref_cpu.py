@@ -1,7 +1,7 @@
-"""Properties of the temporal history rule with per-object motion (tests/temporal_motion_ref.py, the
-numpy restatement of k_temporal's MOTION form) on the analytic scene with one moving rectangle:
-what a slide within its own plane, a translation out of it and a turn keep, what the static rule
-(tests/temporal_ref.py) does with the same input, and what restarts.  Static camera, 45x37, at the
+"""Properties of the temporal history rule with per-object motion (tests/temporal_ref.py's numpy
+restatement of k_temporal given motion planes) on tests/temporal_motion_ref.py's analytic scene
+with one moving rectangle: what a slide within its own plane, a translation out of it and a turn keep, what the static rule
+(no motion planes) does with the same input, and what restarts.  Static camera, 45x37, at the
 origin and with everything 1000 units away.  Runs without a GPU.
 
 "Interior" below is the set of current rectangle pixels whose four motion-reprojected history taps
@@ -65,7 +65,7 @@ def frames(move, offset, seed=1):
 
 def run_motion(cam, now, hist, img, **kw):
     info = {}
-    out = mr.accumulate(img, now["normal_plane"], albedo_depth(now), cam, hist, now["motion"], now["prev_normal"],
+    out = tr.accumulate(img, now["normal_plane"], albedo_depth(now), cam, hist, now["motion"], now["prev_normal"],
                         info=info, **dict(PARAMS, **kw))
     return out, info
 
@@ -99,13 +99,13 @@ def test_zero_motion_is_the_static_rule_bit_for_bit(offset, demod):
     zero = np.zeros((H, W, 4), F)
     params = dict(PARAMS, demodulate_albedo=demod)
     info = {}
-    got = mr.accumulate(img, now["normal_plane"], ad, cur, hist, zero, zero, info=info, **params)
+    got = tr.accumulate(img, now["normal_plane"], ad, cur, hist, zero, zero, info=info, **params)
     want = tr.accumulate(img, now["normal_plane"], ad, cur, hist, **params)
     assert (info["valid_taps"] == 4).sum() > 500 and (info["valid_taps"] == 0).sum() > 20
     for a, b in zip(got, want):
         np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
     # without history, too
-    for a, b in zip(mr.accumulate(img, now["normal_plane"], ad, cur, None, zero, zero, **params),
+    for a, b in zip(tr.accumulate(img, now["normal_plane"], ad, cur, None, zero, zero, **params),
                     tr.accumulate(img, now["normal_plane"], ad, cur, None, **params)):
         np.testing.assert_array_equal(a.view(np.uint32), b.view(np.uint32))
 

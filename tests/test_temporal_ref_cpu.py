@@ -6,19 +6,13 @@ import numpy as np
 import pytest
 
 import temporal_ref as tr
+from denoise_harness import pair_a
 from mcrt.camera import make_camera
 
 F = np.float32
 SIZES = [(45, 37), (16, 16)]
 MIN_FULL = {(45, 37): 1000, (16, 16): 100}
 MIN_NONE = {(45, 37): 20, (16, 16): 3}
-
-
-def pair_a(W, H, offset=(0.0, 0.0, 0.0)):
-    o = np.asarray(offset, np.float64)
-    prev = make_camera(tuple(o + (0.0, 1.0, -4.0)), tuple(o + (0.0, 0.6, 0.0)), W, H, fovy=50.0)
-    cur = make_camera(tuple(o + (0.6, 1.1, -3.8)), tuple(o + (0.1, 0.6, 0.0)), W, H, fovy=50.0)
-    return prev, cur
 
 
 def guides(cam, offset, rng):
