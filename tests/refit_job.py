@@ -16,7 +16,7 @@ sys.path.insert(0, os.path.join(ROOT, "monte-carlo-raytracer_amd"))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
-from refit_util import FORCED_CASES, forced_case, trace  # noqa: E402
+from refit_util import FORCED_CASES, case_opts, forced_case, trace  # noqa: E402
 
 
 def main(out_path):
@@ -28,7 +28,7 @@ def main(out_path):
     res = {}
     for name in FORCED_CASES:
         sc, moved, rays = forced_case(name)
-        ds = lib.DeviceScene(ctx, sc, force_2level=True)
+        ds = lib.DeviceScene(ctx, sc, force_2level=True, **case_opts(name))
         before = ds.records()
         ds.update_transforms(moved.shapes)
         after = ds.records()
@@ -39,7 +39,7 @@ def main(out_path):
         res[f"{name}_path"] = np.array(ds.update_info()["path"])
         if rays:
             r = tl_rays(moved, 20000)
-            fresh = lib.DeviceScene(ctx, moved, force_2level=True)
+            fresh = lib.DeviceScene(ctx, moved, force_2level=True, **case_opts(name))
             for tag, d in (("upd", ds), ("fresh", fresh)):
                 res[f"{name}_{tag}_closest"] = trace(d, r).view(np.uint8)
                 res[f"{name}_{tag}_any"] = trace(d, r, True)

@@ -58,6 +58,24 @@ def power_of_two_line(n):
     return [translate((float(2.0 ** i), 0.0, 0.0)) for i in range(n)]
 
 
+def lattice_line(n_min, bins):
+    """(built scene, moved scene) of at least n_min instances of one unit box (centre 0).  Moved, box i
+    stands at (x_i, 0, 0) with x_i over build_opts.lattice_spots: the centroids of the world boxes
+    then lie exactly on, and one float below, the planes k * (E / bins) that the top level's root
+    prices with `bins` bins (centroid minimum 0, extent E, y and z extents 0), so a plane that is an
+    ulp off changes the partition.  tests/test_build_opts_cpu.py checks that premise on the host."""
+    from build_opts import lattice_spots
+    spots = lattice_spots(bins, TOP_LATTICE_EXTENT)
+    x = np.repeat(spots, -(-n_min // len(spots)))
+    b = scenes.SceneBuilder(f"lattice_line_{len(x)}_{bins}")
+    m = b.add_material(kd=(0.7, 0.7, 0.7))
+    box = b.add_mesh(*scenes.box((-0.5, -0.5, -0.5), (0.5, 0.5, 0.5)), m, transform=grid_place(0))
+    for i in range(1, len(x)):
+        b.add_instance(box, grid_place(i))
+    sc = b.build()
+    return sc, with_transforms(sc, [translate((float(v), 0.0, 0.0)) for v in x])
+
+
 def spill_blocks(depth):
     """Spill blocks of 16 entries the traversal needs for a tree of this depth (finish_accel)."""
     return (depth + 2 + 15) // 16
@@ -79,11 +97,32 @@ def normalised(rec, top_records):
 # the smallest top levels, one-wave requests (<= 256 shapes) on both sides of the wave size, several
 # large requests and level passes (5000); then the degenerate arrangements.
 RECORD_SIZES = (1, 2, 3, 64, 65, 257, 300, 5000)
-FORCED_CASES = tuple(f"n{n}" for n in RECORD_SIZES) + ("collapsed300", "one_axis", "pow2")
+# Build options (cost / bins / SAH switch) the structure must remember for its refits, as
+# "<case>-<tag>": one large request and one wave (n300), several levels of large requests (n5000),
+# the degenerate line at the smallest bin count.
+OPTION_TAGS = {"b2": {"bins": 2}, "b5": {"bins": 5}, "b63": {"bins": 63}, "mid": {"sah": False},
+               "c1e6": {"cost": 1e6}, "cfltmax": {"cost": float(np.finfo(np.float32).max)}}
+OPTION_CASES = tuple(f"{c}-{t}" for c in ("n300", "n5000") for t in ("b5", "b63", "mid", "c1e6", "cfltmax")) + ("pow2-b2",)
+# "lattice<n>-b<bins>": at least n unit boxes moved onto the planes the top level's root prices
+# (lattice_line): one-wave requests and a large one, at bin counts whose step is inexact
+OPTION_CASES += ("lattice100-b5", "lattice100-b63", "lattice300-b5", "lattice300-b63")
+TOP_LATTICE_EXTENT = 24.3   # float32 E * (1 / bins) != E / bins for 3, 5, 7, 33, 63 bins; E + 0.5 < 32
+FORCED_CASES = tuple(f"n{n}" for n in RECORD_SIZES) + ("collapsed300", "one_axis", "pow2") + OPTION_CASES
+
+
+def case_opts(name):
+    """The build options of a forced-path case (none but for OPTION_CASES)."""
+    tag = name.partition("-")[2]
+    return dict(OPTION_TAGS[tag]) if tag else {}
 
 
 def forced_case(name):
     """(built scene, moved scene, trace rays too) of a forced-path case."""
+    if name.startswith("lattice"):
+        return lattice_line(int(name[7:].partition("-")[0]), case_opts(name)["bins"]) + (False,)
+    if "-" in name:
+        sc, moved, _ = forced_case(name.partition("-")[0])
+        return sc, moved, False
     if name.startswith("n"):
         n = int(name[1:])
         sc = synthetic(n)

@@ -2,7 +2,8 @@
 // partition (ranks instead of the two-pointer loop), the tabulated _mm_rcp_ps rule and the
 // split arithmetic of mcrt_sah.h, run top-down on the CPU and compared record for record with
 // the host build (mcrt_bvh.cpp, the RadeonRays Bvh2 restatement).  Exit 0 = identical.
-//   usage: sah_emul [n] [seed] [kind]   kind 0 random soup, 1 grid (ties), 2 degenerate clusters
+//   usage: sah_emul [n] [seed] [kind] [bins cost sah]   kind 0 random soup, 1 grid (ties), 2 degenerate
+//   clusters; bins cost sah: the build options of both sides (default 64 10 1)
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -116,6 +117,10 @@ int main(int argc, char** argv) {
     const size_t n = argc > 1 ? std::strtoull(argv[1], nullptr, 10) : 20000;
     const unsigned seed = argc > 2 ? (unsigned)std::atoi(argv[2]) : 1;
     const int kind = argc > 3 ? std::atoi(argv[3]) : 0;
+    const int bins = argc > 6 ? std::atoi(argv[4]) : 64;
+    const float cost = argc > 6 ? std::strtof(argv[5], nullptr) : 10.0f;
+    const bool sahOn = argc > 6 ? std::atoi(argv[6]) != 0 : true;
+    if (bins < 2) { std::puts("bins < 2"); return 2; }
     std::mt19937 g(seed);
     std::uniform_real_distribution<float> U(-10.0f, 10.0f), S(-0.05f, 0.05f);
     std::vector<float> tri(9 * n);
@@ -136,10 +141,10 @@ int main(int argc, char** argv) {
     std::vector<int32_t> so(n), po(n);
     for (size_t k = 0; k < n; ++k) { so[k] = (int32_t)(k % 3); po[k] = (int32_t)k; }
     BvhOut ref;
-    if (!build_bvh(tri.data(), so.data(), po.data(), n, 10.0f, 64, true, 4, ref)) { std::puts("host build failed"); return 2; }
+    if (!build_bvh(tri.data(), so.data(), po.data(), n, cost, bins, sahOn, 4, ref)) { std::puts("host build failed"); return 2; }
     const HostRcp& R = host_rcp_table();
     if (!R.ok) { std::puts("host rcp/dp rule check failed"); return 3; }
-    Emu e{tri.data(), n, {}, {}, {}, {}, {}, &R, 64, 10.0f, true};
+    Emu e{tri.data(), n, {}, {}, {}, {}, {}, &R, (uint32_t)bins, cost, sahOn};
     e.amin.resize(n); e.amax.resize(n); e.cen.resize(n); e.refs.resize(n); e.nodes.assign(16 * (2 * n - 1), 0.0f);
     V4 smin{INFINITY, INFINITY, INFINITY, INFINITY}, smax{-INFINITY, -INFINITY, -INFINITY, -INFINITY}, cmin = smin, cmax = smax;
     for (size_t k = 0; k < n; ++k) {
@@ -163,8 +168,8 @@ int main(int argc, char** argv) {
     size_t bad = 0, first = (size_t)-1;
     for (size_t i = 0; i < 16 * (2 * n - 1); ++i)
         if (!same(e.nodes[i], ref.nodes[i])) { if (!bad) first = i / 16; ++bad; }
-    std::printf("n=%zu kind=%d rcp_bits=%d depth host=%d emu=%d mismatched floats=%zu first node=%lld\n", n, kind,
-                R.bits, ref.depth, e.depth, bad, (long long)first);
+    std::printf("n=%zu kind=%d bins=%d cost=%g sah=%d rcp_bits=%d depth host=%d emu=%d mismatched floats=%zu first node=%lld\n", n, kind,
+                bins, (double)cost, (int)sahOn, R.bits, ref.depth, e.depth, bad, (long long)first);
     free_bvh(ref);
     return bad == 0 && e.depth == ref.depth ? 0 : 1;
 }

@@ -47,7 +47,8 @@ def _compare_tree(ref_nodes, rbase, mine, mbase, count):
 
 
 def compare_with_reference(scene, **opts):
-    ref = O.ref_bvh2l(scene, world_to_local=opts.get("world_to_local"))
+    """opts: world_to_local and the build options cost / bins / sah, given to both builders."""
+    ref = O.ref_bvh2l(scene, **{k: opts[k] for k in ("world_to_local", "cost", "bins", "sah") if k in opts})
     rec, info = lib.build_host_records(scene, force_2level=True, **opts)
     assert info["two_level"] == 1
     assert rec.shape[0] == ref["nodes"].shape[0]

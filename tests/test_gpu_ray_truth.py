@@ -73,11 +73,13 @@ def _with_env(env, fn):
                 os.environ[k] = v
 
 
-def _build(ctx, scene, layout, check_records=True):
+def _build(ctx, scene, layout, check_records=True, opts=None):
     """The DeviceScene of `layout`, built inside its environment (the variables are read at build
-    time), with the layout's own evidence that the intended records are in use."""
+    time), with the layout's own evidence that the intended records are in use.  opts: further
+    DeviceScene options (tests/test_gpu_build_opts.py: cost / bins / sah)."""
     from mcrt import lib
-    env, opts, two_level = LAYOUTS[layout]
+    env, lopts, two_level = LAYOUTS[layout]
+    opts = dict(lopts, **(opts or {}))
     ds = _with_env(env, lambda: lib.DeviceScene(ctx, scene, **opts))
     info = ds.info()
     if layout == "compact":
@@ -129,19 +131,33 @@ class Case:
                   f"{int((~tr.closest_det[m]).sum())} any {int((~tr.any_det[m]).sum())}")
 
 
+_CASES = {"edge0": lambda: Case(rt.edge_scene()),
+          "edge1000": lambda: Case(rt.edge_scene((1000.0, 1000.0, 1000.0))),
+          "instanced": lambda: Case(rt.instanced_edge_scene())}
+_shared = {}
+
+
+def shared_case(name):
+    """The Case `name`, made once per process: its truths do not depend on the tree, so every test
+    module that walks these scenes (tests/test_gpu_build_opts.py too) judges against the same ones."""
+    if name not in _shared:
+        _shared[name] = _CASES[name]()
+    return _shared[name]
+
+
 @pytest.fixture(scope="module")
 def edge0():
-    return Case(rt.edge_scene())
+    return shared_case("edge0")
 
 
 @pytest.fixture(scope="module")
 def edge1000():
-    return Case(rt.edge_scene((1000.0, 1000.0, 1000.0)))
+    return shared_case("edge1000")
 
 
 @pytest.fixture(scope="module")
 def instanced():
-    return Case(rt.instanced_edge_scene())
+    return shared_case("instanced")
 
 
 def _judge_launch(ctx, ds, case, tr, index, what, rays=None):

@@ -19,7 +19,7 @@ from clref_job import tl_rays
 from mcrt import scenes
 from mcrt import types as T
 from mcrt.camera import scene_camera
-from refit_util import (FORCED_CASES, forced_case, normalised, similarity_transforms, spill_blocks,
+from refit_util import (FORCED_CASES, case_opts, forced_case, normalised, similarity_transforms, spill_blocks,
                         synthetic, trace, translate, with_transforms)
 
 pytestmark = pytest.mark.gpu
@@ -52,7 +52,7 @@ def truth():
     def get(name):
         if name not in cache:
             _, moved, _ = forced_case(name)
-            cache[name] = lib.build_host_records(moved, force_2level=True)
+            cache[name] = lib.build_host_records(moved, force_2level=True, **case_opts(name))
         return cache[name]
     return get
 

@@ -10,37 +10,12 @@ import time
 import numpy as np
 import pytest
 
+from build_opts import _soup
 from helpers import bunny_scene, rr_cornell_scene
 from mcrt import scenes
 from mcrt.camera import scene_camera
 
 pytestmark = pytest.mark.gpu
-
-
-def _soup(kind, n, seed):
-    """Synthetic stress cases: 'grid' (many equal centroid coordinates -> median fallbacks,
-    ties in the bins), 'clusters' (identical triangles: zero centroid extent), 'coplanar'."""
-    rng = np.random.default_rng(seed)
-    b = scenes.SceneBuilder(kind)
-    m = b.add_material(kd=(0.5, 0.5, 0.5))
-    k = np.arange(n)
-    if kind == "grid":
-        c = np.stack([k % 97, (k // 97) % 13 * 0.5, np.zeros(n)], 1)
-    elif kind == "clusters":
-        c = np.where((k % 7 < 3)[:, None], np.stack([k % 7, np.ones(n), 2 * np.ones(n)], 1),
-                     rng.uniform(-10, 10, (n, 3)))
-    else:
-        c = np.stack([rng.uniform(-10, 10, n), rng.uniform(-10, 10, n), np.zeros(n)], 1)
-    off = rng.uniform(-0.05, 0.05, (n, 3, 3))
-    if kind == "coplanar":
-        off[..., 2] = 0.0
-    if kind == "clusters":
-        off[k % 7 < 3] = 0.01 * np.eye(3)
-    P = (c[:, None, :] + off).reshape(-1, 3)
-    tris = np.arange(3 * n).reshape(-1, 3)
-    b.add_mesh(P, np.tile([0.0, 0.0, 1.0], (3 * n, 1)), np.zeros((3 * n, 2)), tris, m)
-    b.add_point_light((0, 0, 20), (10, 10, 10))
-    return b.build()
 
 
 def _same_records(a, b):

@@ -20,9 +20,18 @@ def emul():
     return os.path.join(HERE, "sah_emul", "sah_emul")
 
 
+def run_emul(emul, n, seed, kind, t=None):
+    """t: an option tuple (bins, cost, sah) for both the host build and the emulation (default: the
+    reference's 64 bins, cost 10, SAH on; tests/test_build_opts_cpu.py runs the grid)."""
+    args = [emul, str(n), str(seed), str(kind)]
+    if t is not None:
+        args += [str(t[0]), repr(float(t[1])), "1" if t[2] else "0"]
+    r = subprocess.run(args, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "mismatched floats=0" in r.stdout
+
+
 @pytest.mark.parametrize("n,seed,kind", [(1, 1, 0), (2, 3, 0), (9, 2, 0), (1000, 7, 1), (5000, 9, 2),
                                          (20000, 1, 0), (20000, 1, 1), (20000, 1, 2), (200000, 5, 0)])
 def test_device_algorithm_matches_host_build(emul, n, seed, kind):
-    r = subprocess.run([emul, str(n), str(seed), str(kind)], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "mismatched floats=0" in r.stdout
+    run_emul(emul, n, seed, kind)
