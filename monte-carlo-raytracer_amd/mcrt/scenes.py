@@ -678,6 +678,140 @@ def lod_test_scene(seed=0):
     return b.build()
 
 
+ZOO_SIZES = ((1, 1), (2, 2), (3, 5), (5, 3), (7, 64), (64, 1), (100, 60), (64, 64))   # (width, height)
+ZOO_WRAPS = {False: (0, 1, 0, 1, 3, 2, 2, 3), True: (2, 3, 1, 0, 2, 0, 3, 1)}   # per size: plain, mip-mapped
+ZOO_VIEW = (96, 64)   # the frame size the layout below is laid out for (12 x 8 tiles of 8 x 8 pixels)
+ZOO_CAMERA_Z = -4.0
+ZOO_SPAN = (-1.75, 2.5)
+
+
+def texture_zoo_scene(seed=0):
+    """Texture and material-slot parity scene: flat quads in the plane z = 0 that tile a 96 x 64
+    view exactly (quad edges lie half a pixel off the camera rays, which pass through pixel
+    corners), a back wall (shape 0, untextured) and two lights.
+
+    Textures: every size of ZOO_SIZES with per-texel random RGBA, once plain and once with its mip
+    chain, wrap modes per ZOO_WRAPS (each mode on a power-of-two and on another size in both sets).
+    Pixel rows (y up, row 0 at the bottom):
+      0-15   one 24 x 16 'span' quad per wrap mode, uv over ZOO_SPAN in both axes, plain textures
+      16-31  the same on mip-mapped textures
+      32-47  48 edge strips, 2 x 16 pixels: per wrap mode six whose vertex u is one constant
+             (0, 1, -1, 2, 0.5 / width, 1 - ulp) and six whose v is (0.5 / height) -- a singular uv
+             mapping on purpose -- the other coordinate running over [0.03, 0.97]
+      48-63  ten 8 x 16 quads, one per material slot and special case, and a 16 x 16 block of
+             4 x 4 quads cycling through materials (several materials per 8 x 8 tile), more than
+             one uv unit per pixel (the last mip level)
+    `scene.zoo` describes the content for the tests: texture ids by (width, height, mips), materials
+    by name, and per shape its kind."""
+    rng = np.random.default_rng(SEED_BASE + 300 + seed)
+    b = SceneBuilder("tex_zoo")
+    W, H = ZOO_VIEW
+    th = math.tan(math.radians(45.0) / 2.0) * abs(ZOO_CAMERA_Z)
+    tw = th * W / H
+    info = {"textures": {}, "materials": {}, "shapes": {}}
+
+    def world(px, py):
+        return ((px - 0.5) / W * 2.0 - 1.0) * tw, ((py - 0.5) / H * 2.0 - 1.0) * th
+
+    def quad(px0, py0, px1, py1, uv00, uv10, uv11, uv01, mat, kind):
+        """Pixels [px0, px1) x [py0, py1), uv per corner (x0y0, x1y0, x1y1, x0y1), facing the camera."""
+        (x0, y0), (x1, y1) = world(px0, py0), world(px1, py1)
+        P = [(x0, y0, 0.0), (x1, y0, 0.0), (x1, y1, 0.0), (x0, y1, 0.0)]
+        sid = b.add_mesh(P, np.tile([0.0, 0.0, -1.0], (4, 1)), [uv00, uv10, uv11, uv01], [[0, 2, 1], [0, 3, 2]], mat)
+        info["shapes"][sid] = kind
+        return sid
+
+    # back wall: shape 0, so every textured shape has a non-zero id
+    wall = b.add_material(kd=(0.6, 0.6, 0.6), ks=(0, 0, 0))
+    b.add_mesh(*grid((-1.5 * tw, -1.5 * th, 1.0), (3 * tw, 0, 0), (0, 3 * th, 0), 1, 1, flip=True), wall)
+    info["shapes"][0] = "wall"
+
+    tex = info["textures"]
+    for mips in (False, True):
+        for (w, h), wrap in zip(ZOO_SIZES, ZOO_WRAPS[mips]):
+            img = rng.integers(0, 256, size=(h, w, 4), dtype=np.uint8)
+            img[..., 3] = rng.integers(96, 256, size=(h, w), dtype=np.uint8)   # alpha scales the opacity
+            if (w, h, mips) in ((2, 2, False), (1, 1, True)):     # the ior textures: eta in [0.5, 1]
+                img[..., 0] = rng.integers(128, 256, size=(h, w), dtype=np.uint8)
+            if (w, h, mips) == (64, 1, False):                    # glossy: black regions
+                img[:, :24, :3] = 0
+            if (w, h, mips) == (64, 64, False):                   # opacity: reaches 0
+                img[16:40, 8:40, :3] = 0
+            if (w, h, mips) == (2, 2, True):                      # normal map: keep the normal's z up
+                img[..., 2] = rng.integers(200, 256, size=(h, w), dtype=np.uint8)
+            tex[(w, h, mips)] = b.add_texture(img, wrap=wrap, mips=mips)
+    by_mode = {mips: {wr: [s for s, x in zip(ZOO_SIZES, ZOO_WRAPS[mips]) if x == wr] for wr in range(4)}
+               for mips in (False, True)}
+    pot = lambda s: s[0] & (s[0] - 1) == 0 and s[1] & (s[1] - 1) == 0   # noqa: E731
+    mats = info["materials"]
+
+    def diffuse_mat(key):
+        name = "diffuse_%dx%d%s" % (key[0], key[1], "_mips" if key[2] else "")
+        if name not in mats:
+            mats[name] = b.add_material(kd=(0.9, 0.8, 0.7), ks=(0.1, 0.1, 0.1), roughness=0.3, diffuseTexId=tex[key])
+        return mats[name]
+
+    # rows 0-31: span quads, one per wrap mode; plain then mip-mapped, the non-power-of-two sizes
+    lo, hi = ZOO_SPAN
+    for row, mips in enumerate((False, True)):
+        for wr in range(4):
+            size = [s for s in by_mode[mips][wr] if not pot(s)][0]
+            quad(24 * wr, 16 * row, 24 * wr + 24, 16 * row + 16, (lo, lo), (hi, lo), (hi, hi), (lo, hi),
+                 diffuse_mat(size + (mips,)), ("span", wr, mips))
+    # rows 32-47: edge strips.  u strips on the plain non-power-of-two texture of the mode, v strips
+    # on the mip-mapped one
+    one_m = float(np.nextafter(np.float32(1.0), np.float32(0.0)))
+    x = 0
+    for wr in range(4):
+        for axis, mips in ((0, False), (1, True)):
+            size = [s for s in by_mode[mips][wr] if not pot(s)][0]
+            m = diffuse_mat(size + (mips,))
+            half = float(np.float32(0.5) / np.float32(size[axis]))
+            for c in (0.0, 1.0, -1.0, 2.0, half, one_m):
+                a, z = 0.03, 0.97
+                uvs = [(c, a), (c, a), (c, z), (c, z)] if axis == 0 else [(a, c), (a, c), (z, c), (z, c)]
+                quad(x, 32, x + 2, 48, *uvs, m, ("strip", wr, axis, c, mips))
+                x += 2
+    # rows 48-63: one material per slot, the special cases, then the block of small quads
+    T_ = lambda w, h, mips=False: tex[(w, h, mips)]   # noqa: E731
+    slot = [
+        ("diffuse", dict(kd=(0.9, 0.9, 0.9), ks=(0.1, 0.1, 0.1), diffuseTexId=T_(1, 1))),
+        ("normal", dict(kd=(0.7, 0.7, 0.7), ks=(0.2, 0.2, 0.2), roughness=0.2, normalMapId=T_(2, 2, True))),
+        ("glossy", dict(kd=(0, 0, 0), ks=(0.8, 0.8, 0.8), roughness=0.25, glossyTexId=T_(64, 1))),
+        ("specReflection", dict(kd=(0.2, 0.2, 0.2), ks=(0, 0, 0), kr=(0.8, 0.8, 0.8), specReflectionTexId=T_(3, 5))),
+        ("transmission", dict(kd=(0.1, 0.1, 0.1), ks=(0.1, 0.1, 0.1), kt=(0.9, 0.9, 0.9, 0.0), eta=1.33,
+                              transmissionTexId=T_(5, 3))),
+        ("opacity", dict(kd=(0.6, 0.6, 0.6), ks=(0.2, 0.2, 0.2), opacity=(0.9, 0.8, 0.7), opacityTexId=T_(64, 64))),
+        ("roughness", dict(kd=(0.2, 0.2, 0.2), ks=(0.7, 0.7, 0.7), roughnessTexId=T_(100, 60))),
+        ("ior", dict(kd=(0, 0, 0), ks=(0.1, 0.1, 0.1), kt=(0.9, 0.9, 0.9, 1.0), roughness=0.2, iorTexId=T_(2, 2))),
+        ("all", dict(kd=(0.8, 0.8, 0.8), ks=(0.5, 0.5, 0.5), kr=(0.3, 0.3, 0.3), kt=(0.5, 0.5, 0.5, 1.0),
+                     opacity=(1.0, 0.9, 0.8), normalMapId=T_(2, 2, True), diffuseTexId=T_(64, 64, True),
+                     glossyTexId=T_(64, 1), specReflectionTexId=T_(3, 5), transmissionTexId=T_(5, 3),
+                     opacityTexId=T_(7, 64, True), roughnessTexId=T_(100, 60), iorTexId=T_(1, 1, True))),
+        # shading black (kd = ks = 0) while hasMaterialNonDeltaComponents sees the texture itself
+        ("diffuse_kd0", dict(kd=(0, 0, 0), ks=(0, 0, 0), kr=(0.5, 0.5, 0.5), diffuseTexId=T_(64, 64))),
+    ]
+    for i, (name, kw) in enumerate(slot):
+        mats[name] = b.add_material(**kw)
+        quad(8 * i, 48, 8 * i + 8, 64, (0.1, 0.1), (0.9, 0.1), (0.9, 0.9), (0.1, 0.9), mats[name], ("slot", name))
+    cyc = [mats[n] for n in ("diffuse_kd0", "glossy", "opacity", "all", "diffuse", "roughness", "ior")]
+    cyc += [diffuse_mat(key) for key in ((2, 2, False), (64, 1, True), (1, 1, True), (2, 2, True))]
+    k = 0
+    for by in range(48, 64, 4):
+        for bx in range(80, 96, 4):
+            quad(bx, by, bx + 4, by + 4, (-1.5, -1.2), (3.5, -1.2), (3.5, 3.4), (-1.5, 3.4), cyc[k % len(cyc)], ("small", k))
+            k += 1
+    # lights: behind the camera, shining onto the quads
+    lm = b.add_material(kd=(0.8, 0.8, 0.8), ks=(0, 0, 0))
+    ls = b.add_mesh(*grid((-1.0, 0.5, ZOO_CAMERA_Z - 1.0), (2, 0, 0), (0, 1.5, 0), 1, 1), lm)
+    info["shapes"][ls] = "light"
+    b.add_directional_light((0.25, -0.35, 1.0), (3.0, 3.0, 3.0))
+    b.add_mesh_light(ls, (14.0, 12.0, 10.0))
+    sc = b.build()
+    sc.zoo = info
+    return sc
+
+
 def san_miguel_proxy(tris=10_000_000, seed=4, tex_size=512):
     """San-Miguel proxy (configs 4/5 and the headline metric): courtyard with arcades,
     tables, ~70 % of the triangles in foliage quads with alpha cut-out leaves, >= 64
@@ -866,4 +1000,5 @@ CAMERAS = {
     "instanced_proxy": ((0.0, 9.0, -17.0), (0.0, 0.5, 0.0), 45.0),
     "instances_test": ((0.0, 5.0, -13.0), (0.0, 1.0, 0.0), 45.0),
     "lod_test": ((0.0, 2.0, -9.0), (0.0, 1.0, 10.0), 45.0),
+    "tex_zoo": ((0.0, 0.0, ZOO_CAMERA_Z), (0.0, 0.0, 0.0), 45.0),
 }

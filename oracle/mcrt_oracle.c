@@ -1448,8 +1448,9 @@ void orc_brute_any(orc_scene* s, const mcrt_ray* rays, int n, int32_t* hits) {
 /* Textures: KRN/textures.cl:70-125 (bilinear, always; readTexture2Df :204-209) */
 /* ======================================================================= */
 typedef struct { float x, y, z, w; } f4;
-static f4 readTex(const orc_scene* s, int texId, v2 uv) {
+static f4 readTexIdx(const orc_scene* s, int texId, v2 uv, int32_t* idx /* NULL or x0, y0, x1, y1 (-1: border) */) {
     const mcrt_texture_desc* tex = &s->d.textures[texId];
+    if (idx) idx[0] = idx[1] = idx[2] = idx[3] = -1;
     int w = tex->width, h = tex->height;
     uv.x -= 1.0f / (float)w * 0.5f;
     uv.y -= 1.0f / (float)h * 0.5f;
@@ -1474,6 +1475,7 @@ static f4 readTex(const orc_scene* s, int texId, v2 uv) {
     y1 = y1 < 0 ? 0 : (y1 > h - 1 ? h - 1 : y1);
     float tx = uv.x * (float)w - floorf(uv.x * (float)w);
     float ty = uv.y * (float)h - floorf(uv.y * (float)h);
+    if (idx) { idx[0] = x0; idx[1] = y0; idx[2] = x1; idx[3] = y1; }
     const uint8_t* base = s->d.tex_data + tex->memOffset;
     const uint8_t* p00 = base + 4 * (x0 + y0 * w);
     const uint8_t* p10 = base + 4 * (x1 + y0 * w);
@@ -1489,6 +1491,7 @@ static f4 readTex(const orc_scene* s, int texId, v2 uv) {
     f4 o = {r[0], r[1], r[2], r[3]};
     return o;
 }
+static f4 readTex(const orc_scene* s, int texId, v2 uv) { return readTexIdx(s, texId, uv, NULL); }
 
 /* KRN/materials.cl:76-91 */
 static void getUberProps(const orc_scene* s, int mi, const Interaction* si, UberProps* p) {
@@ -2173,6 +2176,32 @@ static int hasMaterialNonDeltaComponents(const orc_scene* s, int mi, const Inter
     if (m->uber_glossyTexId != -1) { f4 t = readTex(s, m->uber_glossyTexId, si->uv); Ks = V3(t.x, t.y, t.z); }
     if (m->uber_opacityTexId != -1) { f4 t = readTex(s, m->uber_opacityTexId, si->uv); op = V3(t.x, t.y, t.z); }
     return !isBlack(vmul(Kd, op)) || !isBlack(vmul(Ks, op));
+}
+
+/* Unit-level wrappers of the texture read and of the material functions built on it
+ * (tests/test_tex_ref_cpu.py): n uvs on one texture / one material. */
+void orc_read_tex(const orc_scene* s, int texId, int n, const float* uv, float* out, int32_t* idx) {
+    for (int i = 0; i < n; ++i) {
+        v2 q = {uv[2 * i], uv[2 * i + 1]};
+        f4 t = readTexIdx(s, texId, q, idx ? idx + 4 * i : NULL);
+        out[4 * i] = t.x; out[4 * i + 1] = t.y; out[4 * i + 2] = t.z; out[4 * i + 3] = t.w;
+    }
+}
+/* out: ORC_UBER_FLOATS per uv = Kd[3] Ks[3] Kr[3] Kt[4] opacity[3] alpha[2] eta, then
+ * hasMaterialNonDeltaComponents as 0 / 1 */
+void orc_uber_props(const orc_scene* s, int materialIdx, int n, const float* uv, float* out) {
+    for (int i = 0; i < n; ++i) {
+        Interaction si = identityFrame();
+        si.uv.x = uv[2 * i]; si.uv.y = uv[2 * i + 1];
+        UberProps p;
+        getUberProps(s, materialIdx, &si, &p);
+        float* o = out + ORC_UBER_FLOATS * i;
+        o[0] = p.Kd.x; o[1] = p.Kd.y; o[2] = p.Kd.z; o[3] = p.Ks.x; o[4] = p.Ks.y; o[5] = p.Ks.z;
+        o[6] = p.Kr.x; o[7] = p.Kr.y; o[8] = p.Kr.z; memcpy(o + 9, p.Kt, 4 * sizeof(float));
+        o[13] = p.opacity.x; o[14] = p.opacity.y; o[15] = p.opacity.z;
+        o[16] = p.roughness.x; o[17] = p.roughness.y; o[18] = p.eta;
+        o[19] = (float)hasMaterialNonDeltaComponents(s, materialIdx, &si);
+    }
 }
 
 /* BDPT.cl:22-35 */

@@ -104,6 +104,13 @@ float orc_pdf_uber(const float kd[3], const float ks[3], const float kr[3], cons
                    const float rough_alpha[2], const float opacity[3], float eta,
                    const float wo[3], const float wi[3]);
 float orc_roughness_to_alpha(float r);
+/* readTexture2Df (textures.cl:70-125, :204-209) of n uvs (2n floats) on texture texId: out 4n floats;
+ * idx NULL or 4n ints x0, y0, x1, y1 (-1 where the border colour was returned) */
+void orc_read_tex(const orc_scene* s, int texId, int n, const float* uv, float* out, int32_t* idx);
+/* getUberMaterialProperties + hasMaterialNonDeltaComponents (materials.cl:76-91, :161-179) of n uvs on
+ * one material: ORC_UBER_FLOATS per uv = Kd[3] Ks[3] Kr[3] Kt[4] opacity[3] alpha[2] eta nonDelta(0/1) */
+#define ORC_UBER_FLOATS 20
+void orc_uber_props(const orc_scene* s, int materialIdx, int n, const float* uv, float* out);
 
 /* Post-process passes (test restatements): BilateralDenoise (KRN/Denoise.cl:6-47) and
  * ReinhardToneMapping (KRN/ToneMapping.cl:42-63) on RGBA32F images (W*H float4). */

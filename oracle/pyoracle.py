@@ -66,6 +66,8 @@ def lib():
         L.orc_pdf_uber.argtypes = [_vp] * 6 + [_c.c_float, _vp, _vp]
         L.orc_roughness_to_alpha.restype = _c.c_float
         L.orc_roughness_to_alpha.argtypes = [_c.c_float]
+        L.orc_read_tex.argtypes = [_vp, _c.c_int, _c.c_int, _vp, _vp, _vp]
+        L.orc_uber_props.argtypes = [_vp, _c.c_int, _c.c_int, _vp, _vp]
         _lib = L
     return _lib
 
@@ -169,6 +171,26 @@ class OracleScene:
         self._pathlog = np.zeros((H * W, depth, self.PATHLOG_FLOATS), np.float32)
         lib().orc_set_pathlog(self.h, _p(self._pathlog), depth)
         return self._pathlog
+
+    def read_tex(self, tex_id, uv):
+        """readTex of (N, 2) float32 uvs on one texture -> (values (N, 4) float32, x0 y0 x1 y1 (N, 4)
+        int32, -1 where the border colour was returned)."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 4), np.float32)
+        idx = np.zeros((len(uv), 4), np.int32)
+        lib().orc_read_tex(self.h, int(tex_id), len(uv), _p(uv), _p(out), _p(idx))
+        return out, idx
+
+    UBER_FIELDS = {"Kd": slice(0, 3), "Ks": slice(3, 6), "Kr": slice(6, 9), "Kt": slice(9, 13),
+                   "opacity": slice(13, 16), "roughness": slice(16, 18), "eta": 18, "nonDelta": 19}
+
+    def uber_props(self, material, uv):
+        """getUberProps and hasMaterialNonDeltaComponents of (N, 2) uvs on one material: dict of
+        float32 arrays by UBER_FIELDS (roughness = alpha; nonDelta 0 / 1)."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(uv), 20), np.float32)
+        lib().orc_uber_props(self.h, int(material), len(uv), _p(uv), _p(out))
+        return {k: out[:, s] for k, s in self.UBER_FIELDS.items()}
 
     def render_rows(self, cam, rows, frame=0, max_depth=2, sampler=1, threads=8, radiance=None):
         W, H = int(cam["width"][0]), int(cam["height"][0])

@@ -112,7 +112,33 @@ def tl_job(out_path, variant):
     print(f"clref two-level job ({variant}): {len(res)} arrays -> {out_path}")
 
 
-LOD_CASES = [("lod_test", 160, 120), ("mixed", 96, 64)]
+# Texture zoo (mcrt.scenes.texture_zoo_scene): every material texture slot, wrap mode and a spread of
+# texture sizes, against the reference's PathTracing.cl and BDPT.cl (tests/test_gpu_texture_zoo.py)
+TEX_CASES = [("tex_zoo", 96, 64, (0, 1), 3)]
+TEX_BDPT_CASES = [("tex_zoo", 96, 64, (0, 1), 2)]
+
+
+def tex_job(out_path, variant):
+    res = {}
+    for name, W, H, frames, D in TEX_CASES:
+        cs = po.CLRefScene(build_scene(name), variant)
+        cam = scene_camera(name, W, H)
+        for f in frames:
+            res[f"{name}_{W}x{H}_d{D}_f{f}"] = cs.render(cam, frame=f, max_depth=D)
+    for case in TEX_BDPT_CASES:
+        name, W, H, frames, D = case
+        cs = po.CLRefScene(build_scene(name), variant)
+        cam = scene_camera(name, W, H)
+        key = bdpt_key(case)
+        for f in frames:
+            res[f"{key}_f{f}"] = cs.render_bdpt(cam, frame=f, max_depth=D)
+        for which in ("camera_vertices", "light_vertices", "camera_counts", "light_counts"):
+            res[f"{key}_{which}"] = cs.read_bdpt(which)
+    np.savez_compressed(out_path, **res)
+    print(f"clref texture-zoo job ({variant}): {len(res)} arrays -> {out_path}")
+
+
+LOD_CASES = [("lod_test", 160, 120), ("mixed", 96, 64), ("tex_zoo", 96, 64)]
 
 
 def lod_job(out_path, variant):
@@ -134,6 +160,8 @@ def build_scene(name):
         return scenes.dragon_proxy(tris=20000)
     if name == "lod_test":
         return scenes.lod_test_scene()
+    if name == "tex_zoo":
+        return scenes.texture_zoo_scene()
     if name == "instances_test":
         return scenes.instances_test_scene()
     if name == "instanced_small":
@@ -350,6 +378,9 @@ def main():
         return
     if len(sys.argv) > 3 and sys.argv[3] == "lod":
         lod_job(out_path, variant)
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "tex":
+        tex_job(out_path, variant)
         return
     if len(sys.argv) > 3 and sys.argv[3] == "2l":
         tl_job(out_path, variant)

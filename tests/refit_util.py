@@ -147,6 +147,7 @@ def trace(ds, rays, any_hit=False):
     r = torch.from_numpy(rays.view(np.uint8).copy()).cuda()
     if any_hit:
         out = torch.full((len(rays),), -7, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()   # the fill runs on torch's stream, the query on the context's own
         ds.trace_any(r.data_ptr(), len(rays), out.data_ptr())
     else:
         h0 = np.zeros(len(rays), T.ISECT_DTYPE)

@@ -21,6 +21,7 @@ def _gpu_trace(ctx, scene, rays, any_hit=False, init=-7):
     r = torch.from_numpy(rays.view(np.uint8).copy()).cuda()
     if any_hit:
         out = torch.full((len(rays),), init, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()   # the fill runs on torch's stream, the query on the context's own
         ds.trace_any(r.data_ptr(), len(rays), out.data_ptr())
     else:
         h0 = np.zeros(len(rays), T.ISECT_DTYPE)
@@ -160,6 +161,7 @@ def test_traversal_stack_overflow_is_reported(hip_ctx, monkeypatch):
     rays["extra"] = (-1, 1)
     r = torch.from_numpy(rays.view(np.uint8).copy()).cuda()
     h = torch.zeros(64 * 32, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
     # the default spill capacity covers the tree: correct hit, no error
     ok = lib.DeviceScene(hip_ctx, sc)
     assert ok.layout()["depth"] > 16
@@ -193,6 +195,7 @@ def test_device_count_queries_with_events(hip_ctx):
     r = torch.from_numpy(rays.view(np.uint8).copy()).cuda()
     ref_h = torch.full((n * 32,), 0xAB, dtype=torch.uint8, device="cuda")   # a miss leaves uvwt untouched
     ref_o = torch.zeros(n, dtype=torch.int32, device="cuda")
+    torch.cuda.synchronize()   # the fills run on torch's stream, the queries on the context's own
     ds.trace_closest(r.data_ptr(), n, ref_h.data_ptr())
     ds.trace_any(r.data_ptr(), n, ref_o.data_ptr())
     hip_ctx.sync()
@@ -200,6 +203,7 @@ def test_device_count_queries_with_events(hip_ctx):
         cnt = torch.tensor([k], dtype=torch.int32, device="cuda")
         h = torch.full((n * 32,), 0xAB, dtype=torch.uint8, device="cuda")
         o = torch.full((n,), -5, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
         e1 = ds.trace_count(False, r.data_ptr(), cnt.data_ptr(), n, h.data_ptr(), want_event=True)
         e2 = ds.trace_count(True, r.data_ptr(), cnt.data_ptr(), n, o.data_ptr(), wait_event=e1, want_event=True)
         lib.event_wait(e2)
