@@ -372,7 +372,6 @@ bool build_bvh(const float* tri, const int32_t* shapeOf, const int32_t* primOf, 
     out.numTris = 0;
     for (std::size_t i = 0; i < count; ++i) out.numTris += b.isInternal[i] ? 0 : 1;
     out.nodes = (float*)std::malloc(sizeof(float) * 16 * out.numNodes);
-    out.tris = nullptr;
     out.depth = b.maxDepth.load();
     auto leafBox = [&](uint32_t ref, float* bx) {
         const float* p = &tri[9 * (std::size_t)ref];
@@ -425,9 +424,7 @@ bool build_bvh(const float* tri, const int32_t* shapeOf, const int32_t* primOf, 
 
 void free_bvh(BvhOut& out) {
     std::free(out.nodes);
-    std::free(out.tris);
     out.nodes = nullptr;
-    out.tris = nullptr;
 }
 
 }  // namespace mcrt

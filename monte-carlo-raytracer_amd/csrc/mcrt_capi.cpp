@@ -8,16 +8,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <map>
-#include <mutex>
 #include <string>
-#include <thread>
 #include <tuple>
 #include <vector>
 
@@ -36,7 +33,7 @@ int dev_sync(void* stream) { return (int)hipStreamSynchronize((hipStream_t)strea
 }  // namespace mcrt
 // the helpers mcrt_host.h declares for other host files; defined below among the file's own
 using mcrt::fail, mcrt::env_int, mcrt::fb_sync, mcrt::ctx_wait_slots, mcrt::frame_args, mcrt::ensure_spill,
-    mcrt::packet_ctx, mcrt::scene_args;
+    mcrt::trace_ctx, mcrt::packet_ctx, mcrt::with_hints, mcrt::scene_args, mcrt::upload, mcrt::accel_ready;
 namespace {
 
 #define MCRT_MAX_BOUNCES 32
@@ -68,16 +65,6 @@ mcrt_status mcrt::fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg) {
     return code;
 }
 
-// `count` host elements into the (empty) buffer; S is T or the C ABI's name for it
-template <class T, class S>
-static hipError_t upload(DevBuf<T>& dst, const S* src, size_t count, hipStream_t st) {
-    static_assert(sizeof(S) == sizeof(T), "same element");
-    if (!src || count == 0) return hipSuccess;
-    hipError_t e = (hipError_t)dst.alloc(count);
-    if (e != hipSuccess) return e;
-    return hipMemcpyAsync(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice, st);
-}
-
 static void drain_pending(mcrt_ctx ctx) {
     if (ctx->pending.empty()) return;
     for (auto& p : ctx->pending) {
@@ -100,102 +87,9 @@ static void drain_pending(mcrt_ctx ctx) {
     ctx->pending.clear();
 }
 
-// RR transform_point (RR/include/math/mathutils.h:111-118) for the BVH's world-space triangles
-static inline void xformPoint(const mcrt_mat4& m, const mcrt_float4& p, float* o) {
-    const mcrt_float4* r[3] = {&m.m0, &m.m1, &m.m2};
-    for (int i = 0; i < 3; ++i) {
-        float acc = 0.0f;
-        acc += r[i]->x * p.x;
-        acc += r[i]->y * p.y;
-        acc += r[i]->z * p.z;
-        acc += r[i]->w * 0.0f;
-        o[i] = acc + r[i]->w;
-    }
-}
-
-bool mcrt::ensure_spill(mcrt_scene s, size_t rays) {
-    rays = (rays + 63) / 64 * 64;
-    return s->dSpill.grow(rays * (size_t)s->spillCap, s->ctx->stream) == 0;
-}
-
-static TraceCtx trace_ctx(mcrt_scene s) {
-    TraceCtx c = {};
-    c.nodes = s->dNodes.get();
-    c.packet = 0;
-    c.spill = s->dSpill.get();
-    c.spillCap = s->spillCap;
-    c.overflow = s->ctx->dFlags;
-    c.twoLevel = s->twoLevel ? 1 : 0;
-    c.numNodes = (uint32_t)s->numNodes;
-    c.qnodes = s->dQNodes.get();
-    c.qroot = s->qRoot;
-    return c;
-}
-
 int mcrt::env_int(const char* name, int def, int lo, int hi) {
     const char* e = std::getenv(name);
     return e ? (int)std::min<long>(hi, std::max<long>(lo, std::strtol(e, nullptr, 10))) : def;
-}
-
-// Occluder hints for a shadow launch (mcrt_traverse.h hintOccludes; flat trees only -- the leaf test
-// of a two-level record would need the instance transform): bounce-0 rays by pixel (table `pix`,
-// n pixels), later ones by origin cell.  The answers are the walk's with or without them;
-// MCRT_SHADOW_HINTS=0 turns them off (A/B, tests).
-static bool hints_enabled() { return env_int("MCRT_SHADOW_HINTS", 1) != 0; }
-// test hook: MCRT_TEST_HINT_FILL=seed fills a new hint table with pseudo-random words below
-// `range` instead of "no hint", so a test can check that arbitrary hints change no answer
-static hipError_t fill_hints(uint32_t* d, size_t n, uint32_t range, hipStream_t st) {
-    const char* e = std::getenv("MCRT_TEST_HINT_FILL");
-    if (!e) return hipMemsetAsync(d, 0xff, 4 * n, st);
-    std::vector<uint32_t> h(n);
-    uint32_t x = 2463534242u + (uint32_t)std::atoi(e);
-    for (auto& v : h) {
-        x ^= x << 13; x ^= x >> 17; x ^= x << 5;
-        v = x % range;
-    }
-    hipError_t r = hipMemcpyAsync(d, h.data(), 4 * n, hipMemcpyHostToDevice, st);
-    if (r == hipSuccess) r = hipStreamSynchronize(st);
-    return r;
-}
-// Entries of the origin-cell table: 2^25 words (128 MB) for trees of more than 2^22 nodes (the
-// headline scene: 20 M nodes), fewer for smaller trees (2 words per node, at least 2^18).  Any size
-// is safe -- a slot is a hint, never an answer.
-static int hint_bits_for(uint32_t numNodes) {
-    int b = 18;
-    while (b < MCRT_HINT_CELL_BITS && (1u << b) < 2u * numNodes) ++b;
-    return b;
-}
-// The table is allocated (and emptied) on the first launch that uses it, on the context stream,
-// which is finished before the launch's own stream reads it; if it does not fit, hints stay off.
-static bool ensure_hint_cell(mcrt_scene s) {
-    if (s->dHintCell) return true;
-    if (s->hintAllocFailed) return false;
-    mcrt_ctx ctx = s->ctx;
-    const int bits = hint_bits_for((uint32_t)s->numNodes);
-    hipError_t e = (hipError_t)s->dHintCell.alloc((size_t)1 << bits);
-    if (e == hipSuccess) e = fill_hints(s->dHintCell.get(), (size_t)1 << bits, (uint32_t)s->numNodes + 64, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        hipGetLastError();
-        s->dHintCell.reset();
-        s->hintAllocFailed = true;
-        return false;
-    }
-    s->hintBits = bits;
-    return true;
-}
-static void with_hints(TraceCtx& c, mcrt_scene s, uint32_t* pix, uint32_t n) {
-    if (s->twoLevel || !hints_enabled() || !ensure_hint_cell(s)) return;
-    c.hintCell = s->dHintCell.get();
-    c.hintMask = (1u << s->hintBits) - 1;
-    for (int a = 0; a < 3; ++a) {
-        const float ext = s->bbHi[a] - s->bbLo[a];
-        c.hintLo[a] = s->bbLo[a];
-        c.hintInvExt[a] = ext > 0.0f ? 1.0f / ext : 0.0f;
-    }
-    c.hint = pix ? pix : s->dHintCell.get();
-    c.hintMode = pix ? MCRT_HINT_PIXEL : MCRT_HINT_CELL;
-    c.hintPixels = n;
 }
 
 // Stop rule of the extension rays' compact walks (TraceCtx::walkCap / walkLanes): a wave stops
@@ -218,12 +112,6 @@ static int walk_max_bounce() { return env_int("MCRT_WALK_MAXB", 0); }
 static int bdpt_light_in_vertex() { return env_int("MCRT_BDPT_LIGHT_IN_VERTEX", 1) != 0; }
 static int walk_lanes() { return env_int("MCRT_WALK_LANES", 8, 0, 64); }
 
-TraceCtx mcrt::packet_ctx(mcrt_scene s) {
-    TraceCtx c = trace_ctx(s);
-    c.packet = s->packets ? 1 : 0;
-    return c;
-}
-
 SceneArgs mcrt::scene_args(mcrt_scene s) {
     SceneArgs a;
     a.shapes = s->dShapes.get();
@@ -236,7 +124,7 @@ SceneArgs mcrt::scene_args(mcrt_scene s) {
     a.sobol = s->dSobol.get();
     a.lights = s->dLights.get();
     a.materials = s->dMaterials.get();
-    a.nodes = s->dNodes.get();
+    a.nodes = mcrt::accel_nodes(s);
     a.surf = s->dSurf.get();
     a.surfBase = s->dSurfBase.get();
     a.numLights = (int)s->numLights;
@@ -545,19 +433,15 @@ MCRT_API mcrt_status mcrt_scene_create(mcrt_ctx ctx, const mcrt_scene_desc* d, m
     if (d->num_shapes == 0 || !d->shapes) return fail(ctx, MCRT_ERROR_INVALID_ARG, "scene has no shapes");
     if (!d->indices || !d->positions || !d->uvs || !d->normals)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "indices/positions/uvs/normals are required");
+    uint32_t at = 0;
+    if (const int bad = mcrt::check_shape_ranges(d->shapes, d->num_shapes, d->indices, d->num_indices, d->num_vertices, &at))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, bad == 1 ? "shape " + std::to_string(at) + " indexes past the index array"
+                                                          : "vertex index out of range in shape " + std::to_string(at));
     for (uint32_t i = 0; i < d->num_shapes; ++i) {
         const mcrt_shape& s = d->shapes[i];
-        if ((uint64_t)s.startIdx + 3ull * s.numTriangles > d->num_indices)
-            return fail(ctx, MCRT_ERROR_INVALID_ARG, "shape " + std::to_string(i) + " indexes past the index array");
         if (s.materialId >= (int)d->num_materials)
             return fail(ctx, MCRT_ERROR_INVALID_ARG, "shape " + std::to_string(i) + " has an invalid material id");
         if (s.lightID >= (int)d->num_lights) return fail(ctx, MCRT_ERROR_INVALID_ARG, "invalid light id");
-    }
-    for (uint32_t i = 0; i < d->num_shapes; ++i) {
-        const mcrt_shape& s = d->shapes[i];
-        for (uint32_t k = 0; k < 3u * s.numTriangles; ++k)
-            if ((uint64_t)s.startVertex + d->indices[s.startIdx + k] >= d->num_vertices)
-                return fail(ctx, MCRT_ERROR_INVALID_ARG, "vertex index out of range in shape " + std::to_string(i));
     }
     for (uint32_t i = 0; i < d->num_lights; ++i) {
         const mcrt_light& L = d->lights[i];
@@ -652,436 +536,6 @@ MCRT_API mcrt_status mcrt_scene_motion_snapshot(mcrt_scene s) {
     return MCRT_OK;
 }
 
-static mcrt_status finish_accel(mcrt_scene s, std::chrono::steady_clock::time_point t0, const float* box6);
-
-MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts) {
-    if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
-    mcrt_ctx ctx = s->ctx;
-    const float cost = opts ? opts->traversal_cost : 10.0f;
-    const int bins = opts ? opts->num_bins : 64;
-    const bool sah = opts ? opts->use_sah != 0 : true;
-    if (bins < 2 || bins > 4096) return fail(ctx, MCRT_ERROR_INVALID_ARG, "num_bins out of range");
-    s->haveOpts = opts != nullptr;
-    if (opts && opts != &s->lastOpts) s->lastOpts = *opts;
-    s->lastOpts.world_to_local = nullptr;   // the caller's array, not kept
-    auto t0 = std::chrono::steady_clock::now();
-    size_t n = 0;
-    for (auto& sh : s->shapes) n += sh.numTriangles;
-    if (n == 0) return fail(ctx, MCRT_ERROR_INVALID_ARG, "scene has no triangles (RR: Commit on empty scene throws)");
-    if (n > (size_t)0x7fffffff) return fail(ctx, MCRT_ERROR_INVALID_ARG, "too many triangles");
-    // IntersectorTwoLevel when forced or when a mesh is shared, unless flat is forced
-    // (CalcIntersectionDevice::Preprocess, RR/src/device/calc_intersection_device.cpp:68-105)
-    const bool use2 = (opts && opts->force_2level) ||
-                      (!(opts && opts->force_flat) && mcrt::shapes_are_instanced(s->shapes.data(), s->shapes.size()));
-    if (use2) {
-        int threads = (int)std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-        mcrt::Bvh2lOut b2;
-        const mcrt_mat4* w2l = opts ? opts->world_to_local : nullptr;
-        if (!mcrt::build_bvh2l(s->shapes.data(), s->shapes.size(), s->indices.data(), s->positions.data(),
-                               w2l, cost, bins, sah, threads, b2))
-            return fail(ctx, MCRT_ERROR_INVALID_ARG, "two-level BVH build failed");
-        hipSetDevice(ctx->device);
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        s->dNodes.reset();
-        hipError_t e = (hipError_t)s->dNodes.alloc(4 * b2.numNodes);
-        if (e == hipSuccess) e = hipMemcpy(s->dNodes.get(), b2.records.data(), 64 * b2.numNodes, hipMemcpyHostToDevice);
-        if (e != hipSuccess) return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, std::string("BVH upload: ") + hipGetErrorString(e));
-        s->numNodes = b2.numNodes;
-        s->numTris = (uint32_t)n;
-        s->bvhDepth = b2.depth;
-        s->twoLevel = true;
-        s->numMeshes = b2.numMeshes;
-        s->numInstances = b2.numInstances;
-        s->top2l = std::move(b2.top);
-        s->topNodes = b2.topNodes;
-        mcrt::top_build_destroy(s->topDev);   // sized for the previous top level
-        s->topDev = nullptr;
-        return finish_accel(s, t0, b2.topBox);
-    }
-    s->twoLevel = false;
-    s->numMeshes = s->numInstances = 0;
-    const int buildMode = opts ? opts->device_build : 0;
-    if (buildMode == 0 || buildMode == 2) {   // on-device SAH, node-identical to the host build
-        hipSetDevice(ctx->device);
-        std::vector<uint32_t> first(s->shapes.size());
-        uint32_t acc = 0;
-        for (size_t si = 0; si < s->shapes.size(); ++si) { first[si] = acc; acc += s->shapes[si].numTriangles; }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        float4* nodes = nullptr;
-        int depth = 0;
-        const char* why = nullptr;
-        const hipError_t e = mcrt::gpu_build_sah(s->dShapes.get(), first, s->dIndices.get(), s->dPositions.get(), n, cost,
-                                                 bins, sah, ctx->stream, &nodes, &depth, &why);
-        if (e == hipSuccess) {
-            s->dNodes.adopt(nodes, 4 * (2 * n - 1));
-            s->numNodes = 2 * n - 1;
-            s->numTris = (uint32_t)n;
-            s->bvhDepth = depth;
-            s->builder = 2;
-            return finish_accel(s, t0, nullptr);
-        }
-        // configurations the device path does not reproduce (> 64 bins, a host whose rcpps the
-        // table cannot model, pathological level counts) take the host build: same tree; so does a
-        // device without room for the build's scratch (~230 B per triangle beyond the records)
-        if (e != hipErrorNotSupported && e != hipErrorInvalidValue && e != hipErrorOutOfMemory)
-            return fail(ctx, MCRT_ERROR_DEVICE, std::string("device SAH build: ") + (why ? why : hipGetErrorString(e)));
-        (void)hipGetLastError();
-        if (e == hipErrorOutOfMemory)
-            std::fprintf(stderr, "mcrt: device SAH build out of memory, building the same tree on the host\n");
-    }
-    s->builder = 0;
-    if (buildMode == 1) {   // on-device linear BVH (mcrt_gpubuild.hip)
-        hipSetDevice(ctx->device);
-        std::vector<uint32_t> first(s->shapes.size());
-        uint32_t acc = 0;
-        for (size_t si = 0; si < s->shapes.size(); ++si) { first[si] = acc; acc += s->shapes[si].numTriangles; }
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        float4* nodes = nullptr;
-        int depth = 0;
-        HIPCHK(ctx, mcrt::gpu_build_bvh(s->dShapes.get(), first, s->dIndices.get(), s->dPositions.get(), n, ctx->stream,
-                                        &nodes, &depth));
-        s->dNodes.adopt(nodes, 4 * (2 * n - 1));
-        s->numNodes = 2 * n - 1;
-        s->numTris = (uint32_t)n;
-        s->bvhDepth = depth;
-        s->builder = 1;
-        return finish_accel(s, t0, nullptr);
-    }
-    std::vector<float> tri(9 * n);
-    std::vector<int32_t> shapeOf(n), primOf(n);
-    size_t k = 0;
-    for (size_t si = 0; si < s->shapes.size(); ++si) {
-        const mcrt_shape& sh = s->shapes[si];
-        for (uint32_t f = 0; f < sh.numTriangles; ++f, ++k) {
-            for (int c = 0; c < 3; ++c)
-                xformPoint(sh.toWorldTransform, s->positions[sh.startVertex + s->indices[sh.startIdx + 3 * f + c]],
-                           &tri[9 * k + 3 * c]);
-            shapeOf[k] = (int32_t)si;
-            primOf[k] = (int32_t)f;
-        }
-    }
-    int threads = (int)std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-    mcrt::BvhOut bvh;
-    if (!mcrt::build_bvh(tri.data(), shapeOf.data(), primOf.data(), n, cost, bins, sah, threads, bvh, buildMode == 4))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "BVH build failed");
-    if (buildMode == 4) s->builder = 4;   // the perf tree (3-axis SAH), not the reference's
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    s->dNodes.reset();
-    hipError_t e = (hipError_t)s->dNodes.alloc(4 * bvh.numNodes);
-    if (e == hipSuccess) e = hipMemcpy(s->dNodes.get(), bvh.nodes, 64 * bvh.numNodes, hipMemcpyHostToDevice);
-    s->numNodes = bvh.numNodes;
-    s->numTris = (uint32_t)bvh.numTris;
-    s->bvhDepth = bvh.depth;
-    mcrt::free_bvh(bvh);
-    if (e != hipSuccess) return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, std::string("BVH upload: ") + hipGetErrorString(e));
-    return finish_accel(s, t0, nullptr);
-}
-
-// per-ray spill columns deep enough for the tree (allocated by ensure_spill for the largest launch)
-static void apply_spill_cap(mcrt_scene s) {
-    int needCap = ((s->bvhDepth + 2 + 15) / 16) * 16;   // whole spill blocks of STACK_LDS entries
-    // test hook: MCRT_TEST_SPILL_CAP=k caps the spill columns at k entries (0 = LDS stack only) so a
-    // test can drive a traversal past its capacity and check that the overflow is reported
-    if (const char* tc = std::getenv("MCRT_TEST_SPILL_CAP")) needCap = std::max(0, std::atoi(tc) / 16 * 16);
-    if (needCap != s->spillCap) {
-        s->dSpill.reset();
-        s->spillCap = needCap;
-    }
-}
-
-// traversal scratch: overflow flag, spill columns
-static mcrt_status finish_accel(mcrt_scene s, std::chrono::steady_clock::time_point t0, const float* box6) {
-    mcrt_ctx ctx = s->ctx;
-    // wave packets for the coherent launches (mcrt_traverse.h traversePacket): flat trees whose
-    // depth fits the packet stack (at most 2 entries per internal level: 2 x depth, the leaves'
-    // level).  MCRT_CAMERA_PACKETS=0 walks them per ray (A/B and tests: the results are the same bit
-    // for bit).
-    s->packets = !s->twoLevel && 2 * s->bvhDepth <= MCRT_PK_STACK && s->numNodes < (1u << 26) &&   // 32-bit offsets
-                 env_int("MCRT_CAMERA_PACKETS", 1) != 0;
-    if (!s->dScratch) HIPCHK(ctx, s->dScratch.alloc(256));
-    HIPCHK(ctx, hipMemset(s->dScratch.get(), 0, 256 * sizeof(int)));
-    if (!s->twoLevel) {
-        // parent links of the leaves (occluder hints).  The origin-cell hint table is allocated on
-        // its first use (ensure_hint_cell, sized for the tree); a rebuild drops the old one
-        mcrt::launch_leaf_parents(s->dNodes.get(), (uint32_t)s->numNodes, ctx->stream);
-        HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-        s->dHintCell.reset();
-        s->hintAllocFailed = false;
-    }
-    // compact records for the per-ray walks (mcrt_traverse.h traverseQOct): depth-first flat trees;
-    // MCRT_QUANT_NODES=0 keeps the 64-B records everywhere (A/B, tests).  A tree the converter
-    // cannot take (LBVH numbering) or a device without room for it (~0.8 GB at 10 M triangles)
-    // keeps the 64-B walk: the same answers.
-    s->dQNodes.reset();
-    if (!s->twoLevel && env_int("MCRT_QUANT_NODES", 1) != 0) {
-        float4* q = nullptr;
-        size_t units = 0;
-        const hipError_t e = mcrt::build_qnodes(s->dNodes.get(), (uint32_t)s->numNodes, &q, &units, ctx->stream);
-        if (e == hipSuccess) {
-            s->dQNodes.adopt(q, units);
-        } else if (e != hipErrorNotSupported && e != hipErrorOutOfMemory) {
-            return fail(ctx, MCRT_ERROR_DEVICE, std::string("compact records: ") + hipGetErrorString(e));
-        } else {
-            (void)hipGetLastError();
-        }
-    }
-    apply_spill_cap(s);
-    if (box6) {
-        for (int a = 0; a < 3; ++a) { s->bbLo[a] = box6[a]; s->bbHi[a] = box6[3 + a]; }
-        s->buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return MCRT_OK;
-    }
-    // world bounds = the root record's two child boxes (or its triangle)
-    float r[16];
-    HIPCHK(ctx, hipMemcpy(r, s->dNodes.get(), 64, hipMemcpyDeviceToHost));
-    int32_t mark;
-    std::memcpy(&mark, &r[12], 4);
-    s->qRoot = mark >= 0 ? 0u : 1u;   // compact reference of the root: offset 0, leaf bit
-    if (mark >= 0) {
-        const float lo[3] = {std::min(r[0], r[4]), std::min(r[2], r[6]), std::min(r[8], r[10])};
-        const float hi[3] = {std::max(r[1], r[5]), std::max(r[3], r[7]), std::max(r[9], r[11])};
-        for (int a = 0; a < 3; ++a) { s->bbLo[a] = lo[a]; s->bbHi[a] = hi[a]; }
-    } else {
-        for (int a = 0; a < 3; ++a) {
-            const float v0 = r[a], v1 = r[a] + r[4 + a], v2 = r[a] + r[8 + a];
-            s->bbLo[a] = std::min(v0, std::min(v1, v2));
-            s->bbHi[a] = std::max(v0, std::max(v1, v2));
-        }
-    }
-    s->buildMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return MCRT_OK;
-}
-
-// Shapes from which a top-level instance count the device builds the top tree when MCRT_TOP_BUILD
-// is unset (tools/refit_time.py -> profiles/refit/refit_time.json, "threshold")
-static constexpr size_t MCRT_TOP_DEVICE_MIN_SHAPES = 10000;
-
-// same shapes but for transforms and surface data; two-level: the mesh key must not move
-static bool same_topology(const mcrt_shape* a, const mcrt_shape* b, size_t n, bool twoLevel) {
-    for (size_t i = 0; i < n; ++i)
-        if (a[i].startIdx != b[i].startIdx || a[i].numTriangles != b[i].numTriangles ||
-            (twoLevel && a[i].startVertex != b[i].startVertex))
-            return false;
-    return true;
-}
-
-MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape* sh, uint32_t n,
-                                                  const mcrt_mat4* world_to_local) {
-    if (!s || !sh || n != s->shapes.size())
-        return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "shape count must not change");
-    mcrt_ctx ctx = s->ctx;
-    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
-    if (!same_topology(sh, s->shapes.data(), n, s->twoLevel))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "shape topology must not change");
-    const auto t0 = std::chrono::steady_clock::now();
-    hipSetDevice(ctx->device);
-    // after every launch that reads the records or the shapes: the context stream and the
-    // frame-slot streams of the context's frame buffers (as mcrt_ctx_synchronize reaches them)
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipDeviceSynchronize());
-    auto done = [&](int path) {
-        s->updatePath = path;
-        s->updateMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        return MCRT_OK;
-    };
-    if (!s->twoLevel) {
-        // RR's flat intersector rebuilds on every Commit: the last build's options again
-        mcrt_status st = mcrt_scene_update_shapes(s, sh, n);
-        if (st != MCRT_OK) return st;
-        mcrt_accel_opts o = s->lastOpts;
-        o.world_to_local = world_to_local;
-        const bool had = s->haveOpts;
-        st = mcrt_accel_build(s, had ? &o : nullptr);
-        if (st != MCRT_OK) return st;
-        return done(3);
-    }
-    // the mesh keys are unchanged, so the surface records and their bases are too
-    s->shapes.assign(sh, sh + n);
-    HIPCHK(ctx, hipMemcpy(s->dShapes.get(), sh, sizeof(mcrt_shape) * n, hipMemcpyHostToDevice));
-    const mcrt::Bvh2lTop& top = s->top2l;
-    const char* env = std::getenv("MCRT_TOP_BUILD");
-    const bool forceHost = env && std::strcmp(env, "host") == 0;
-    const bool forceDev = env && std::strcmp(env, "device") == 0;
-    bool device = forceDev || (!forceHost && top.world.size() >= MCRT_TOP_DEVICE_MIN_SHAPES);
-    std::string devWhy;
-    if (device && top.bins > 64) {   // as mcrt_sahbuild.hip
-        device = false;
-        devWhy = "the device top-level build supports 2..64 bins";
-    }
-    int depth = 0, path = 2;
-    float box[6];
-    if (device) {
-        hipError_t e = hipSuccess;
-        const char* why = nullptr;
-        DevBuf<mcrt_mat4> dW2l;
-        if (!s->topDev) e = mcrt::top_build_create(top, &s->topDev);
-        if (e == hipSuccess && world_to_local) e = upload(dW2l, world_to_local, (size_t)n, ctx->stream);
-        if (e == hipSuccess)
-            e = mcrt::top_build_run(s->topDev, s->dShapes.get(), dW2l.get(), s->dNodes.get(), ctx->stream, &depth, box,
-                                    &why);
-        if (dW2l) {
-            (void)hipStreamSynchronize(ctx->stream);
-            dW2l.reset();
-        }
-        if (e == hipSuccess) {
-            path = 1;
-        } else if (e == hipErrorNotSupported || e == hipErrorInvalidValue || e == hipErrorOutOfMemory) {
-            (void)hipGetLastError();
-            devWhy = why ? why : hipGetErrorString(e);   // the host path below rewrites the records
-        } else {
-            return fail(ctx, MCRT_ERROR_DEVICE, std::string("device top-level build: ") + hipGetErrorString(e));
-        }
-    }
-    if (path == 2) {
-        std::vector<float> rec(16 * (size_t)s->topNodes);
-        mcrt::build_bvh2l_top(top, s->shapes.data(), world_to_local, rec.data(), &depth, box);
-        HIPCHK(ctx, hipMemcpy(s->dNodes.get(), rec.data(), 64 * (size_t)s->topNodes, hipMemcpyHostToDevice));
-    }
-    s->bvhDepth = depth;
-    for (int a = 0; a < 3; ++a) { s->bbLo[a] = box[a]; s->bbHi[a] = box[3 + a]; }
-    apply_spill_cap(s);
-    done(path);
-    if (forceDev && path != 1) return fail(ctx, MCRT_ERROR_DEVICE, "MCRT_TOP_BUILD=device: " + devWhy);
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_accel_update_info(mcrt_scene s, int32_t* path, double* ms) {
-    if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
-    if (path) *path = s->updatePath;
-    if (ms) *ms = s->updateMs;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_accel_info(mcrt_scene s, uint64_t* num_nodes, uint64_t* device_bytes, double* build_ms,
-                                     uint32_t* num_triangles) {
-    if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
-    if (num_nodes) *num_nodes = s->numNodes;
-    if (device_bytes) *device_bytes = 64ull * s->numNodes + 16ull * s->dQNodes.size();
-    if (build_ms) *build_ms = s->buildMs;
-    if (num_triangles) *num_triangles = s->numTris;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_accel_layout(mcrt_scene s, int32_t* two_level, uint32_t* num_meshes,
-                                       uint32_t* num_instances, int32_t* depth) {
-    if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
-    if (!s->dNodes) return fail(s->ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
-    if (two_level) *two_level = s->twoLevel ? 1 : 0;
-    if (num_meshes) *num_meshes = (uint32_t)s->numMeshes;
-    if (num_instances) *num_instances = (uint32_t)s->numInstances;
-    if (depth) *depth = s->bvhDepth;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_accel_read_records(mcrt_scene s, float* out, uint64_t max_records, uint64_t* num_records) {
-    if (!s || !num_records) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    if (!s->dNodes) return fail(s->ctx, MCRT_ERROR_INVALID_ARG, "scene has no acceleration structure");
-    *num_records = s->numNodes;
-    if (!out) return MCRT_OK;
-    mcrt_ctx ctx = s->ctx;
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    HIPCHK(ctx, hipMemcpy(out, s->dNodes.get(), 64 * std::min<uint64_t>(max_records, s->numNodes), hipMemcpyDeviceToHost));
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_accel_builder(mcrt_scene s, int32_t* builder) {
-    if (!s || !builder) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    *builder = s->twoLevel ? 0 : s->builder;
-    return MCRT_OK;
-}
-
-static mcrt_status host_records(const mcrt_scene_desc* d, const mcrt_accel_opts* opts, const mcrt_shape* moved,
-                                const mcrt_mat4* moved_w2l, float* out_records, uint64_t max_records,
-                                uint64_t* num_records, int32_t* info) {
-    if (!d || !d->shapes || !d->indices || !d->positions || !num_records)
-        return fail(nullptr, MCRT_ERROR_INVALID_ARG, "invalid arguments");
-    const float cost = opts ? opts->traversal_cost : 10.0f;
-    const int bins = opts ? opts->num_bins : 64;
-    const bool sah = opts ? opts->use_sah != 0 : true;
-    if (bins < 2 || bins > 4096) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "num_bins out of range");
-    for (uint32_t i = 0; i < d->num_shapes; ++i) {
-        const mcrt_shape& sh = d->shapes[i];
-        if ((uint64_t)sh.startIdx + 3ull * sh.numTriangles > d->num_indices)
-            return fail(nullptr, MCRT_ERROR_INVALID_ARG, "shape indices out of range");
-        for (uint64_t k = 0; k < 3ull * sh.numTriangles; ++k)
-            if ((uint64_t)sh.startVertex + d->indices[sh.startIdx + k] >= d->num_vertices)
-                return fail(nullptr, MCRT_ERROR_INVALID_ARG, "vertex index out of range");
-    }
-    const int threads = (int)std::max(1u, std::min(64u, std::thread::hardware_concurrency()));
-    const bool use2 = (opts && opts->force_2level) ||
-                      (!(opts && opts->force_flat) && mcrt::shapes_are_instanced(d->shapes, d->num_shapes));
-    int32_t inf[4] = {use2 ? 1 : 0, 0, 0, 0};
-    if (use2) {
-        mcrt::Bvh2lOut b2;
-        if (!mcrt::build_bvh2l(d->shapes, d->num_shapes, d->indices, d->positions, opts ? opts->world_to_local : nullptr,
-                               cost, bins, sah, threads, b2))
-            return fail(nullptr, MCRT_ERROR_INVALID_ARG, "two-level BVH build failed");
-        if (moved) {   // mcrt_accel_refit_host_records: the refit's top level over the built one
-            mcrt::build_bvh2l_top(b2.top, moved, moved_w2l, b2.records.data(), &b2.depth, b2.topBox);
-        }
-        *num_records = b2.numNodes;
-        if (out_records) std::memcpy(out_records, b2.records.data(), 64 * std::min<uint64_t>(max_records, b2.numNodes));
-        inf[1] = (int32_t)b2.topNodes;
-        inf[2] = b2.depth;
-        inf[3] = b2.numMeshes;
-    } else {
-        size_t n = 0;
-        for (uint32_t i = 0; i < d->num_shapes; ++i) n += d->shapes[i].numTriangles;
-        if (n == 0) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene has no triangles");
-        std::vector<float> tri(9 * n);
-        std::vector<int32_t> shapeOf(n), primOf(n);
-        size_t k = 0;
-        for (uint32_t si = 0; si < d->num_shapes; ++si) {
-            const mcrt_shape& sh = d->shapes[si];
-            for (uint32_t f = 0; f < sh.numTriangles; ++f, ++k) {
-                for (int c = 0; c < 3; ++c)
-                    xformPoint(sh.toWorldTransform, d->positions[sh.startVertex + d->indices[sh.startIdx + 3 * f + c]],
-                               &tri[9 * k + 3 * c]);
-                shapeOf[k] = (int32_t)si;
-                primOf[k] = (int32_t)f;
-            }
-        }
-        mcrt::BvhOut bvh;
-        if (!mcrt::build_bvh(tri.data(), shapeOf.data(), primOf.data(), n, cost, bins, sah, threads, bvh,
-                             opts && opts->device_build == 4))
-            return fail(nullptr, MCRT_ERROR_INVALID_ARG, "BVH build failed");
-        *num_records = bvh.numNodes;
-        if (out_records) std::memcpy(out_records, bvh.nodes, 64 * std::min<uint64_t>(max_records, bvh.numNodes));
-        inf[1] = (int32_t)bvh.numNodes;
-        inf[2] = bvh.depth;
-        mcrt::free_bvh(bvh);
-    }
-    if (info) std::memcpy(info, inf, sizeof(inf));
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_accel_build_host_records(const mcrt_scene_desc* d, const mcrt_accel_opts* opts,
-                                                   float* out_records, uint64_t max_records, uint64_t* num_records,
-                                                   int32_t* info) {
-    return host_records(d, opts, nullptr, nullptr, out_records, max_records, num_records, info);
-}
-
-MCRT_API mcrt_status mcrt_accel_refit_host_records(const mcrt_scene_desc* d, const mcrt_accel_opts* opts,
-                                                   const mcrt_shape* moved_shapes, const mcrt_mat4* moved_world_to_local,
-                                                   float* out_records, uint64_t max_records, uint64_t* num_records,
-                                                   int32_t* info) {
-    if (!d || !d->shapes || !moved_shapes) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "invalid arguments");
-    const bool use2 = (opts && opts->force_2level) ||
-                      (!(opts && opts->force_flat) && mcrt::shapes_are_instanced(d->shapes, d->num_shapes));
-    if (!same_topology(moved_shapes, d->shapes, d->num_shapes, use2))
-        return fail(nullptr, MCRT_ERROR_INVALID_ARG, "shape topology must not change");
-    if (use2) return host_records(d, opts, moved_shapes, moved_world_to_local, out_records, max_records, num_records, info);
-    // a flat structure is rebuilt: the fresh build of the moved shapes
-    mcrt_scene_desc md = *d;
-    md.shapes = moved_shapes;
-    mcrt_accel_opts o = {10.0f, 64, 1, 0, 0, 0, nullptr};   // mcrt_accel_build's defaults
-    if (opts) o = *opts;
-    o.world_to_local = moved_world_to_local;
-    return host_records(&md, &o, nullptr, nullptr, out_records, max_records, num_records, info);
-}
-
 // ---------------------------------------------------------------------------
 // RadeonRays-style queries
 // ---------------------------------------------------------------------------
@@ -1097,7 +551,7 @@ static mcrt_status trace_common(mcrt_scene s, const mcrt_ray* rays, int32_t n, c
     if (done) *done = nullptr;
     if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
     mcrt_ctx ctx = s->ctx;
-    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
+    if (!accel_ready(s)) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
     if (n < 0 || (n > 0 && !rays) || (n > 0 && !any && !hits) || (n > 0 && any && !occl))
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "invalid ray query arguments");
     hipSetDevice(ctx->device);
@@ -1314,7 +768,7 @@ MCRT_API mcrt_status mcrt_framebuffer_create(mcrt_ctx ctx, uint32_t width, uint3
     for (auto* img : {&fb->wsum, &fb->image, &fb->denoised, &fb->display})
         if (e == hipSuccess) e = hipMemsetAsync(img->get(), 0, 16 * N, fb->slot[0].stream);
     if (e == hipSuccess) e = hipMemsetAsync(fb->wts.get(), 0, 4 * N, fb->slot[0].stream);
-    if (e == hipSuccess) e = fill_hints(fb->hintPix.get(), N, 1u << 22, fb->slot[0].stream);   // no hints
+    if (e == hipSuccess) e = mcrt::fill_hints(fb->hintPix.get(), N, 1u << 22, fb->slot[0].stream);   // no hints
     if (e == hipSuccess) e = hipStreamSynchronize(fb->slot[0].stream);
     if (e != hipSuccess) {
         fb_free(fb);
@@ -1406,7 +860,7 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
     const size_t NQ = bdpt_queue_cap(fb) * (size_t)B;
     // spill columns: one per ray of the widest closest-hit launch (2 NQ) and one per wave of the
     // grid-stride visibility launch (mcrt::BDPT_VIS_MAX_WAVES)
-    const size_t spillWords = (std::max(2 * NQ, (size_t)mcrt::BDPT_VIS_MAX_WAVES * 64) + 63) / 64 * 64 * (size_t)s->spillCap;
+    const size_t spillWords = (std::max(2 * NQ, (size_t)mcrt::BDPT_VIS_MAX_WAVES * 64) + 63) / 64 * 64 * (size_t)mcrt::accel_spill_cap(s);
     HIPCHK(ctx, bs.spill.grow(spillWords, st));
     TraceCtx tcs = trace_ctx(s);
     tcs.spill = bs.spill.get();
@@ -1442,9 +896,10 @@ static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_cam
     // k_bdpt_vertex, sorted below, walked through the permutation by k_extend
     b.extKey = nullptr;
     b.extSlot = nullptr;
+    const float* box = mcrt::accel_world_box(s);
     for (int a = 0; a < 3; ++a) {
-        const float ext = s->bbHi[a] - s->bbLo[a];
-        b.keyLo[a] = s->bbLo[a];
+        const float ext = box[3 + a] - box[a];
+        b.keyLo[a] = box[a];
         b.keyScale[a] = ext > 0.0f ? (a == 1 ? 8.0f : 32.0f) / ext : 0.0f;
     }
     b.cams = dCam;
@@ -1587,7 +1042,7 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
     if (!s || !fb || !cam || !p) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
     mcrt_ctx ctx = s->ctx;
     if (fb->ctx != ctx) return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame buffer belongs to another context");
-    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
+    if (!accel_ready(s)) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
     if (count < 1 || count > MCRT_MAX_BATCH_FRAMES)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame count must be 1 .. MCRT_MAX_BATCH_FRAMES (256)");
     if (p->integrator == MCRT_INTEGRATOR_BDPT && count > MCRT_MAX_BDPT_BATCH_FRAMES)
@@ -1664,7 +1119,7 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
         slot_free(slot);
         HIPCHK(ctx, slot_alloc(slot, fb->N, bdpt_queue_cap(fb), count, qNeed));
     }
-    const int cap = s->spillCap;
+    const int cap = mcrt::accel_spill_cap(s);
     const size_t spillRays = (std::max((size_t)bandPaths, 2 * qNeed + 64) + 63) / 64 * 64;
     HIPCHK(ctx, slot.spill.grow(spillRays * cap, slot.stream));
     hipStream_t st = slot.stream;
@@ -1793,7 +1248,7 @@ MCRT_API mcrt_status mcrt_render_aov(mcrt_scene s, mcrt_framebuffer fb, const mc
                                      const mcrt_frame_params* p, int aov, float* host_out) {
     if (!s || !fb || !cam || !p || !host_out) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
     mcrt_ctx ctx = s->ctx;
-    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
+    if (!accel_ready(s)) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
     if (aov != MCRT_AOV_ALBEDO && aov != MCRT_AOV_TEXTURE_LOD) return fail(ctx, MCRT_ERROR_INVALID_ARG, "unknown aov");
     if (cam->width != fb->W || cam->height != fb->H)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");

@@ -530,7 +530,7 @@ static mcrt_status render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
     if (!s || !fb || !cam || !p) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
     mcrt_ctx ctx = s->ctx;
     if (fb->ctx != ctx) return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame buffer belongs to another context");
-    if (!s->dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
+    if (!mcrt::accel_ready(s)) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
     if (cam->width != fb->W || cam->height != fb->H)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "camera size differs from the frame buffer");
     FrameArgs f;

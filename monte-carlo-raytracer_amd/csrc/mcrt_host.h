@@ -2,8 +2,9 @@
 // the few helpers of mcrt_capi.cpp that host code in another file may call.  Not part of the ABI.
 //
 // This is the boundary for host code outside mcrt_capi.cpp: a subsystem with entry points of its
-// own (mcrt_denoise.hip) includes it, reaches the runtime through what is declared here and
-// nothing else, and keeps its state in one struct held by the frame buffer.  It compiles as plain
+// own (mcrt_denoise.hip, mcrt_accel.cpp) includes it, reaches the runtime through what is declared
+// here and nothing else, and keeps its state in one struct held by the frame buffer (DenoiseState)
+// or the scene (AccelState).  It compiles as plain
 // C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip translation unit.
 #pragma once
 #include <climits>
@@ -48,6 +49,38 @@ struct mcrt_ctx_s {
     int64_t items[K_COUNT] = {};
 };
 
+// The acceleration structure of a scene (mcrt_accel.cpp), written by mcrt_accel_build's commit and
+// mcrt_accel_update_transforms.  Only mcrt_accel.cpp names its fields; the rest of the runtime
+// goes through the views and accessors declared below.
+struct AccelState {
+    DevBuf<float4> dNodes;     // 4 float4 per record; empty: no structure
+    mcrt::TreeInfo tree;       // counts, depth, layout, builder, world box
+    // compact records of the flat tree (TraceCtx::qnodes; mcrt::build_qnodes), empty when not built
+    DevBuf<float4> dQNodes;
+    uint32_t qRoot = 0;
+    bool packets = false;      // coherent launches as wave packets
+    double buildMs = 0.0;
+    // traversal scratch
+    DevBuf<uint32_t> dSpill;   // spillCap words per ray (ensure_spill)
+    int spillCap = 0;
+    DevBuf<int> dScratch;      // work counters for API queries
+    // occluder hints of the shadow rays after bounce 0, by origin cell (TraceCtx::hint, flat trees):
+    // allocated on the first shadow launch that uses hints (ensure_hint_cell), 2^hintBits words
+    DevBuf<uint32_t> dHintCell;
+    int hintBits = 0;
+    bool hintAllocFailed = false;   // no memory for the table: hints stay off for this structure
+    // transform updates (mcrt_accel_update_transforms): the options of the last mcrt_accel_build
+    // (without its world_to_local pointer), the two-level build's refit state, the device top-level
+    // builder's arrays (made by the first update that takes the device path)
+    mcrt_accel_opts lastOpts = {};
+    bool haveOpts = false;
+    mcrt::Bvh2lTop top2l;
+    mcrt::TopBuildDev* topDev = nullptr;
+    int updatePath = 0;
+    double updateMs = 0.0;
+    ~AccelState() { mcrt::top_build_destroy(topDev); }   // the buffers free themselves
+};
+
 struct mcrt_scene_s {
     mcrt_ctx ctx = nullptr;
     // host copies needed for the BVH build and dynamic updates
@@ -70,43 +103,10 @@ struct mcrt_scene_s {
     DevBuf<uint32_t> dSurfMeshes;   // build scratch: startIdx | startVertex | base per distinct mesh
     uint32_t numLights = 0, numMaterials = 0, numTextures = 0;
     bool hasSobol = false;
-    // BVH
-    DevBuf<float4> dNodes;     // 4 float4 per record
-    bool packets = false;      // coherent launches as wave packets (finish_accel)
-    uint64_t numNodes = 0;
-    uint32_t numTris = 0;
-    double buildMs = 0.0;
-    int builder = 0;   // which builder made the flat structure: 0 host, 1 device LBVH, 2 device SAH
-    int bvhDepth = 0;
-    bool twoLevel = false;          // instanced scene: two-level records (mcrt_bvh2l.cpp)
-    int numMeshes = 0, numInstances = 0;
-    // traversal scratch
-    DevBuf<uint32_t> dSpill;   // spillCap words per ray (ensure_spill)
-    int spillCap = 0;
-    DevBuf<int> dScratch;      // work counters for API queries
-    float bbLo[3] = {0, 0, 0}, bbHi[3] = {0, 0, 0};   // world bounds (root record of the BVH)
-    // occluder hints of the shadow rays after bounce 0, by origin cell (TraceCtx::hint, flat trees):
-    // allocated on the first shadow launch that uses hints (ensure_hint_cell), 2^hintBits words
-    DevBuf<uint32_t> dHintCell;
-    int hintBits = 0;
-    // compact records of the flat tree (TraceCtx::qnodes; mcrt::build_qnodes), empty when not built
-    DevBuf<float4> dQNodes;
-    uint32_t qRoot = 0;
-    bool hintAllocFailed = false;   // no memory for the table: hints stay off for this scene
-    // transform updates (mcrt_accel_update_transforms): the options of the last mcrt_accel_build
-    // (without its world_to_local pointer), the two-level build's refit state, the device top-level
-    // builder's arrays (made by the first update that takes the device path)
-    mcrt_accel_opts lastOpts = {};
-    bool haveOpts = false;
-    mcrt::Bvh2lTop top2l;
-    uint64_t topNodes = 0;
-    mcrt::TopBuildDev* topDev = nullptr;
-    int updatePath = 0;
-    double updateMs = 0.0;
+    AccelState accel;   // the acceleration structure and what is sized by it (mcrt_accel.cpp)
     // previous poses (mcrt_scene_motion_snapshot): one record per shape, allocated by the first
     // snapshot; only k_guides_motion receives it
     DevBuf<PrevPose> dPrevPose;
-    ~mcrt_scene_s() { mcrt::top_build_destroy(topDev); }   // the buffers free themselves
 };
 
 // One frame in flight (PT): the per-frame buffers of mcrt_render_frame, its own stream and
@@ -263,10 +263,32 @@ hipError_t fb_sync(mcrt_framebuffer fb);
 // that reads or rewrites slot buffers: BDPT, AOVs, device copies).
 void ctx_wait_slots(mcrt_framebuffer fb);
 bool frame_args(mcrt_framebuffer fb, const mcrt_frame_params* p, FrameArgs& f, std::string& err);
+// mcrt_accel.cpp: the views of the scene's acceleration structure and the little else of it that
+// the rest of the runtime reads
+bool accel_ready(mcrt_scene s);            // mcrt_accel_build has made a structure
+const float4* accel_nodes(mcrt_scene s);   // its records (SceneArgs::nodes)
+int accel_spill_cap(mcrt_scene s);         // spill entries per ray the tree's depth asks for
+const float* accel_world_box(mcrt_scene s);   // lo xyz, hi xyz
 // Per-ray spill columns for `rays` rays (rounded up to whole waves); grown on demand.
 bool ensure_spill(mcrt_scene s, size_t rays);
+// the per-ray walks' view
+TraceCtx trace_ctx(mcrt_scene s);
 // the coherent launches' view (camera rays, bounce-0 shadow rays): wave packets when the tree allows
 TraceCtx packet_ctx(mcrt_scene s);
+// Occluder hints for a shadow launch (mcrt_traverse.h hintOccludes; flat trees only): bounce-0 rays
+// by pixel (table `pix`, n pixels), later ones by origin cell; MCRT_SHADOW_HINTS=0 turns them off
+void with_hints(TraceCtx& c, mcrt_scene s, uint32_t* pix, uint32_t n);
+// a new hint table (the scene's by cell, a frame buffer's by pixel) filled with "no hint"
+hipError_t fill_hints(uint32_t* d, size_t n, uint32_t range, hipStream_t st);
+// `count` host elements into the (empty) buffer; S is T or the C ABI's name for it
+template <class T, class S>
+hipError_t upload(DevBuf<T>& dst, const S* src, size_t count, hipStream_t st) {
+    static_assert(sizeof(S) == sizeof(T), "same element");
+    if (!src || count == 0) return hipSuccess;
+    hipError_t e = (hipError_t)dst.alloc(count);
+    if (e != hipSuccess) return e;
+    return hipMemcpyAsync(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice, st);
+}
 SceneArgs scene_args(mcrt_scene s);
 // Allocates the plane (one T per pixel, zero-filled on the context stream) when it does not exist yet.
 template <class T>

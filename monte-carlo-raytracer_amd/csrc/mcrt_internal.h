@@ -213,7 +213,7 @@ void launch_band_unpack(const FrameArgs& f, int maxRows, const float* recv, floa
 void launch_denoise(int W, int H, int r, float ss, float sr, const float4* in, float4* out, hipStream_t st);
 void launch_tonemap(int n, float Lwhite, const float4* in, float4* out, hipStream_t st);
 void launch_stream_copy(const float4* src, float4* dst, size_t n4, int numCUs, hipStream_t st);
-// parent index of each triangle leaf into its record's word 13 (flat trees, finish_accel)
+// parent index of each triangle leaf into its record's word 13 (flat trees, mcrt_accel.cpp finish)
 void launch_leaf_parents(float4* nodes, uint32_t n, hipStream_t st);
 // order[0..n) = tiles by descending cost[tile] (bucketed; one workgroup)
 void launch_tile_order(const uint32_t* cost, int n, uint32_t* order, hipStream_t st);
@@ -272,19 +272,23 @@ namespace mcrt {
 void set_last_error(const std::string& msg);
 }
 // Host BVH builder (mcrt_bvh.cpp)
+#include <cstdlib>
 namespace mcrt {
 struct BvhOut {
     // GPU layout
     std::size_t numNodes = 0;
     std::size_t numTris = 0;
-    float* nodes = nullptr;   // 16 floats per node
-    float* tris = nullptr;    // unused (leaves live in `nodes`)
+    float* nodes = nullptr;   // 16 floats per node (the leaves live here too), malloc'd by build_bvh
     int depth = 0;
+    BvhOut() = default;
+    BvhOut(const BvhOut&) = delete;
+    BvhOut& operator=(const BvhOut&) = delete;
+    ~BvhOut() { std::free(nodes); }
 };
 // world-space triangles (9 floats each), shape id / prim id per triangle
 bool build_bvh(const float* tri, const int32_t* shapeOf, const int32_t* primOf, std::size_t n, float cost, int bins,
                bool sah, int threads, BvhOut& out, bool axes3 = false);
-void free_bvh(BvhOut& out);
+void free_bvh(BvhOut& out);   // early release; the destructor frees what is left
 }  // namespace mcrt
 // Host two-level (instanced) build (mcrt_bvh2l.cpp)
 namespace mcrt {
@@ -326,4 +330,46 @@ void top_build_destroy(TopBuildDev* d);
 // the input is one the device path does not take and the records are unspecified
 hipError_t top_build_run(TopBuildDev* d, const mcrt_shape* dShapes, const mcrt_mat4* dWorldToLocal, float4* nodes,
                          hipStream_t st, int* depth, float* topBox, const char** why);
+}  // namespace mcrt
+// The acceleration structure's host layer (mcrt_accel_host.cpp): no device, no context.  What
+// mcrt_accel_build uploads and what mcrt_accel_build_host_records returns is one build_host_tree.
+namespace mcrt {
+// The options of one build, parsed once (make_accel_plan); these are the defaults of NULL opts
+struct AccelPlan {
+    float cost = 10.0f;
+    int bins = 64;
+    bool sah = true;
+    int deviceBuild = 0;      // mcrt_accel_opts.device_build
+    bool twoLevel = false;    // IntersectorTwoLevel when forced or when a mesh is shared, unless flat is forced
+                              // (CalcIntersectionDevice::Preprocess, RR/src/device/calc_intersection_device.cpp:68-105)
+    const mcrt_mat4* worldToLocal = nullptr;   // the caller's array, not kept
+};
+// false: num_bins outside 2..4096
+bool make_accel_plan(const mcrt_accel_opts* opts, const mcrt_shape* shapes, std::size_t n, AccelPlan& plan);
+// Every shape's index range inside the index array, then every vertex it names inside the vertex
+// array: 0, or 1 (an index range) / 2 (a vertex index) with the offending shape in *badShape
+int check_shape_ranges(const mcrt_shape* shapes, std::size_t n, const uint32_t* indices, uint64_t numIndices,
+                       uint64_t numVertices, uint32_t* badShape);
+// same shapes but for transforms and surface data; two-level: the mesh key must not move
+bool same_topology(const mcrt_shape* a, const mcrt_shape* b, std::size_t n, bool twoLevel);
+// box (lo xyz, hi xyz) of a flat tree from its root record: the two child boxes, or the lone triangle
+void root_record_box(const float* rec16, float* box);
+// What describes a built structure, whichever builder made it
+struct TreeInfo {
+    std::size_t numNodes = 0, topNodes = 0, numTris = 0;
+    int depth = 0, numMeshes = 0, numInstances = 0;
+    bool twoLevel = false;   // instanced scene: two-level records (mcrt_bvh2l.cpp)
+    int builder = 0;         // of a flat tree: 0 host, 1 device LBVH, 2 device SAH, 4 host 3-axis SAH
+    float box[6] = {};       // world bounds (lo xyz, hi xyz)
+};
+struct HostTree : TreeInfo {
+    const float* records = nullptr;   // 16 floats per record, owned by one of:
+    BvhOut flat;                      //   a flat tree
+    std::vector<float> two;           //   a two-level tree
+    Bvh2lTop top;                     // two-level: the refit state
+};
+// The host build of the plan's tree over range-checked shapes; MCRT_ERROR_INVALID_ARG (and the
+// thread's last error) when there is nothing to build
+mcrt_status build_host_tree(const AccelPlan& plan, const mcrt_shape* shapes, std::size_t n, const uint32_t* indices,
+                            const mcrt_float4* positions, HostTree& out);
 }  // namespace mcrt

@@ -194,7 +194,7 @@ MCRT_DEV int traverseOct(const float4* __restrict__ nodes, const TraceRay& r, f3
 // busy 0.85, profiles/pmc_latest.json round 5; this layout halves the scalar instructions of an
 // internal step, profiles/r05/ab/README.txt item 12.)  A level pushes at most 2 entries, so a tree
 // of depth D (leaves at level D) needs 2 D entries: the host takes this path for 2 D <= MCRT_PK_STACK
-// = 64 (mcrt_capi.cpp finish_accel).
+// = 64 (mcrt_accel.cpp finish).
 typedef float __attribute__((ext_vector_type(4))) PkV4;
 typedef const __attribute__((address_space(4))) PkV4* PkNodes;   // uniform loads -> s_load
 static_assert(MCRT_PK_STACK == 64, "the packet stack is one VGPR lane per entry");

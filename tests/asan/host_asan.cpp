@@ -1,5 +1,6 @@
 // Sanitizer run of the host-side code (no GPU): OBJ/MTL ingestion (mcrt_objload.cpp), the host camera
-// (mcrt_camera.cpp), the host Bvh2 restatement (mcrt_bvh.cpp) and the oracle (oracle/mcrt_oracle.c:
+// (mcrt_camera.cpp), the host Bvh2 restatement (mcrt_bvh.cpp), the acceleration structure's host layer
+// (mcrt_accel_host.cpp over mcrt_bvh.cpp and mcrt_bvh2l.cpp) and the oracle (oracle/mcrt_oracle.c:
 // BVH build, closest / any-hit traversal against brute force, one PT and one BDPT frame, accumulate,
 // denoise, tone map) and the runtime's owning device-buffer type (mcrt_devbuf.h, over malloc / free), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
 // every check held and the sanitizers reported nothing (they abort on the first finding).
@@ -117,6 +118,141 @@ static int devbuf_checks() {
         CHECK(t.a.size() == 8 && !s.a && g_frees == freesBefore + 4);
     }
     CHECK(g_allocs == g_frees && g_allocs == 10);
+    return 0;
+}
+
+// The acceleration structure's host layer (mcrt_accel_host.cpp) through its two entry points:
+// every route and every rejected input, each with the status it has always returned.  The record
+// buffers are sized exactly, so a copy past max_records is a sanitizer finding.
+static mcrt_shape shape_at(float x, uint32_t startIdx, uint32_t startVertex, uint32_t numTriangles) {
+    mcrt_shape s;
+    std::memset(&s, 0, sizeof(s));
+    const mcrt_mat4 id = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
+    s.toWorldTransform = id;
+    s.toWorldTransform.m0.w = x;
+    s.toWorldInverseTranspose = id;
+    s.toWorldInverseTranspose.m3.x = -x;
+    s.startIdx = startIdx;
+    s.startVertex = startVertex;
+    s.numTriangles = numTriangles;
+    s.materialId = s.lightID = -1;
+    return s;
+}
+
+static int accel_host_checks() {
+    // two meshes: a quad (vertices 0-3, indices 0-5) and a three-triangle fan (vertices 4-8, indices 6-14)
+    const mcrt_float4 pos[9] = {{0, 0, 0, 0}, {1, 0, 0, 0}, {1, 1, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0},
+                                {1, 0, 1.5f, 0}, {1, 1, 2, 0}, {0, 1, 1.5f, 0}, {-1, 0.5f, 1, 0}};
+    const uint32_t idx[15] = {0, 1, 2, 0, 2, 3, 0, 1, 2, 0, 2, 3, 0, 3, 4};
+    mcrt_scene_desc d;
+    std::memset(&d, 0, sizeof(d));
+    d.indices = idx;
+    d.num_indices = 15;
+    d.positions = pos;
+    d.num_vertices = 9;
+    const mcrt_accel_opts defaults = {10.0f, 64, 1, 0, 0, 0, nullptr};
+    uint64_t n = 0;
+    int32_t info[4];
+    auto build = [&](const mcrt_accel_opts* o, std::vector<float>& rec) {   // size query, then the records
+        n = 0;
+        if (mcrt_accel_build_host_records(&d, o, nullptr, 0, &n, info) != MCRT_OK) return false;
+        rec.assign(16 * n, 0.0f);
+        uint64_t n2 = 0;
+        return mcrt_accel_build_host_records(&d, o, rec.data(), n, &n2, nullptr) == MCRT_OK && n2 == n;
+    };
+    std::vector<float> rec, rec2;
+    auto same = [](const std::vector<float>& a, const std::vector<float>& b) {   // bit for bit: leaf marks are NaNs
+        return a.size() == b.size() && std::memcmp(a.data(), b.data(), 4 * a.size()) == 0;
+    };
+
+    // flat: two distinct meshes, 5 triangles; NULL options are the defaults
+    const mcrt_shape flat[2] = {shape_at(0.0f, 0, 0, 2), shape_at(3.0f, 6, 4, 3)};
+    d.shapes = flat;
+    d.num_shapes = 2;
+    CHECK(build(nullptr, rec) && n == 9 && info[0] == 0 && info[1] == 9 && info[3] == 0);
+    CHECK(build(&defaults, rec2) && same(rec2, rec));
+    mcrt_accel_opts o = defaults;
+    o.device_build = 4;   // the 3-axis tree
+    CHECK(build(&o, rec2) && n == 9);
+    o = defaults;
+    o.force_2level = 1;
+    CHECK(build(&o, rec2) && info[0] == 1 && info[3] == 2);
+    // a max_records smaller than the tree: that many records, the full count reported
+    std::vector<float> head(16 * 4);
+    n = 0;
+    CHECK(mcrt_accel_build_host_records(&d, nullptr, head.data(), 4, &n, info) == MCRT_OK && n == 9);
+    CHECK(std::memcmp(head.data(), rec.data(), 64 * 4) == 0);
+    // the refit of a flat structure is the fresh build of the moved shapes (startVertex may move)
+    const mcrt_shape flatMoved[2] = {shape_at(-2.0f, 0, 0, 2), shape_at(5.0f, 6, 4, 3)};
+    rec2.assign(16 * 9, 0.0f);
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, flatMoved, nullptr, rec2.data(), 9, &n, info) == MCRT_OK && n == 9);
+    d.shapes = flatMoved;
+    CHECK(build(nullptr, rec) && same(rec, rec2));
+    d.shapes = flat;
+    mcrt_shape changed[2] = {flat[0], flat[1]};
+    changed[1].numTriangles = 2;
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, changed, nullptr, nullptr, 0, &n, info) == MCRT_ERROR_INVALID_ARG);
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, nullptr, nullptr, nullptr, 0, &n, info) == MCRT_ERROR_INVALID_ARG);
+    // a single shape: flat, or two-level when forced
+    d.num_shapes = 1;
+    CHECK(build(nullptr, rec) && n == 3 && info[0] == 0);
+    o = defaults;
+    o.force_2level = 1;
+    CHECK(build(&o, rec) && info[0] == 1 && info[3] == 1);
+
+    // instanced: two shapes share the fan, one has the quad
+    const mcrt_shape inst[3] = {shape_at(0.0f, 6, 4, 3), shape_at(4.0f, 0, 0, 2), shape_at(8.0f, 6, 4, 3)};
+    d.shapes = inst;
+    d.num_shapes = 3;
+    CHECK(build(nullptr, rec) && info[0] == 1 && info[3] == 2 && info[1] == 5);
+    const uint64_t nTwo = n;
+    o = defaults;
+    o.force_flat = 1;
+    CHECK(build(&o, rec2) && info[0] == 0 && n == 2 * 8 - 1);
+    head.assign(16 * 2, 0.0f);
+    CHECK(mcrt_accel_build_host_records(&d, nullptr, head.data(), 2, &n, nullptr) == MCRT_OK && n == nTwo);
+    CHECK(std::memcmp(head.data(), rec.data(), 64 * 2) == 0);
+    // the refit of a two-level structure equals the fresh build of the moved shapes
+    const mcrt_shape instMoved[3] = {shape_at(1.0f, 6, 4, 3), shape_at(-4.0f, 0, 0, 2), shape_at(9.5f, 6, 4, 3)};
+    rec2.assign(16 * nTwo, 0.0f);
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, instMoved, nullptr, rec2.data(), nTwo, &n, info) == MCRT_OK);
+    CHECK(n == nTwo && info[0] == 1);
+    head.assign(16 * 2, 0.0f);
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, instMoved, nullptr, head.data(), 2, &n, nullptr) == MCRT_OK);
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, instMoved, nullptr, nullptr, 0, &n, nullptr) == MCRT_OK && n == nTwo);
+    d.shapes = instMoved;
+    CHECK(build(nullptr, rec) && same(rec, rec2) && std::memcmp(head.data(), rec.data(), 64 * 2) == 0);
+    d.shapes = inst;
+    mcrt_shape instChanged[3] = {inst[0], inst[1], inst[2]};
+    instChanged[1].startVertex = 1;   // the mesh key of a two-level structure must not move
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, instChanged, nullptr, nullptr, 0, &n, info) == MCRT_ERROR_INVALID_ARG);
+    instChanged[1] = inst[1];
+    instChanged[2].numTriangles = 1;
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, instChanged, nullptr, nullptr, 0, &n, info) == MCRT_ERROR_INVALID_ARG);
+
+    // rejected inputs
+    auto rejected = [&](const mcrt_accel_opts* opt) {
+        return mcrt_accel_build_host_records(&d, opt, nullptr, 0, &n, info) == MCRT_ERROR_INVALID_ARG;
+    };
+    for (int bins : {1, 4097}) {
+        o = defaults;
+        o.num_bins = bins;
+        CHECK(rejected(&o));
+    }
+    o.num_bins = 4096;
+    CHECK(!rejected(&o));
+    mcrt_shape bad[2] = {shape_at(0.0f, 0, 0, 2), shape_at(3.0f, 9, 4, 3)};   // indices 9..17 of 15
+    d.shapes = bad;
+    d.num_shapes = 2;
+    CHECK(rejected(nullptr));
+    bad[1] = shape_at(3.0f, 6, 5, 3);   // vertex 5 + 4 of 9
+    CHECK(rejected(nullptr));
+    CHECK(mcrt_accel_refit_host_records(&d, nullptr, bad, nullptr, nullptr, 0, &n, info) == MCRT_ERROR_INVALID_ARG);
+    bad[0].numTriangles = 0;
+    bad[1] = shape_at(3.0f, 6, 4, 0);   // no triangles: nothing for the flat route to build
+    CHECK(rejected(nullptr));
+    CHECK(mcrt_accel_build_host_records(&d, nullptr, nullptr, 0, nullptr, info) == MCRT_ERROR_INVALID_ARG);
+    CHECK(mcrt_accel_build_host_records(nullptr, nullptr, nullptr, 0, &n, info) == MCRT_ERROR_INVALID_ARG);
     return 0;
 }
 
@@ -257,6 +393,7 @@ int main() {
     CHECK(mcrt::build_bvh(tri.data(), shapeOf.data(), primOf.data(), nt, 10.0f, 64, true, 4, out));
     CHECK(out.numNodes == 2 * nt - 1);
     mcrt::free_bvh(out);
+    if (accel_host_checks() != 0) return 1;
 
     mcrt_obj_free(os);
     std::string cmd = "rm -rf " + d;

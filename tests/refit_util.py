@@ -77,7 +77,7 @@ def lattice_line(n_min, bins):
 
 
 def spill_blocks(depth):
-    """Spill blocks of 16 entries the traversal needs for a tree of this depth (finish_accel)."""
+    """Spill blocks of 16 entries the traversal needs for a tree of this depth (mcrt_accel.cpp apply_spill_cap)."""
     return (depth + 2 + 15) // 16
 
 

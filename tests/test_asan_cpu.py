@@ -1,8 +1,10 @@
 """Host-code sanitizer run (no GPU): tests/asan builds the C ABI's host parts (OBJ/MTL ingestion
-mcrt_objload.cpp, camera mcrt_camera.cpp, the host Bvh2 restatement mcrt_bvh.cpp) and the oracle with
+mcrt_objload.cpp, camera mcrt_camera.cpp, the host Bvh2 restatement mcrt_bvh.cpp, the acceleration
+structure's host layer mcrt_accel_host.cpp with mcrt_bvh2l.cpp) and the oracle with
 AddressSanitizer + UndefinedBehaviorSanitizer, then loads an OBJ/MTL scene, traces it against brute
-force, renders PT and BDPT frames, accumulates, denoises, tone-maps and builds a 30 k-triangle BVH
-on 4 threads.  Any sanitizer finding aborts the program."""
+force, renders PT and BDPT frames, accumulates, denoises, tone-maps, builds a 30 k-triangle BVH
+on 4 threads and takes mcrt_accel_build_host_records / mcrt_accel_refit_host_records through every
+route and every rejected input.  Any sanitizer finding aborts the program."""
 import os
 import subprocess
 

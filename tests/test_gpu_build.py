@@ -143,3 +143,69 @@ def test_perf_tree_frames_within_reference_tolerance(hip_ctx, which):
     miss0, miss1 = hits[0]["shapeid"] < 0, hits[1]["shapeid"] < 0
     np.testing.assert_array_equal(miss0, miss1)
     np.testing.assert_array_equal(t0[~miss0], t1[~miss1])
+
+
+def test_every_route_in_sequence_on_one_scene(hip_ctx):
+    """One DeviceScene of the instanced edge scene rebuilt through every route in turn -- natural
+    two-level, the flat device SAH, its fallback to the host (65 bins), the device LBVH, the host
+    SAH, the host 3-axis tree, two-level again, then a transform update -- so that each build has
+    to drop what the one before left (instance counts, the top level's refit state, compact
+    records, packets).  After every step: builder / layout / counts are the route's, the records are
+    the host build's of the same options as uint32 (a flat leaf's word 13 aside: its parent's index
+    on the device, -1 on the host; the LBVH is another tree and is not compared), the compact
+    records exist exactly on the flat depth-first routes, and the rays of every family pass the
+    float64 truth with 0 strong and 0 weak failures (K on flat trees, K_2L on two-level ones)."""
+    import ray_truth as rt
+    import refit_util as ru
+    from mcrt import lib
+    from test_gpu_ray_truth import Case, _both_orders, shared_case
+    case = shared_case("instanced")
+    sc = case.scene
+    ntri = sc.num_triangles
+    mats = [np.array(m, np.float32) for m in sc.shapes["toWorldTransform"]]
+    mats[1] = ru.translate((2.0, 0.5, 3.0)) @ mats[1]
+    moved = Case(ru.with_transforms(sc, mats))
+    flat = {"force_flat": True}
+    # (what, options, builder, compared with the host build, compact records)
+    steps = [("two-level", {}, 0, True, False),
+             ("flat device SAH", flat, 2, True, True),
+             ("flat 65 bins", dict(flat, bins=65), 0, True, True),
+             ("flat LBVH", dict(flat, device_build=1), 1, False, False),
+             ("flat host SAH", dict(flat, device_build=3), 0, True, True),
+             ("flat 3-axis", dict(flat, device_build=4), 4, True, True),
+             ("two-level again", {}, 0, True, False),
+             ("moved", None, 0, True, False)]
+    ds = lib.DeviceScene(hip_ctx, sc, build=False)
+    bad = []
+    try:
+        for what, o, builder, compare, compact in steps:
+            if o is None:
+                ds.update_transforms(moved.scene.shapes)
+                assert ds.update_info()["path"] == 2
+                o, now = {}, moved
+            else:
+                ds.build(**o)
+                now = case
+            two = 0 if o.get("force_flat") else 1
+            want, winfo = lib.build_host_records(now.scene, **o)
+            info, lay = ds.info(), ds.layout()
+            print(f"{what}: builder {ds.builder()}, layout {lay}, info {info}, host {winfo}")
+            assert ds.builder() == builder, what
+            assert winfo["two_level"] == two and lay["two_level"] == two, what
+            assert lay["meshes"] == winfo["meshes"] == (1 if two else 0), what
+            assert lay["instances"] == (len(sc.shapes) - 1 if two else 0), what
+            assert info["triangles"] == ntri and info["nodes"] == (len(want) if two else 2 * ntri - 1), what
+            assert info["bytes"] > 64 * info["nodes"] if compact else info["bytes"] == 64 * info["nodes"], what
+            if compare:
+                got = ds.records()
+                if not two:
+                    leaf = got.view(np.int32)[:, 12] < 0
+                    got.view(np.int32)[leaf, 13] = -1
+                differ = (got.view(np.uint32) != want.view(np.uint32)).any(1) if got.shape == want.shape else None
+                print(f"{what}: records {got.shape} host {want.shape}, differing {None if differ is None else int(differ.sum())}")
+                assert differ is not None and not differ.any(), what
+                assert lay["depth"] == winfo["depth"], what
+            bad += _both_orders(hip_ctx, ds, now, now.truth(rt.K_2L if two else rt.K), what)
+    finally:
+        ds.close()
+    assert not bad, "\n".join(bad)

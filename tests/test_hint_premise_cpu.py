@@ -9,7 +9,7 @@ Checked for every flat builder: the host restatement of the reference's Bvh2 (de
 which the device SAH build reproduces byte for byte) and the host 3-axis perf tree (4) here; the
 device LBVH (1) and the device SAH build (2) on the GPU (test_gpu_shadow_hints.py).  The same
 walk checks each builder's reported depth, which bounds the wave-packet stack (2 entries per
-level, mcrt_capi.cpp finish_accel): it must not be below the deepest leaf's level."""
+level, mcrt_accel.cpp finish): it must not be below the deepest leaf's level."""
 import numpy as np
 import pytest
 

@@ -7,7 +7,7 @@ DESIGN.md) and writes profiles/refit/refit_time.json.
    it at every update).
 2. Device against host top build: synthetic top levels of single-triangle instances; "threshold" is
    the smallest measured count at which the device path wins (MCRT_TOP_DEVICE_MIN_SHAPES in
-   csrc/mcrt_capi.cpp).
+   csrc/mcrt_accel.cpp).
 
 Each figure is the median of --runs runs, synchronised before and after.
 usage: python tools/refit_time.py [--runs 10] [--sizes 1000,10000,100000,1000000] [--out FILE]"""

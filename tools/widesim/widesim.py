@@ -44,7 +44,7 @@ def load():
 
 def world_triangles(sc):
     """(n, 9) float32 world-space triangles in shape order and the shapes' first triangle, with
-    the host build's arithmetic (mcrt_capi.cpp xformPoint: separately rounded float32 ops)."""
+    the host build's arithmetic (mcrt_accel_host.cpp xformPoint: separately rounded float32 ops)."""
     f32 = np.float32
     tris, first, acc = [], [], 0
     for s in sc.shapes:
