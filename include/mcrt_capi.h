@@ -299,11 +299,25 @@ MCRT_API mcrt_status mcrt_ctx_gather_chase_compact(mcrt_ctx ctx, uint64_t record
  * SetTransform/Commit: APP/raytracing/scene/RTScene.cpp:28-56,199-267,564-809;
  * RR/include/radeon_rays.h:214-237).                                        */
 /* ------------------------------------------------------------------------ */
+/* Accepted ranges, checked on the host before anything is uploaded: a shape's materialId in
+ * -1 .. num_materials-1 (-1: no material) and lightID in -1 .. num_lights-1 (-1: not an emitter);
+ * each of a material's eight texture ids in -1 .. num_textures-1 (-1: none), whatever its type; a
+ * mesh light's shapeId names a shape with triangles; every index range inside the index array and
+ * every vertex it names inside the vertex array.  MCRT_ERROR_INVALID_ARG otherwise, with a message
+ * that names the entry.  num_lights = 0 is legal: both integrators return zeros. */
 MCRT_API mcrt_status mcrt_scene_create(mcrt_ctx ctx, const mcrt_scene_desc* desc, mcrt_scene* out);
 MCRT_API mcrt_status mcrt_scene_destroy(mcrt_scene scene);
 /* Dynamic updates (RTScene::update, APP/raytracing/scene/RTScene.cpp:317-391). Shapes
  * whose transforms change go through mcrt_accel_update_transforms (below), which replaces the
  * shapes and brings the acceleration structure up to date in one call. */
+/* Each update is checked against the tables the scene holds before any state changes, with the
+ * ranges of mcrt_scene_create; a rejected call (MCRT_ERROR_INVALID_ARG) leaves the scene as it was.
+ * _lights: every shape's lightID in -1 .. n-1, mesh lights name a shape with triangles; n = 0 is
+ * legal while no shape holds a light id.  _materials: every shape's materialId in -1 .. n-1, the
+ * new materials' texture ids in -1 .. num_textures-1; n = 0 is legal while no shape names a
+ * material.  _shapes (and mcrt_accel_update_transforms): same count, startIdx and numTriangles;
+ * materialId and lightID in the current tables' ranges; a moved startVertex keeps every vertex
+ * the shape names inside the vertex array. */
 MCRT_API mcrt_status mcrt_scene_update_lights(mcrt_scene scene, const mcrt_light* lights, uint32_t n);
 MCRT_API mcrt_status mcrt_scene_update_materials(mcrt_scene scene, const mcrt_material* m, uint32_t n);
 MCRT_API mcrt_status mcrt_scene_update_shapes(mcrt_scene scene, const mcrt_shape* s, uint32_t n);
@@ -898,6 +912,7 @@ static_assert(sizeof(mcrt_intersection) == 32, "RR Intersection is 32 B");
 static_assert(sizeof(mcrt_filter) == 56, "RTFilterProperties (device) is 56 B");
 static_assert(offsetof(mcrt_material, uber_roughness) == 80, "roughness @80");
 static_assert(offsetof(mcrt_material, uber_normalMapId) == 96, "normalMapId @96");
+static_assert(offsetof(mcrt_material, uber_iorTexId) == 96 + 28, "the eight texture ids are consecutive: iorTexId @124");
 static_assert(offsetof(mcrt_camera, width) == 160, "width @160");
 static_assert(offsetof(mcrt_filter, radius) == 8, "radius @8 (device)");
 static_assert(offsetof(mcrt_filter, mitchellB) == 16, "B @16 (device)");

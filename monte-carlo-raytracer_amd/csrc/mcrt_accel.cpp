@@ -286,6 +286,7 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
     if (!a.dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
     if (!mcrt::same_topology(sh, s->shapes.data(), n, a.tree.twoLevel))
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "shape topology must not change");
+    if (const mcrt_status st = mcrt::check_updated_shapes(s, sh, n)) return st;   // before any state changes
     const auto t0 = Clock::now();
     hipSetDevice(ctx->device);
     // after every launch that reads the records or the shapes: the context stream and the
@@ -308,8 +309,8 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
         return done(3);
     }
     // the mesh keys are unchanged, so the surface records and their bases are too
-    s->shapes.assign(sh, sh + n);
     HIPCHK(ctx, hipMemcpy(s->dShapes.get(), sh, sizeof(mcrt_shape) * n, hipMemcpyHostToDevice));
+    s->shapes.assign(sh, sh + n);
     const mcrt::Bvh2lTop& top = a.top2l;
     const char* env = std::getenv("MCRT_TOP_BUILD");
     const bool forceHost = env && std::strcmp(env, "host") == 0;

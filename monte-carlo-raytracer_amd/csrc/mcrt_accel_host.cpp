@@ -46,6 +46,52 @@ int check_shape_ranges(const mcrt_shape* shapes, std::size_t n, const uint32_t* 
     return 0;
 }
 
+int check_scene_tables(const SceneTables& t, uint32_t* entry, uint32_t* slot) {
+    uint32_t none;
+    uint32_t& at = entry ? *entry : none;
+    uint32_t& sl = slot ? *slot : none;
+    at = sl = 0;
+    auto outside = [](int32_t id, std::size_t n) { return id < -1 || (id >= 0 && (std::size_t)id >= n); };
+    if (t.indices)
+        if (const int bad = check_shape_ranges(t.shapes, t.numShapes, t.indices, t.numIndices, t.numVertices, &at)) return bad;
+    for (at = 0; at < t.numShapes; ++at) {
+        if (outside(t.shapes[at].materialId, t.numMaterials)) return TABLE_MATERIAL_ID;
+        if (outside(t.shapes[at].lightID, t.numLights)) return TABLE_LIGHT_ID;
+    }
+    for (at = 0; t.materials && at < t.numMaterials; ++at) {   // whatever the type: normal mapping runs before the type test
+        const mcrt_material& m = t.materials[at];
+        const int32_t ids[8] = {m.uber_normalMapId, m.uber_diffuseTexId, m.uber_glossyTexId, m.uber_specReflectionTexId,
+                                m.uber_transmissionTexId, m.uber_opacityTexId, m.uber_roughnessTexId, m.uber_iorTexId};
+        for (sl = 0; sl < 8; ++sl)
+            if (outside(ids[sl], t.numTextures)) return TABLE_TEXTURE_ID;
+    }
+    sl = 0;
+    for (at = 0; t.lights && at < t.numLights; ++at) {
+        const mcrt_light& L = t.lights[at];
+        if (L.type == MCRT_TRIANGLE_MESH_AREA_LIGHT &&
+            (L.shapeId < 0 || (std::size_t)L.shapeId >= t.numShapes || t.shapes[L.shapeId].numTriangles == 0))
+            return TABLE_MESH_LIGHT;
+    }
+    at = 0;
+    return TABLE_OK;
+}
+
+std::string scene_tables_message(int rule, uint32_t entry, uint32_t slot) {
+    static const char* const slots[8] = {"normal map", "diffuse", "glossy", "specular reflection",
+                                         "transmission", "opacity", "roughness", "ior"};
+    const std::string e = std::to_string(entry);
+    switch (rule) {
+    case TABLE_OK: return "";
+    case TABLE_INDEX_RANGE: return "shape " + e + " indexes past the index array";
+    case TABLE_VERTEX_INDEX: return "vertex index out of range in shape " + e;
+    case TABLE_MATERIAL_ID: return "shape " + e + " has an invalid material id";
+    case TABLE_LIGHT_ID: return "shape " + e + " has an invalid light id";
+    case TABLE_TEXTURE_ID: return "material " + e + " has an invalid " + slots[slot & 7] + " texture id";
+    case TABLE_MESH_LIGHT: return "mesh light " + e + " has an invalid shape";
+    }
+    return "invalid scene tables";
+}
+
 bool same_topology(const mcrt_shape* a, const mcrt_shape* b, std::size_t n, bool twoLevel) {
     for (std::size_t i = 0; i < n; ++i)
         if (a[i].startIdx != b[i].startIdx || a[i].numTriangles != b[i].numTriangles ||

@@ -667,7 +667,9 @@ __global__ __launch_bounds__(BDPT_BLOCK) void k_bdpt_vertex(SceneArgs s, FrameAr
                 int sampledType = 0, numNonDelta = 0;
                 if (mat.type == 0)
                     fv = sampleUberBSDF(um, cur.fr, bsdfSample, wo, &wi, &pdfFwd, &sampledType, mode, &numNonDelta);
-                if (numNonDelta > 0) cur.flags |= VF_CONNECTIBLE;
+                // sampleMaterial (materials.cl:144-156) leaves numNonDeltaTypes unset for another type and
+                // BDPT.cl:415 reads it: the reference's compiled kernel marks such a vertex connectible
+                if (numNonDelta > 0 || mat.type != 0) cur.flags |= VF_CONNECTIBLE;
                 if (isBlack(fv) || isNearZero(pdfFwd)) {
                     storeVertex(V, depth, pix, N, cur);
                 } else {

@@ -194,6 +194,37 @@ static mcrt_status replace_array(mcrt_scene s, DevBuf<T>& dst, const T* src, siz
     return MCRT_OK;
 }
 
+// An update's tables against the ones the scene keeps: `t` holds the replaced table and the counts
+// after the update; the scene's current shapes are filled in here.  Nothing is changed.
+static mcrt_status check_update(mcrt_scene s, mcrt::SceneTables t) {
+    if (!t.shapes) {
+        t.shapes = s->shapes.data();
+        t.numShapes = s->shapes.size();
+    }
+    uint32_t at = 0, slot = 0;
+    if (const int bad = mcrt::check_scene_tables(t, &at, &slot))
+        return fail(s->ctx, MCRT_ERROR_INVALID_ARG, mcrt::scene_tables_message(bad, at, slot));
+    return MCRT_OK;
+}
+
+mcrt_status mcrt::check_updated_shapes(mcrt_scene s, const mcrt_shape* sh, uint32_t n) {
+    mcrt::SceneTables t;   // the new shapes against the current counts
+    t.shapes = sh;
+    t.numShapes = n;
+    t.numMaterials = s->numMaterials;
+    t.numLights = s->numLights;
+    t.numTextures = s->numTextures;
+    const mcrt_status st = check_update(s, t);
+    if (st != MCRT_OK) return st;
+    // the index ranges are the topology's and stay; a moved startVertex moves the vertices a shape names
+    for (uint32_t i = 0; i < n; ++i) {
+        if (sh[i].startVertex == s->shapes[i].startVertex) continue;
+        if (mcrt::check_shape_ranges(&sh[i], 1, s->indices.data(), s->indices.size(), s->positions.size(), nullptr))
+            return fail(s->ctx, MCRT_ERROR_INVALID_ARG, mcrt::scene_tables_message(mcrt::TABLE_VERTEX_INDEX, i, 0));
+    }
+    return MCRT_OK;
+}
+
 // ---------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------
@@ -433,21 +464,23 @@ MCRT_API mcrt_status mcrt_scene_create(mcrt_ctx ctx, const mcrt_scene_desc* d, m
     if (d->num_shapes == 0 || !d->shapes) return fail(ctx, MCRT_ERROR_INVALID_ARG, "scene has no shapes");
     if (!d->indices || !d->positions || !d->uvs || !d->normals)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "indices/positions/uvs/normals are required");
-    uint32_t at = 0;
-    if (const int bad = mcrt::check_shape_ranges(d->shapes, d->num_shapes, d->indices, d->num_indices, d->num_vertices, &at))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, bad == 1 ? "shape " + std::to_string(at) + " indexes past the index array"
-                                                          : "vertex index out of range in shape " + std::to_string(at));
-    for (uint32_t i = 0; i < d->num_shapes; ++i) {
-        const mcrt_shape& s = d->shapes[i];
-        if (s.materialId >= (int)d->num_materials)
-            return fail(ctx, MCRT_ERROR_INVALID_ARG, "shape " + std::to_string(i) + " has an invalid material id");
-        if (s.lightID >= (int)d->num_lights) return fail(ctx, MCRT_ERROR_INVALID_ARG, "invalid light id");
-    }
-    for (uint32_t i = 0; i < d->num_lights; ++i) {
-        const mcrt_light& L = d->lights[i];
-        if (L.type == MCRT_TRIANGLE_MESH_AREA_LIGHT && (L.shapeId < 0 || L.shapeId >= (int)d->num_shapes ||
-                                                        d->shapes[L.shapeId].numTriangles == 0))
-            return fail(ctx, MCRT_ERROR_INVALID_ARG, "mesh light " + std::to_string(i) + " has an invalid shape");
+    if ((d->num_materials && !d->materials) || (d->num_lights && !d->lights) || (d->num_textures && !d->textures))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "a table with a non-zero count is NULL");
+    {
+        mcrt::SceneTables t;
+        t.shapes = d->shapes;
+        t.numShapes = d->num_shapes;
+        t.materials = d->materials;
+        t.numMaterials = d->num_materials;
+        t.lights = d->lights;
+        t.numLights = d->num_lights;
+        t.numTextures = d->num_textures;
+        t.indices = d->indices;
+        t.numIndices = d->num_indices;
+        t.numVertices = d->num_vertices;
+        uint32_t at = 0, slot = 0;
+        if (const int bad = mcrt::check_scene_tables(t, &at, &slot))
+            return fail(ctx, MCRT_ERROR_INVALID_ARG, mcrt::scene_tables_message(bad, at, slot));
     }
     for (uint32_t i = 0; i < d->num_textures; ++i) {
         const mcrt_texture_desc& t = d->textures[i];
@@ -499,14 +532,28 @@ MCRT_API mcrt_status mcrt_scene_destroy(mcrt_scene s) {
 
 MCRT_API mcrt_status mcrt_scene_update_lights(mcrt_scene s, const mcrt_light* lights, uint32_t n) {
     if (!s || (n && !lights)) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "invalid lights");
-    mcrt_status st = replace_array(s, s->dLights, lights, n);
+    mcrt::SceneTables t;   // the new lights against the current shapes
+    t.lights = lights;
+    t.numLights = n;
+    t.numMaterials = s->numMaterials;
+    t.numTextures = s->numTextures;
+    mcrt_status st = check_update(s, t);
+    if (st != MCRT_OK) return st;
+    st = replace_array(s, s->dLights, lights, n);
     if (st == MCRT_OK) s->numLights = n;
     return st;
 }
 
 MCRT_API mcrt_status mcrt_scene_update_materials(mcrt_scene s, const mcrt_material* m, uint32_t n) {
     if (!s || (n && !m)) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "invalid materials");
-    mcrt_status st = replace_array(s, s->dMaterials, m, n);
+    mcrt::SceneTables t;   // the new materials against the current shapes and texture count
+    t.materials = m;
+    t.numMaterials = n;
+    t.numLights = s->numLights;
+    t.numTextures = s->numTextures;
+    mcrt_status st = check_update(s, t);
+    if (st != MCRT_OK) return st;
+    st = replace_array(s, s->dMaterials, m, n);
     if (st == MCRT_OK) s->numMaterials = n;
     return st;
 }
@@ -517,9 +564,11 @@ MCRT_API mcrt_status mcrt_scene_update_shapes(mcrt_scene s, const mcrt_shape* sh
     for (uint32_t i = 0; i < n; ++i)
         if (sh[i].startIdx != s->shapes[i].startIdx || sh[i].numTriangles != s->shapes[i].numTriangles)
             return fail(s->ctx, MCRT_ERROR_INVALID_ARG, "shape topology must not change");
-    s->shapes.assign(sh, sh + n);
-    mcrt_status st = replace_array(s, s->dShapes, sh, n);
+    mcrt_status st = mcrt::check_updated_shapes(s, sh, n);
     if (st != MCRT_OK) return st;
+    st = replace_array(s, s->dShapes, sh, n);
+    if (st != MCRT_OK) return st;
+    s->shapes.assign(sh, sh + n);   // after the last check: a rejected call leaves the scene as it was
     HIPCHK(s->ctx, build_surface_records(s));   // startVertex may have moved
     return MCRT_OK;
 }

@@ -255,6 +255,10 @@ static const char* const kNoSlotBuffers = "the frame slot has no buffers (its la
 namespace mcrt {
 // records msg as the thread's and the context's (may be NULL) last error; returns code
 mcrt_status fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg);
+// The shapes of an update (same count and topology as the scene's, checked by the caller) against
+// the scene's current table counts (check_scene_tables), and a moved startVertex against the host
+// copies of the indices and the vertex count.  Changes nothing; MCRT_ERROR_INVALID_ARG names the shape.
+mcrt_status check_updated_shapes(mcrt_scene s, const mcrt_shape* shapes, uint32_t n);
 // An integer environment variable clamped to lo .. hi, or `def` when it is not set.
 int env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX);
 // Host reads and context-stream work that touch the slots: all slot streams first.

@@ -350,6 +350,36 @@ bool make_accel_plan(const mcrt_accel_opts* opts, const mcrt_shape* shapes, std:
 // array: 0, or 1 (an index range) / 2 (a vertex index) with the offending shape in *badShape
 int check_shape_ranges(const mcrt_shape* shapes, std::size_t n, const uint32_t* indices, uint64_t numIndices,
                        uint64_t numVertices, uint32_t* badShape);
+// The tables a scene holds, as the kernels index them.  Every id the kernels test against -1 and
+// then use as an index must be -1 or inside its table (check_scene_tables).
+struct SceneTables {
+    const mcrt_shape* shapes = nullptr;
+    std::size_t numShapes = 0;
+    const mcrt_material* materials = nullptr;
+    std::size_t numMaterials = 0;
+    const mcrt_light* lights = nullptr;
+    std::size_t numLights = 0;
+    std::size_t numTextures = 0;   // the material's texture ids index the texture table
+    const uint32_t* indices = nullptr;
+    uint64_t numIndices = 0, numVertices = 0;
+};
+enum TableRule {
+    TABLE_OK = 0,
+    TABLE_INDEX_RANGE = 1,    // check_shape_ranges 1
+    TABLE_VERTEX_INDEX = 2,   // check_shape_ranges 2
+    TABLE_MATERIAL_ID = 3,    // shape.materialId outside -1 .. numMaterials - 1
+    TABLE_LIGHT_ID = 4,       // shape.lightID outside -1 .. numLights - 1
+    TABLE_TEXTURE_ID = 5,     // one of a material's eight texture ids outside -1 .. numTextures - 1 (any type)
+    TABLE_MESH_LIGHT = 6,     // a mesh light's shapeId outside the shapes, or a shape without triangles
+};
+// The first rule the tables break (TABLE_OK: none) with the offending shape, material or light in
+// *entry and, for TABLE_TEXTURE_ID, the slot 0..7 in the material's field order in *slot.  Either
+// may be NULL.  A NULL materials, lights or indices pointer leaves that table's own entries unread
+// (an update that replaces one table checks the others' ids against its count alone).  No device,
+// no context.
+int check_scene_tables(const SceneTables& t, uint32_t* entry, uint32_t* slot);
+// The message of a broken rule, naming the entry
+std::string scene_tables_message(int rule, uint32_t entry, uint32_t slot);
 // same shapes but for transforms and surface data; two-level: the mesh key must not move
 bool same_topology(const mcrt_shape* a, const mcrt_shape* b, std::size_t n, bool twoLevel);
 // box (lo xyz, hi xyz) of a flat tree from its root record: the two child boxes, or the lone triangle

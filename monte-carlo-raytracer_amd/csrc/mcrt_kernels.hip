@@ -525,9 +525,13 @@ MCRT_DEV f3 shadePath(const SceneArgs& s, const FrameArgs& f, int bounce, int pi
         frame += k;
     }
     Sampler sampler = makeSampler(f.sampler, (uint32_t)px, frame, bounce, f.W, f.H, s.sobol);
-    const bool isUber = materialId != -1 && mat.type == 0;   // materials.cl:130-142: other types evaluate to 0
+    // materials.cl:130-142: other types evaluate to 0.  sampleMaterial (materials.cl:144-156) leaves
+    // pdf and the sampled type unset for them and PathTracing.cl:154 reads the pdf, so the
+    // reference's compiled kernel has no such path: it samples every material as the uber one.
+    const bool hasMat = materialId != -1;
+    const bool isUber = hasMat && mat.type == 0;
     Uber um;
-    if (isUber) um = uberProps(s, mat, si.uv, lod);
+    if (hasMat) um = uberProps(s, mat, si.uv, lod);
     // next-event estimation, one light (PathTracing.cl:107-136)
     {
         uint32_t lightIdx = (uint32_t)floorf(getSample1D(sampler) * s.numLights);
@@ -557,7 +561,7 @@ MCRT_DEV f3 shadePath(const SceneArgs& s, const FrameArgs& f, int bounce, int pi
     // extension (PathTracing.cl:138-175)
     if (EXT && bounce + 1 < f.maxDepth) {
         const f2 bsdfSample = getSample2D(sampler);
-        if (isUber) {
+        if (hasMat) {
             f3 wi;
             float pdf;
             int sampledType;

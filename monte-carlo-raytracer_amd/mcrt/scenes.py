@@ -812,6 +812,163 @@ def texture_zoo_scene(seed=0):
     return sc
 
 
+TABLE_ZOO_PDFS = (0.05, 0.1, 0.15, 0.2, 0.25, 0.13, 0.12)   # choicePdf per light: distinct, sum 1, none 1 / 7
+TABLE_ZOO_KINDS = ("no_material", "type1", "point_light_id", "emitter_back", "diffuse", "plastic", "glossy", "textured")
+
+
+def scene_table_zoo(seed=0, lights=True):
+    """Shape-, material- and light-table parity scene for a 96 x 64 view (camera 'table_zoo'): the
+    rare branches of the tables, every id -1 or in range, light types 0..3.
+
+    A layer of panels in the plane z = 0 faces the camera; their edges lie half a pixel off the
+    camera rays.  Behind it stand emitter 1 (z = 2.5) and a back wall (z = 4); below and above the
+    view frustum, in front of the layer, lie emitter 3 (a floor) and a ceiling.
+      rows 0-31    4 x 4 pixel panels cycling through TABLE_ZOO_KINDS, each kind one shape: no
+                   material (materialId -1), a material of type 1 with a normal map, a lightID that
+                   names the point light, emitter 2 (a mesh light turned away from the camera), a
+                   diffuse-only material and three ordinary uber materials
+      rows 32-63   columns 0-15 a plane tilted 75 degrees, strips of a kr-only mirror and an uber
+                   material, whose reflections reach emitter 1; columns 80-95 a plane tilted 80
+                   degrees the other way, strips of a diffuse-only and an uber material, facing
+                   emitter 1; columns 40-71 a window of 8 x 4 holes onto emitter 1 in a checker with
+                   panels; columns 72-79 strips of perfectly specular glass (kt.w = 0) in front of
+                   emitter 1; ordinary panels elsewhere
+    Emitter 1: 6 triangles of six different areas (up to 2.6 x apart) under a transform with a non-uniform
+    scale and a rotation; the shape's and the light's area are the world-space sum, as RTScene
+    takes them from MeshRenderer::computeSurfaceArea.  Emitter 3 has no material.  The disk light
+    lies in the plane z = 0 with the panels' normal, so every area sample taken from a panel of the
+    layer has |n . wi| = 0 and pushes no shadow ray.  Lights: directional, point, disk, the three
+    mesh lights and a point light of intensity 0, choicePdf TABLE_ZOO_PDFS.
+    lights=False: the same scene without lights and light ids (both integrators render zeros).
+    `scene.zoo`: shape ids by name, materials by name."""
+    rng = np.random.default_rng(SEED_BASE + 400 + seed)
+    b = SceneBuilder("table_zoo")
+    W, H = ZOO_VIEW
+    th = math.tan(math.radians(45.0) / 2.0) * abs(ZOO_CAMERA_Z)
+    tw = th * W / H
+    info = {"shapes": {}, "materials": {}}
+
+    def world(px, py, z=0.0):
+        k = (z - ZOO_CAMERA_Z) / abs(ZOO_CAMERA_Z)
+        return ((px - 0.5) / W * 2.0 - 1.0) * tw * k, ((py - 0.5) / H * 2.0 - 1.0) * th * k, z
+
+    def quad(px0, py0, px1, py1, z0=0.0, z1=0.0, back=False):
+        """Pixels [px0, px1) x [py0, py1); the left edge at depth z0, the right one at z1."""
+        P = [world(px0, py0, z0), world(px1, py0, z1), world(px1, py1, z1), world(px0, py1, z0)]
+        n = np.cross(np.subtract(P[1], P[0]), np.subtract(P[3], P[0]))
+        n = -n / np.linalg.norm(n)   # towards the camera
+        tris = [[0, 2, 1], [0, 3, 2]]
+        if back:
+            n, tris = -n, [[0, 1, 2], [0, 2, 3]]
+        uv = [(px0 / 16.0, py0 / 16.0), (px1 / 16.0, py0 / 16.0), (px1 / 16.0, py1 / 16.0), (px0 / 16.0, py1 / 16.0)]
+        return np.asarray(P), np.tile(n, (4, 1)), np.asarray(uv), np.asarray(tris)
+
+    def tilted_depth(px_near, px_far, deg):
+        """Depth of the far edge of a plane through column px_near at z = 0, tilted `deg` from facing."""
+        x0 = world(px_near, 0)[0]
+        sgn = 1.0 if px_far > px_near else -1.0
+        c, s_ = math.cos(math.radians(deg)), math.sin(math.radians(deg))
+        k = ((px_far - 0.5) / W * 2.0 - 1.0) * tw   # x of column px_far = k * (z + 4) / 4
+        t = (k - x0) / (sgn * c - k * s_ / abs(ZOO_CAMERA_Z))
+        return t * s_
+
+    def shape(name, parts, mat):
+        sid = b.add_mesh(*merge(parts), mat)
+        info["shapes"][name] = sid
+        return sid
+
+    mats = info["materials"]
+    checker = b.add_texture(tex_checker(16, (230, 230, 230), (60, 60, 170), tiles=4))
+    nmap = b.add_texture(tex_normalmap(16, rng))
+    mats["wall"] = b.add_material(kd=(0.6, 0.6, 0.6), ks=(0, 0, 0))
+    mats["type1"] = b.add_material(kd=(0.7, 0.7, 0.7), ks=(0.3, 0.3, 0.3), normalMapId=nmap, type=1)
+    mats["diffuse"] = b.add_material(kd=(0.8, 0.7, 0.6), ks=(0, 0, 0))
+    mats["plastic"] = b.add_material(kd=(0.5, 0.3, 0.2), ks=(0.3, 0.3, 0.3), roughness=0.3)
+    mats["glossy"] = b.add_material(kd=(0.05, 0.05, 0.05), ks=(0.8, 0.7, 0.5), roughness=0.15)
+    mats["textured"] = b.add_material(kd=(1, 1, 1), ks=(0.1, 0.1, 0.1), diffuseTexId=checker, normalMapId=nmap)
+    mats["mirror"] = b.add_material(kd=(0, 0, 0), ks=(0, 0, 0), kr=(0.9, 0.9, 0.9))
+    mats["glass"] = b.add_material(kd=(0, 0, 0), ks=(0, 0, 0), kt=(0.9, 0.95, 0.9, 0.0), eta=1.2)
+    mats["emitter"] = b.add_material(kd=(0.7, 0.7, 0.7), ks=(0.1, 0.1, 0.1), roughness=0.4)
+    kind_mat = {"no_material": -1, "type1": mats["type1"], "point_light_id": mats["plastic"],
+                "emitter_back": mats["emitter"], "diffuse": mats["diffuse"], "plastic": mats["plastic"],
+                "glossy": mats["glossy"], "textured": mats["textured"]}
+
+    # shape 0: the back wall
+    info["shapes"]["wall"] = b.add_mesh(*grid((-2.2 * tw, -2.2 * th, 4.0), (4.4 * tw, 0, 0), (0, 4.4 * th, 0), 1, 1,
+                                              flip=True), mats["wall"])
+    # rows 0-31: 4 x 4 panels, kind (bx + 3 by) % 8 -- the four panels of an 8 x 8 tile differ
+    parts = {k: [] for k in TABLE_ZOO_KINDS}
+    for by in range(8):
+        for bx in range(24):
+            k = TABLE_ZOO_KINDS[(bx + 3 * by) % 8]
+            parts[k].append(quad(4 * bx, 4 * by, 4 * bx + 4, 4 * by + 4, back=(k == "emitter_back")))
+    # rows 32-63 of the layer: window, glass strips and ordinary panels between the tilted planes
+    glass = []
+    ordinary = ("plastic", "glossy", "textured", "diffuse")
+    for by in range(8):
+        for bx in range(2, 10):
+            x0, y0 = 8 * bx, 32 + 4 * by
+            hole = 5 <= bx < 9 and by < 6 and (bx + by) % 2 == 0
+            if hole:
+                continue
+            if bx == 9 and by < 6 and by % 2 == 0:
+                glass.append(quad(x0, y0, x0 + 8, y0 + 4))
+                continue
+            for h in range(2):
+                parts[ordinary[(bx + by + 2 * h) % 4]].append(quad(x0 + 4 * h, y0, x0 + 4 * h + 4, y0 + 4))
+    for k in TABLE_ZOO_KINDS:
+        shape(k, parts[k], kind_mat[k])
+    shape("glass", glass, mats["glass"])
+    # the tilted planes, 4-row strips
+    zl = tilted_depth(0, 16, 75.0)
+    zr = tilted_depth(96, 80, 80.0)
+    strips = {"mirror": [], "tilt_plastic": [], "tilt_diffuse": [], "tilt_glossy": []}
+    for by in range(8):
+        y0 = 32 + 4 * by
+        strips["mirror" if by % 2 == 0 else "tilt_plastic"].append(quad(0, y0, 16, y0 + 4, 0.0, zl))
+        strips["tilt_diffuse" if by % 2 == 0 else "tilt_glossy"].append(quad(80, y0, 96, y0 + 4, zr, 0.0))
+    shape("mirror", strips["mirror"], mats["mirror"])
+    shape("tilt_plastic", strips["tilt_plastic"], mats["plastic"])
+    shape("tilt_diffuse", strips["tilt_diffuse"], mats["diffuse"])
+    shape("tilt_glossy", strips["tilt_glossy"], mats["glossy"])
+    # emitter 1: three skewed quads, 6 triangles, facing the camera under scale x rotation
+    bot, top = (-1.0, -0.6, 0.3, 1.0), (-1.0, -0.2, 0.65, 1.0)
+    P = [(x, -1.0, 0.0) for x in bot] + [(x, 1.0, 0.0) for x in top]
+    tris = []
+    for i in range(3):
+        tris += [[i, i + 5, i + 1], [i, i + 4, i + 5]]
+    a = math.radians(20.0)
+    M = np.eye(4)
+    M[:3, :3] = np.array([[math.cos(a), -math.sin(a), 0], [math.sin(a), math.cos(a), 0], [0, 0, 1]]) @ np.diag([2.3, 1.1, 1.0])
+    M[:3, 3] = (1.25, 1.15, 2.5)
+    e1 = b.add_mesh(P, np.tile([0.0, 0.0, -1.0], (8, 1)), [(p[0], p[1]) for p in P], tris, mats["emitter"],
+                    transform=M.astype(np.float32))
+    info["shapes"]["emitter1"] = e1
+    # emitter 3 (no material): a floor below the frustum in front of the layer, under a small blocker;
+    # the ceiling above the frustum: one half of type 1, the other diffuse
+    e3 = b.add_mesh(*grid((-2.6, -1.75, -3.0), (5.2, 0, 0), (0, 0, 2.95), 1, 1, flip=True), -1)
+    info["shapes"]["emitter3"] = e3
+    info["shapes"]["blocker"] = b.add_mesh(*grid((-1.2, -1.70, -2.2), (2.4, 0, 0), (0, 0, 1.2), 1, 1, flip=True),
+                                           mats["plastic"])
+    info["shapes"]["ceiling_type1"] = b.add_mesh(*grid((-2.6, 1.75, -3.0), (2.6, 0, 0), (0, 0, 2.95), 1, 1), mats["type1"])
+    info["shapes"]["ceiling_diffuse"] = b.add_mesh(*grid((0.0, 1.75, -3.0), (2.6, 0, 0), (0, 0, 2.95), 1, 1), mats["diffuse"])
+    if lights:
+        b.add_directional_light((0.25, -0.35, 1.0), (2.0, 2.0, 2.0))
+        point = b.add_point_light((0.3, 0.5, -2.5), (5.0, 5.0, 5.0))
+        hx, hy, _ = world(44.5, 34.5)   # the middle of the window's first hole, reaching under its neighbours
+        b.add_disk_light((hx, hy, 0.0), (0.0, 0.0, -1.0), 0.3, (6.0, 6.0, 5.0))
+        b.add_mesh_light(e1, (9.0, 8.0, 7.0))
+        b.add_mesh_light(info["shapes"]["emitter_back"], (6.0, 7.0, 8.0))
+        b.add_mesh_light(e3, (3.0, 3.0, 3.5))
+        b.add_point_light((-0.5, -0.4, -1.5), (0.0, 0.0, 0.0))
+    sc = b.build()
+    if lights:
+        sc.lights["choicePdf"] = np.asarray(TABLE_ZOO_PDFS, np.float32)
+        sc.shapes["lightID"][info["shapes"]["point_light_id"]] = point
+    sc.zoo = info
+    return sc
+
+
 def san_miguel_proxy(tris=10_000_000, seed=4, tex_size=512):
     """San-Miguel proxy (configs 4/5 and the headline metric): courtyard with arcades,
     tables, ~70 % of the triangles in foliage quads with alpha cut-out leaves, >= 64
@@ -1001,4 +1158,5 @@ CAMERAS = {
     "instances_test": ((0.0, 5.0, -13.0), (0.0, 1.0, 0.0), 45.0),
     "lod_test": ((0.0, 2.0, -9.0), (0.0, 1.0, 10.0), 45.0),
     "tex_zoo": ((0.0, 0.0, ZOO_CAMERA_Z), (0.0, 0.0, 0.0), 45.0),
+    "table_zoo": ((0.0, 0.0, ZOO_CAMERA_Z), (0.0, 0.0, 0.0), 45.0),
 }

@@ -1657,6 +1657,7 @@ typedef struct {
     atomic_llong stats[8];
 } RenderCtx;
 
+static int isUberMat(const orc_scene* s, int mi);
 static void renderPixel(RenderCtx* rc, int x, int y, uint32_t* stack) {
     const orc_scene* s = rc->s;
     const mcrt_camera* cam = rc->cam;
@@ -1729,17 +1730,33 @@ static void renderPixel(RenderCtx* rc, int x, int y, uint32_t* stack) {
                     v3 L = V3(0, 0, 0);
                     int mid = sh->materialId;
                     if (mid != -1) {
-                        UberProps um;
-                        getUberProps(s, mid, &si, &um);
-                        v3 bsdf = evaluateUberBSDF(&um, &si, si.wo, wi, TRANSPORT_MODE_RADIANCE);
+                        v3 bsdf = V3(0, 0, 0);   /* evaluateMaterial, materials.cl:131-142: 0 for another type */
+                        if (isUberMat(s, mid)) {
+                            UberProps um;
+                            getUberProps(s, mid, &si, &um);
+                            bsdf = evaluateUberBSDF(&um, &si, si.wo, wi, TRANSPORT_MODE_RADIANCE);
+                        }
                         bsdf = vs(bsdf, absDot(wi, si.sn));
                         if (!isNearZero(lightPdf)) L = vdivs(vmul(Li, bsdf), lightPdf);
                     }
                     temp = vadd(temp, vmul(throughput, L));
+                    /* Shaping of the path log and the query statistics only, not an observation of the
+                     * reference (which runs its occluded kernel over every shadow ray): with no
+                     * material, a material of another type or a black light the term is exactly zero
+                     * whatever the query answers (0 * V), so none is made and the log shows none.  The
+                     * product goes further and queues no shadow ray for ANY exactly zero term; other
+                     * zero terms (a light behind the surface) are still queried here, so that the
+                     * statistics of every scene without these three cases stay what they were. */
+                    const mcrt_float3* I0 = &s->d.lights[lightIdx].intensity;
+                    if (mid == -1 || !isUberMat(s, mid) || (I0->x == 0.0f && I0->y == 0.0f && I0->z == 0.0f)) shadowSet = 0;
                 }
                 if (b + 1 < rc->maxDepth) {
                     v2 bs = getSample2D(&smp);
                     float pdf = 0.0f;
+                    /* sampleMaterial, materials.cl:144-156, leaves pdf and the sampled type unset for
+                     * another type and line 154 of PathTracing.cl reads the pdf: the reference's compiled
+                     * kernel has no such path and samples every material as the uber one (measured on
+                     * the table zoo, tests/test_gpu_table_zoo.py) */
                     if (sh->materialId != -1) {
                         int sampledType = 0, unused = 0;
                         v3 wi = V3(0, 0, 0);
@@ -2415,7 +2432,10 @@ static void bdptSecondary(BdptCtx* c, uint32_t bufferIdx, int isCam, int curDept
         f = sampleUberBSDF(&um, &si, bs, mode, BSDF_ALL, wo, &wi, &pdfFwd, &numNonDelta, &sampledType);
     }
     cur->in = si;
-    if (numNonDelta > 0) cur->flags |= BVF_CONNECTIBLE;
+    /* sampleMaterial (materials.cl:144-156) leaves numNonDeltaTypes unset for another type and
+     * BDPT.cl:415 reads it: the reference's compiled kernel marks such a vertex connectible and,
+     * f being black, ends the walk (measured on the table zoo, tests/test_gpu_table_zoo.py) */
+    if (numNonDelta > 0 || !isUberMat(s, mi)) cur->flags |= BVF_CONNECTIBLE;
     if (isBlack(f) || isNearZero(pdfFwd)) { ray->active = 0; return; }
     *throughput = vmul(*throughput, vdivs(vs(f, absDot(wi, si.sn)), pdfFwd));
     float pdfRev;

@@ -2,11 +2,13 @@
 // (mcrt_camera.cpp), the host Bvh2 restatement (mcrt_bvh.cpp), the acceleration structure's host layer
 // (mcrt_accel_host.cpp over mcrt_bvh.cpp and mcrt_bvh2l.cpp) and the oracle (oracle/mcrt_oracle.c:
 // BVH build, closest / any-hit traversal against brute force, one PT and one BDPT frame, accumulate,
-// denoise, tone map) and the runtime's owning device-buffer type (mcrt_devbuf.h, over malloc / free), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
+// denoise, tone map), the scene-table check (check_scene_tables) and the runtime's owning device-buffer type (mcrt_devbuf.h, over malloc / free), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
 // every check held and the sanitizers reported nothing (they abort on the first finding).
 #include <unistd.h>
 
+#include <climits>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -256,14 +258,181 @@ static int accel_host_checks() {
     return 0;
 }
 
+// The scene-table check (check_scene_tables, mcrt_accel_host.cpp) called directly: per rule the
+// first rejected value on both sides (-2, n) and the last accepted ones (-1, n - 1), all eight
+// texture slots, a startVertex moved one past the end.  The tables are sized exactly, so a read
+// past a table is a sanitizer finding.
+static int32_t mcrt_material::* const kTexSlot[8] = {
+    &mcrt_material::uber_normalMapId, &mcrt_material::uber_diffuseTexId, &mcrt_material::uber_glossyTexId,
+    &mcrt_material::uber_specReflectionTexId, &mcrt_material::uber_transmissionTexId, &mcrt_material::uber_opacityTexId,
+    &mcrt_material::uber_roughnessTexId, &mcrt_material::uber_iorTexId};
+
+static int table_checks() {
+    using namespace mcrt;
+    const uint32_t idx[6] = {0, 1, 2, 0, 2, 3};
+    std::vector<mcrt_shape> shapes = {shape_at(0.0f, 0, 0, 2), shape_at(1.0f, 0, 4, 2)};   // 8 vertices
+    std::vector<mcrt_material> mats(3);
+    std::vector<mcrt_light> lights(2);
+    std::memset(mats.data(), 0, sizeof(mcrt_material) * mats.size());
+    std::memset(lights.data(), 0, sizeof(mcrt_light) * lights.size());
+    for (auto& m : mats)
+        for (int k = 0; k < 8; ++k) m.*kTexSlot[k] = -1;
+    lights[0].type = MCRT_POINT_LIGHT;
+    lights[0].shapeId = -1;
+    lights[1].type = MCRT_TRIANGLE_MESH_AREA_LIGHT;
+    lights[1].shapeId = 1;
+    const uint32_t numTextures = 4;
+    auto tables = [&]() {
+        SceneTables t;
+        t.shapes = shapes.data();
+        t.numShapes = shapes.size();
+        t.materials = mats.data();
+        t.numMaterials = mats.size();
+        t.lights = lights.data();
+        t.numLights = lights.size();
+        t.numTextures = numTextures;
+        t.indices = idx;
+        t.numIndices = 6;
+        t.numVertices = 8;
+        return t;
+    };
+    uint32_t at = 77, slot = 77;
+    CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_OK);
+    CHECK(check_scene_tables(tables(), nullptr, nullptr) == TABLE_OK);
+    // shape ids
+    for (int32_t v : {-1, (int32_t)mats.size() - 1}) {
+        shapes[1].materialId = v;
+        CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_OK);
+    }
+    for (int32_t v : {-2, (int32_t)mats.size(), INT32_MIN, INT32_MAX}) {
+        shapes[1].materialId = v;
+        CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_MATERIAL_ID && at == 1);
+        CHECK(scene_tables_message(TABLE_MATERIAL_ID, at, slot).find("shape 1") != std::string::npos);
+    }
+    shapes[1].materialId = 0;
+    for (int32_t v : {-1, (int32_t)lights.size() - 1}) {
+        shapes[0].lightID = v;
+        CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_OK);
+    }
+    for (int32_t v : {-2, (int32_t)lights.size(), INT32_MIN, INT32_MAX}) {
+        shapes[0].lightID = v;
+        CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_LIGHT_ID && at == 0);
+        CHECK(scene_tables_message(TABLE_LIGHT_ID, at, slot).find("shape 0") != std::string::npos);
+    }
+    shapes[0].lightID = -1;
+    // every texture slot of a material of either type
+    for (int type : {0, 1}) {
+        mats[2].type = type;
+        for (uint32_t k = 0; k < 8; ++k) {
+            int32_t& id = mats[2].*kTexSlot[k];
+            for (int32_t v : {-1, (int32_t)numTextures - 1}) {
+                id = v;
+                CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_OK);
+            }
+            for (int32_t v : {-2, (int32_t)numTextures}) {
+                id = v;
+                CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_TEXTURE_ID && at == 2 && slot == k);
+                CHECK(scene_tables_message(TABLE_TEXTURE_ID, at, slot).find("material 2") != std::string::npos);
+            }
+            id = -1;
+        }
+    }
+    mats[2].type = 0;
+    // no materials at all while a shape names one; none named: accepted
+    {
+        SceneTables t = tables();
+        t.materials = nullptr;
+        t.numMaterials = 0;
+        CHECK(check_scene_tables(t, &at, &slot) == TABLE_MATERIAL_ID && at == 1);
+        shapes[1].materialId = -1;
+        CHECK(check_scene_tables(t, &at, &slot) == TABLE_OK);
+        shapes[1].materialId = 0;
+    }
+    // mesh light: its shape id on both sides, a shape without triangles
+    for (int32_t v : {0, (int32_t)shapes.size() - 1}) {
+        lights[1].shapeId = v;
+        CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_OK);
+    }
+    for (int32_t v : {-1, -2, (int32_t)shapes.size()}) {
+        lights[1].shapeId = v;
+        CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_MESH_LIGHT && at == 1);
+    }
+    lights[1].shapeId = 1;
+    shapes[1].numTriangles = 0;
+    CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_MESH_LIGHT && at == 1);
+    shapes[1].numTriangles = 2;
+    lights[0].shapeId = 99;   // not a mesh light: its shapeId is not read
+    CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_OK);
+    // a moved startVertex: the last one that fits (4 + 3 = 7 of 8) and one past it
+    CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_OK);
+    shapes[1].startVertex = 5;
+    CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_VERTEX_INDEX && at == 1);
+    CHECK(check_shape_ranges(&shapes[1], 1, idx, 6, 8, nullptr) == 2);
+    shapes[1].startVertex = 4;
+    shapes[1].startIdx = 1;   // indices 1..6 of 6
+    CHECK(check_scene_tables(tables(), &at, &slot) == TABLE_INDEX_RANGE && at == 1);
+    shapes[1].startIdx = 0;
+    // one table replaced (the update calls): the others' entries are not read, their counts are
+    {
+        SceneTables t = tables();
+        t.materials = nullptr;
+        t.lights = nullptr;
+        t.indices = nullptr;
+        CHECK(check_scene_tables(t, &at, &slot) == TABLE_OK);
+        t.numLights = 0;   // a scene without lights is legal while no shape names one
+        CHECK(check_scene_tables(t, &at, &slot) == TABLE_OK);
+        shapes[0].lightID = 0;
+        CHECK(check_scene_tables(t, &at, &slot) == TABLE_LIGHT_ID && at == 0);
+        shapes[0].lightID = -1;
+    }
+    return 0;
+}
+
+// host_asan --tables FILE: the check over tables written by tests/test_table_zoo_cpu.py (seven
+// uint32 counts -- shapes, materials, lights, textures, indices, vertices, the expected rule --
+// then the shape, material, light and index arrays); exit 0 when the check gives the expected rule
+static int tables_file(const char* path) {
+    FILE* f = std::fopen(path, "rb");
+    CHECK(f != nullptr);
+    uint32_t n[7];
+    CHECK(std::fread(n, 4, 7, f) == 7);
+    std::vector<mcrt_shape> shapes(n[0]);
+    std::vector<mcrt_material> mats(n[1]);
+    std::vector<mcrt_light> lights(n[2]);
+    std::vector<uint32_t> idx(n[4]);
+    CHECK(std::fread(shapes.data(), sizeof(mcrt_shape), n[0], f) == n[0]);
+    CHECK(std::fread(mats.data(), sizeof(mcrt_material), n[1], f) == n[1]);
+    CHECK(std::fread(lights.data(), sizeof(mcrt_light), n[2], f) == n[2]);
+    CHECK(std::fread(idx.data(), 4, n[4], f) == n[4]);
+    std::fclose(f);
+    mcrt::SceneTables t;
+    t.shapes = shapes.data();
+    t.numShapes = n[0];
+    t.materials = mats.data();
+    t.numMaterials = n[1];
+    t.lights = lights.data();
+    t.numLights = n[2];
+    t.numTextures = n[3];
+    t.indices = idx.data();
+    t.numIndices = n[4];
+    t.numVertices = n[5];
+    uint32_t at = 0, slot = 0;
+    const int rule = mcrt::check_scene_tables(t, &at, &slot);
+    std::printf("tables: %u shapes, %u materials, %u lights, %u textures: rule %d%s%s\n", n[0], n[1], n[2], n[3], rule,
+                rule ? " -- " : "", mcrt::scene_tables_message(rule, at, slot).c_str());
+    return rule == (int)n[6] ? 0 : 1;
+}
+
 static void write_file(const std::string& p, const char* text) {
     FILE* f = std::fopen(p.c_str(), "w");
     std::fputs(text, f);
     std::fclose(f);
 }
 
-int main() {
+int main(int argc, char** argv) {
+    if (argc == 3 && std::strcmp(argv[1], "--tables") == 0) return tables_file(argv[2]);
     if (devbuf_checks() != 0) return 1;
+    if (table_checks() != 0) return 1;
     // a room (floor, back wall), a box, an emissive quad and a quad fan, with an MTL
     char tmpl[] = "/tmp/mcrt_asan_XXXXXX";
     const char* dir = mkdtemp(tmpl);

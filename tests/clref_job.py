@@ -119,13 +119,17 @@ TEX_BDPT_CASES = [("tex_zoo", 96, 64, (0, 1), 2)]
 
 
 def tex_job(out_path, variant):
+    zoo_job(out_path, variant, TEX_CASES, TEX_BDPT_CASES, "texture-zoo")
+
+
+def zoo_job(out_path, variant, pt_cases, bdpt_cases, what):
     res = {}
-    for name, W, H, frames, D in TEX_CASES:
+    for name, W, H, frames, D in pt_cases:
         cs = po.CLRefScene(build_scene(name), variant)
         cam = scene_camera(name, W, H)
         for f in frames:
             res[f"{name}_{W}x{H}_d{D}_f{f}"] = cs.render(cam, frame=f, max_depth=D)
-    for case in TEX_BDPT_CASES:
+    for case in bdpt_cases:
         name, W, H, frames, D = case
         cs = po.CLRefScene(build_scene(name), variant)
         cam = scene_camera(name, W, H)
@@ -135,7 +139,17 @@ def tex_job(out_path, variant):
         for which in ("camera_vertices", "light_vertices", "camera_counts", "light_counts"):
             res[f"{key}_{which}"] = cs.read_bdpt(which)
     np.savez_compressed(out_path, **res)
-    print(f"clref texture-zoo job ({variant}): {len(res)} arrays -> {out_path}")
+    print(f"clref {what} job ({variant}): {len(res)} arrays -> {out_path}")
+
+
+# Table zoo (mcrt.scenes.scene_table_zoo): the rare branches of the shape, material and light tables
+# (tests/test_gpu_table_zoo.py).  Every table value is one the reference's kernels guard.
+TABLE_CASES = [("table_zoo", 96, 64, (0, 1), 3)]
+TABLE_BDPT_CASES = [("table_zoo", 96, 64, (0, 1), 2)]
+
+
+def table_job(out_path, variant):
+    zoo_job(out_path, variant, TABLE_CASES, TABLE_BDPT_CASES, "table-zoo")
 
 
 LOD_CASES = [("lod_test", 160, 120), ("mixed", 96, 64), ("tex_zoo", 96, 64)]
@@ -162,6 +176,8 @@ def build_scene(name):
         return scenes.lod_test_scene()
     if name == "tex_zoo":
         return scenes.texture_zoo_scene()
+    if name == "table_zoo":
+        return scenes.scene_table_zoo()
     if name == "instances_test":
         return scenes.instances_test_scene()
     if name == "instanced_small":
@@ -381,6 +397,9 @@ def main():
         return
     if len(sys.argv) > 3 and sys.argv[3] == "tex":
         tex_job(out_path, variant)
+        return
+    if len(sys.argv) > 3 and sys.argv[3] == "table":
+        table_job(out_path, variant)
         return
     if len(sys.argv) > 3 and sys.argv[3] == "2l":
         tl_job(out_path, variant)
