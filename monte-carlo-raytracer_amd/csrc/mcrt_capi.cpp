@@ -18,6 +18,7 @@
 #include <tuple>
 #include <vector>
 
+#include "mcrt_bands.h"
 #include "mcrt_host.h"
 
 namespace {
@@ -47,14 +48,6 @@ const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN"
                                      "k_temporal",    "k_temporal_var", "k_guides_motion", "k_temporal_motion"};
 
 }  // namespace
-
-// The set of the last BDPT call, as cur_slot (mcrt_host.h) is the slot of the last rendered frame
-static BdptSet& cur_bset(mcrt_framebuffer fb) { return fb->bset[fb->bdptSet]; }
-
-// BDPT queue counters (64 ints per frame set): [d] the subpath-ray queue of depth d (d <= 33;
-// at depth 0 the light rays only), then these
-enum { BDPT_CNT_CONN = 40, BDPT_CNT_CAM0 = 41, BDPT_CNT_SPLATS = 42 };
-static int bdpt_max_connections(int D) { const int t = D + 2; return t * (t + 1) / 2 - 2; }   // RTBDPTPass.cpp:404-408
 
 // ---------------------------------------------------------------------------
 // helpers
@@ -107,10 +100,21 @@ static int walk_cap() { return env_int("MCRT_WALK_CAP", 60, 0); }
 // 0.659).  The tests set it to 0 to run the rule on small frames.
 static int64_t walk_min_paths() { return env_int("MCRT_WALK_MIN_PATHS", 16000000); }
 static int walk_max_bounce() { return env_int("MCRT_WALK_MAXB", 0); }
-// BDPT: the light-tracing strategies (t = 1) evaluated by the vertex launches that create their
-// light vertices instead of by a connection launch that re-reads them (MCRT_BDPT_LIGHT_IN_VERTEX)
-static int bdpt_light_in_vertex() { return env_int("MCRT_BDPT_LIGHT_IN_VERTEX", 1) != 0; }
 static int walk_lanes() { return env_int("MCRT_WALK_LANES", 8, 0, 64); }
+
+hipError_t mcrt::walk_rule(TraceCtx& c, int64_t paths, DevBuf<float4>& suspend, DevBuf<int>& suspendCnt, int counts,
+                           size_t entries, hipStream_t st) {
+    const int wcap = c.qnodes && !c.twoLevel && paths >= walk_min_paths() ? walk_cap() : 0;
+    if (wcap <= 0) return hipSuccess;
+    hipError_t e = (hipError_t)suspend.grow(MCRT_SUSPEND_F4 * entries, st);
+    if (e == hipSuccess && !suspendCnt) e = (hipError_t)suspendCnt.alloc(counts);
+    if (e == hipSuccess) e = hipMemsetAsync(suspendCnt.get(), 0, counts * sizeof(int), st);
+    if (e != hipSuccess) return e;
+    c.walkCap = wcap;
+    c.walkLanes = walk_lanes();
+    c.suspend = suspend.get();
+    return hipSuccess;
+}
 
 SceneArgs mcrt::scene_args(mcrt_scene s) {
     SceneArgs a;
@@ -169,14 +173,9 @@ bool mcrt::frame_args(mcrt_framebuffer fb, const mcrt_frame_params* p, FrameArgs
     if (f.bandRows <= 0 || (f.bandRows & 7) != 0) { err = "band_rows must be a positive multiple of 8"; return false; }
     if (f.bandIndex < 0 || f.bandIndex >= f.numBands) { err = "band_index out of range"; return false; }
     f.tilesX = (int)((fb->W + 7) / 8);
-    // row-blocks (8 rows) of this band set inside the image
-    const int blocksTotal = (int)((fb->H + 7) / 8);
-    const int bpb = f.bandRows / 8;
-    int myBlocks = 0;
-    for (int gb = 0; gb < blocksTotal; ++gb)
-        if ((gb / bpb) % f.numBands == f.bandIndex) ++myBlocks;
-    // tile ids are dealt in the kernel as tb -> gb; count the band-local blocks that map inside
-    f.numTiles = myBlocks * f.tilesX;
+    // row-blocks (8 rows) of this band set inside the image; tile ids are dealt in the kernel as
+    // tb -> gb, over the band-local blocks that map inside
+    f.numTiles = mcrt::band_blocks(fb->H, f.bandRows, f.numBands, f.bandIndex) * f.tilesX;
     return true;
 }
 
@@ -667,14 +666,6 @@ MCRT_API mcrt_status mcrt_event_destroy(mcrt_event ev) {
 // ---------------------------------------------------------------------------
 // frame buffer + integrator
 // ---------------------------------------------------------------------------
-static void fb_free_bdpt(mcrt_framebuffer fb) {
-    for (auto& b : fb->bset) b = BdptSet();
-    fb->sampLight.reset();
-    if (fb->bdptConnect) hipEventDestroy(fb->bdptConnect);
-    fb->bdptConnect = nullptr;
-    fb->bdptDepth = 0;
-}
-
 static void slot_free(FrameSlot& k) {
     if (k.stream) hipStreamSynchronize(k.stream);
     if (k.done) hipEventDestroy(k.done);
@@ -683,10 +674,9 @@ static void slot_free(FrameSlot& k) {
     k = FrameSlot();
 }
 
-// the slots' streams and events and every slot and set; the frame buffer's own planes go with it
+// the slots' streams, events and buffers; the frame buffer's own planes and its BDPT state go with it
 static void fb_free(mcrt_framebuffer fb) {
     for (auto& k : fb->slot) slot_free(k);
-    fb_free_bdpt(fb);
 }
 
 // Per-frame planes (radiance, primary hits) for `frames` frames of N pixels; ray queues of Q entries.
@@ -719,80 +709,17 @@ static hipError_t slot_alloc(FrameSlot& k, size_t N, size_t T, int frames = 1, s
     return e;
 }
 
-// NQ = the pixels of the whole 8x8 tiles covering the image (>= N): the start queues hold one slot
-// per lane of the tile walk.  Ray queues and hits hold 2 x NQ (the depth-1 camera and light halves).
-static hipError_t bset_alloc(BdptSet& b, size_t N, size_t NQ, int D, int frames, hipStream_t st) {
-    const size_t C = (size_t)bdpt_max_connections(D);
-    N *= frames;    // every per-frame array holds the batch's frames
-    NQ *= frames;
-    hipError_t e = hipSuccess;
-    auto A = [&](auto& buf, size_t count) {
-        if (e == hipSuccess) e = (hipError_t)buf.alloc(count);
-    };
-    A(b.camV, N * BDPT_VERTEX_PLANES * (D + 2));
-    A(b.lightV, N * BDPT_VERTEX_PLANES * (D + 1));
-    A(b.slots, N * (C - D));
-    A(b.splat, N);
-    A(b.camCount, N);
-    A(b.lightCount, N);
-    A(b.bdptCounters, 64);
-    for (int i = 0; i < 2; ++i) { A(b.bqO[i], 2 * NQ); A(b.bqD[i], 2 * NQ); A(b.bqT[i], 2 * NQ); }
-    A(b.bHits, 2 * NQ);
-    A(b.cO, N * C);
-    A(b.cD, N * C);
-    A(b.cL, N * C);
-    A(b.lkey, NQ);
-    A(b.lkey2, NQ);
-    A(b.lslot, NQ);
-    A(b.lperm, NQ);
-    A(b.ekey, 2 * N);
-    A(b.ekey2, 2 * N);
-    A(b.eslot, 2 * N);
-    A(b.eperm, 2 * N);
-    A(b.sortTmp, mcrt::bdpt_light_sort_temp_bytes((int)std::max(NQ, 2 * N)));
-    // zero-fills on the stream of the set's frames (st, its slot's), ahead of the first launch
-    // that writes the set: a 3 GB vertex-plane memset on another stream could still be running
-    // under k_bdpt_start and zero its vertices
-    if (e == hipSuccess) e = hipMemsetAsync(b.splat.get(), 0, 16 * N, st);
-    if (e == hipSuccess) e = hipMemsetAsync(b.camV.get(), 0, 16 * N * BDPT_VERTEX_PLANES * (D + 2), st);
-    if (e == hipSuccess) e = hipMemsetAsync(b.lightV.get(), 0, 16 * N * BDPT_VERTEX_PLANES * (D + 1), st);
-    if (e != hipSuccess) b = BdptSet();
-    else b.frames = frames;
-    return e;
-}
-
-// RTBDPTPass::createBuffers (RTBDPTPass.cpp:442-479), sized for max depth D: set k of the
-// per-frame arrays, plus the persistent sampled-light-vertex planes, which start zeroed (the
-// reference's buffer starts with whatever the allocation holds; its clref runner zero-fills it too).
-// (also the packed camera-hit slots per frame: every 8x8 tile of the frame x 64)
-static size_t bdpt_queue_cap(mcrt_framebuffer fb) {
-    return (size_t)((fb->W + 7) / 8) * ((fb->H + 7) / 8) * 64;
-}
-static hipError_t fb_ensure_bdpt(mcrt_framebuffer fb, int D, int k, int frames, hipStream_t st) {
-    const size_t N = fb->N;
-    if (fb->bdptDepth != D) {
-        for (auto& sl : fb->slot)
-            if (sl.stream) hipStreamSynchronize(sl.stream);
-        hipStreamSynchronize(fb->ctx->stream);
-        fb_free_bdpt(fb);
-        hipError_t e = (hipError_t)fb->sampLight.alloc(N * D);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&fb->bdptConnect, hipEventDisableTiming);
-        // zeroed on this frame's stream; every connect launch (the planes' only reader and writer)
-        // waits for bdptConnect, recorded here first
-        if (e == hipSuccess) e = hipMemsetAsync(fb->sampLight.get(), 0, 16 * N * D, st);
-        if (e == hipSuccess) e = hipEventRecord(fb->bdptConnect, st);
-        if (e != hipSuccess) { fb_free_bdpt(fb); return e; }
-        fb->bdptDepth = D;
+// The slot with planes for `frames` frames and ray queues of qNeed entries (0: slot_alloc's least):
+// allocated on first use; a smaller one is freed, once the accumulation of its last frame has read
+// it and its stream has finished, and allocated again.  After a failure the slot is empty.
+static hipError_t slot_ensure(mcrt_framebuffer fb, FrameSlot& slot, int frames, size_t qNeed) {
+    if (slot.stream) {
+        if (slot.frames >= frames && slot.queueCap >= qNeed) return hipSuccess;
+        const hipError_t e = hipEventSynchronize(slot.free);
+        if (e != hipSuccess) return e;
+        slot_free(slot);
     }
-    BdptSet& bs = fb->bset[k];
-    if (bs.camV && bs.frames < frames) {   // a larger batch: the set's last frames must be done
-        for (auto& sl : fb->slot)
-            if (sl.stream) hipStreamSynchronize(sl.stream);
-        hipStreamSynchronize(fb->ctx->stream);
-        bs = BdptSet();
-    }
-    if (!bs.camV) return bset_alloc(bs, N, bdpt_queue_cap(fb), D, frames, st);
-    return hipSuccess;
+    return slot_alloc(slot, fb->N, mcrt::tile_lanes(fb), frames, qNeed);
 }
 
 MCRT_API mcrt_status mcrt_framebuffer_create(mcrt_ctx ctx, uint32_t width, uint32_t height, mcrt_framebuffer* out) {
@@ -879,213 +806,6 @@ static int frames_in_flight(mcrt_framebuffer fb, const FrameArgs& f) {
     return std::max(1, std::min(n, MCRT_MAX_FRAMES_IN_FLIGHT));
 }
 
-// RTBDPTPass::update (RTBDPTPass.cpp:67-128): start vertices, D+1 rounds of (trace, vertex),
-// connections + MIS, visibility, gather.  Rays of both subpaths share one compacted queue.
-static mcrt_status render_bdpt(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_frame_params* p,
-                               const FrameArgs& f, int k, FrameSlot& slot) {
-    // frame slot k on its stream: per-frame arrays of set k; the connect launch (the only reader
-    // and writer of the shared sampled-light-vertex planes) waits for the previous frame's connect
-    mcrt_ctx ctx = s->ctx;
-    hipStream_t st = slot.stream;
-    const int D = p->max_depth;
-    const int B = f.batch;   // frames of this call (mcrt_render_frames): path = k * W*H + pixel
-    HIPCHK(ctx, fb_ensure_bdpt(fb, D, k, B, st));
-    BdptSet& bs = fb->bset[k];
-    fb->bdptSet = k;
-    slot.lastMaxDepth = D;
-    slot.lastPixels = 0;
-    fb->bands = f;
-    fb->haveBands = true;
-    fb->lastIntegrator = MCRT_INTEGRATOR_BDPT;
-    fb->bdptBatch = B;
-    mcrt_camera* dCam = slot.cameras();
-    HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera) * B, hipMemcpyHostToDevice, st));
-    HIPCHK(ctx, hipMemsetAsync(bs.bdptCounters.get(), 0, 64 * sizeof(int), st));
-    if (s->numLights == 0) {   // RTBDPTPass.cpp:69: no lights -> pass skipped
-        HIPCHK(ctx, hipMemsetAsync(slot.radiance.get(), 0, 16 * fb->N * (size_t)B, st));
-        return MCRT_OK;
-    }
-    const size_t N = fb->N * (size_t)B, C = (size_t)bdpt_max_connections(D);   // N: paths of the batch
-    const size_t NQ = bdpt_queue_cap(fb) * (size_t)B;
-    // spill columns: one per ray of the widest closest-hit launch (2 NQ) and one per wave of the
-    // grid-stride visibility launch (mcrt::BDPT_VIS_MAX_WAVES)
-    const size_t spillWords = (std::max(2 * NQ, (size_t)mcrt::BDPT_VIS_MAX_WAVES * 64) + 63) / 64 * 64 * (size_t)mcrt::accel_spill_cap(s);
-    HIPCHK(ctx, bs.spill.grow(spillWords, st));
-    TraceCtx tcs = trace_ctx(s);
-    tcs.spill = bs.spill.get();
-    const SceneArgs sa = scene_args(s);
-    // the closest-hit launches' stop rule (TraceCtx::walkCap): a traced queue holds at most
-    // max(bandQ, nSort) = nSort rays (below)
-    const int wcap = tcs.qnodes && !tcs.twoLevel && (int64_t)f.numTiles * 64 * B >= walk_min_paths() ? walk_cap() : 0;
-    TraceCtx tce = tcs;
-    if (wcap > 0) {
-        const size_t need = (size_t)std::min((size_t)2 * N, (size_t)2 * (size_t)f.numTiles * 64 * B);
-        HIPCHK(ctx, bs.suspend.grow(MCRT_SUSPEND_F4 * need, st));
-        if (!bs.suspendCnt) HIPCHK(ctx, bs.suspendCnt.alloc(64));
-        HIPCHK(ctx, hipMemsetAsync(bs.suspendCnt.get(), 0, 64 * sizeof(int), st));
-        tce.walkCap = wcap;
-        tce.walkLanes = walk_lanes();
-        tce.suspend = bs.suspend.get();
-    }
-    BdptArgs b{};
-    b.camV = bs.camV.get();
-    b.lightV = bs.lightV.get();
-    b.camCount = bs.camCount.get();
-    b.lightCount = bs.lightCount.get();
-    b.sampLight = fb->sampLight.get();
-    b.slots = bs.slots.get();
-    b.splat = bs.splat.get();
-    b.ownSlots = (int)C - D;
-    // (planes at another stride hold other data; another band's paths were never written)
-    // the light-start rays are traced in cell order (keys from k_bdpt_start, rocPRIM sort below):
-    // k_extend 3.07 -> 2.82 ms per frame at 1080p (profiles/r04/ab/README.txt)
-    b.lightKey = bs.lkey.get();
-    b.lightSlot = bs.lslot.get();
-    // the bounce queues that are traced (depths 1..D) in octant / origin-cell order: keys written by
-    // k_bdpt_vertex, sorted below, walked through the permutation by k_extend
-    b.extKey = nullptr;
-    b.extSlot = nullptr;
-    const float* box = mcrt::accel_world_box(s);
-    for (int a = 0; a < 3; ++a) {
-        const float ext = box[3 + a] - box[a];
-        b.keyLo[a] = box[a];
-        b.keyScale[a] = ext > 0.0f ? (a == 1 ? 8.0f : 32.0f) / ext : 0.0f;
-    }
-    b.cams = dCam;
-    b.connCount = bs.bdptCounters.get() + BDPT_CNT_CONN;
-    b.connO = bs.cO.get();
-    b.connD = bs.cD.get();
-    b.connL = bs.cL.get();
-    b.lightInVertex = bdpt_light_in_vertex();
-    BdptArgs bk = b;   // the vertex launches whose output queue is traced
-    bk.extKey = bs.ekey.get();
-    bk.extSlot = bs.eslot.get();
-    // a bounce queue holds at most the band's camera + light rays (2 per path of this rank's tiles),
-    // appended compactly from slot 0: sort (and clear) only that range, not the whole frame's -- a
-    // rank of a band split would otherwise sort 8 x its own rays at N = 8
-    const int bandQ = f.numTiles * 64 * B;   // this rank's paths: a start queue holds at most one ray each
-    const int nSort = (int)std::min((size_t)2 * N, (size_t)2 * (size_t)bandQ);
-    // the queue traced at round D + 1 holds camera rays only (the light subpaths end at depth D): at
-    // most one per path, so it is sorted (and its keys cleared) over bandQ slots, not 2 x bandQ
-    auto sortRange = [&](int tracedAt) { return tracedAt == D + 1 ? std::min(nSort, bandQ) : nSort; };
-    auto clearKeys = [&](int n) {   // unwritten slots sort last (stable sort: after the written ones)
-        return hipMemsetAsync(bs.ekey.get(), 0xFF, 4 * (size_t)n, st);
-    };
-    b.depth0Const = bs.constStride == N && bs.constBand[0] == f.bandRows && bs.constBand[1] == f.numBands &&
-                    bs.constBand[2] == f.bandIndex ? 1 : 0;
-    bs.constStride = N;
-    bs.constBand[0] = f.bandRows;
-    bs.constBand[1] = f.numBands;
-    bs.constBand[2] = f.bandIndex;
-    float4* const bHits = bs.bHits.get();
-    int* cnt = bs.bdptCounters.get();   // [d] ray queue of depth d (d <= D + 1 <= 33), BDPT_CNT_* below
-    auto queue = [&](int d) {
-        BdptQueue q;
-        q.count = cnt + d;
-        q.o = bs.bqO[d & 1].get();
-        q.d = bs.bqD[d & 1].get();
-        q.t = bs.bqT[d & 1].get();
-        return q;
-    };
-    const bool bandSplit = f.numBands > 1;
-    const bool sparse = bandSplit && fb->splatExchange == MCRT_SPLAT_EXCHANGE_SPARSE;
-    if (sparse) {
-        // the splats landing in other ranks' rows go to a list (at most D per path: t = 1, s = 2..D+1);
-        // the rank's own rows are zeroed by k_bdpt_start, the other rows of its plane stay unused
-        const size_t cap = (size_t)D * (size_t)bandQ;
-        HIPCHK(ctx, bs.splatList.grow(cap, st));
-        if (!bs.splatAux) HIPCHK(ctx, bs.splatAux.alloc(128));
-        b.splatList = bs.splatList.get();
-        b.splatListCount = cnt + BDPT_CNT_SPLATS;
-        b.splatListCap = (int)std::min(cap, (size_t)INT32_MAX);
-        b.splatW = (int)f.W;
-        b.splatN0 = (int)(f.W * f.H);
-        b.splatBpb = f.bandRows / 8;
-        b.splatBands = f.numBands;
-        b.splatBand = f.bandIndex;
-    } else if (bandSplit) {   // splats of this rank's light paths land in any pixel: clear the whole buffer
-        mcrt::launch_bdpt_clear_splat((int)N, bs.splat.get(), st);
-    }
-    // depth 0: camera rays (coherent, 8x8 tiles in order) in the first half of queue 0's buffers
-    // with their own count, light rays in the second half with count [0]; ONE launch traces both,
-    // the camera rays as wave packets like PT's camera rays (packet_ctx); both
-    // halves then feed the depth-1 vertex launches, which append to queue 1
-    BdptQueue camQ = queue(0), lightQ = queue(0);
-    camQ.count = cnt + BDPT_CNT_CAM0;
-    lightQ.o += NQ;
-    lightQ.d += NQ;
-    lightQ.t += NQ;
-    {
-        Timed t(ctx, K_BDPT_START, nullptr, (int64_t)f.numTiles * 64 * B, st);
-        mcrt::launch_bdpt_start(sa, f, b, dCam, camQ, lightQ, st);
-    }
-    {
-        TraceCtx tcc = packet_ctx(s);
-        tcc.spill = bs.spill.get();
-        Timed t(ctx, K_EXTEND, camQ.count, 0, st);
-        // exactly the slots k_bdpt_start wrote (the light queue's count, f.numTiles x 64 x B <= NQ)
-        HIPCHK(ctx, mcrt::bdpt_light_sort(bs.lkey.get(), bs.lkey2.get(), bs.lslot.get(), bs.lperm.get(), f.numTiles * 64 * B,
-                                          bs.sortTmp.get(), bs.sortTmp.size(), st));
-        TraceCtx tl = tce;
-        tl.suspendCount = wcap > 0 ? bs.suspendCnt.get() : nullptr;
-        mcrt::launch_extend_pair(tcc, tl, camQ.count, camQ.o, camQ.d, bHits, lightQ.count, lightQ.o, lightQ.d,
-                                 bHits + NQ, bandQ, bandQ, st, bs.lperm.get());   // grids sized to the band
-        if (wcap > 0) mcrt::launch_walk_resume(tl, lightQ.o, lightQ.d, bHits + NQ, bandQ, st);
-    }
-    HIPCHK(ctx, clearKeys(sortRange(2)));   // queue 1 is traced (D >= 1), at round 2
-    {
-        Timed t(ctx, K_BDPT_VERTEX, camQ.count, 0, st);
-        mcrt::launch_bdpt_vertex(sa, f, bk, 1, camQ, bHits, queue(1), bandQ, st);
-    }
-    {
-        Timed t(ctx, K_BDPT_VERTEX, lightQ.count, 0, st);
-        mcrt::launch_bdpt_vertex(sa, f, bk, 1, lightQ, bHits + NQ, queue(1), bandQ, st);
-    }
-    for (int d = 2; d <= D + 1; ++d) {
-        const BdptQueue qIn = queue(d - 1), qOut = queue(d);
-        {
-            Timed t(ctx, K_EXTEND, qIn.count, 0, st);
-            const int nQ = sortRange(d);
-            HIPCHK(ctx, mcrt::bdpt_light_sort(bs.ekey.get(), bs.ekey2.get(), bs.eslot.get(), bs.eperm.get(), nQ,
-                                              bs.sortTmp.get(), bs.sortTmp.size(), st, 16));
-            TraceCtx te = tce;
-            te.suspendCount = wcap > 0 ? bs.suspendCnt.get() + d : nullptr;
-            mcrt::launch_extend(te, qIn.count, qIn.o, qIn.d, bHits, nQ, st, bs.eperm.get());
-            if (wcap > 0) mcrt::launch_walk_resume(te, qIn.o, qIn.d, bHits, nQ, st);
-        }
-        const bool traced = d <= D;   // queue d is traced by the next round
-        if (traced) HIPCHK(ctx, clearKeys(sortRange(d + 1)));
-        Timed t(ctx, K_BDPT_VERTEX, qIn.count, 0, st);
-        mcrt::launch_bdpt_vertex(sa, f, traced ? bk : b, d, qIn, bHits, qOut, nSort, st);
-    }
-    BdptQueue cq;
-    cq.count = cnt + BDPT_CNT_CONN;
-    cq.o = bs.cO.get();
-    cq.d = bs.cD.get();
-    cq.t = bs.cL.get();
-    HIPCHK(ctx, hipStreamWaitEvent(st, fb->bdptConnect, 0));   // sampled-light planes in frame order
-    {
-        Timed t(ctx, K_BDPT_CONNECT, nullptr, (int64_t)f.numTiles * 64 * B, st);
-        mcrt::launch_bdpt_connect(sa, f, b, dCam, cq, st);
-    }
-    HIPCHK(ctx, hipEventRecord(fb->bdptConnect, st));
-    {
-        Timed t(ctx, K_BDPT_VIS, cq.count, 0, st);
-        TraceCtx tvis = tcs;
-        with_hints(tvis, s, nullptr, 0);   // occluder hints by origin cell
-        mcrt::launch_bdpt_vis(tvis, b, cq, (int)(C * N), st);
-    }
-    if (bandSplit) {   // completed by mcrt_bdpt_gather once the ranks' splats are summed
-        fb->bdptPendingGather = true;
-    } else {
-        Timed t(ctx, K_BDPT_GATHER, nullptr, (int64_t)f.numTiles * 64 * B, st);
-        mcrt::launch_bdpt_gather(f, b, slot.radiance.get(), nullptr, 0, st);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    slot.lastPixels = (int64_t)f.numTiles * 64 * B;
-    return MCRT_OK;
-}
-
 static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam, int count,
                                  const mcrt_frame_params* p) {
     if (!s || !fb || !cam || !p) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
@@ -1113,7 +833,7 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "Sobol sampler requires the 1024x52 Sobol matrices in the scene");
     if (p->integrator != MCRT_INTEGRATOR_PT && p->integrator != MCRT_INTEGRATOR_BDPT)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "unknown integrator");
-    if (fb->bdptPendingGather)
+    if (mcrt::bdpt_pending_gather(fb))
         return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
     FrameArgs f;
     std::string err;
@@ -1122,51 +842,28 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
     f.batch = count;
     // frame slot: its buffers are free once the accumulation of its previous frame has read them
     const bool bdpt = p->integrator == MCRT_INTEGRATOR_BDPT;
-    const int S = bdpt && fb->bdptOneSet ? 1 : frames_in_flight(fb, f);
+    const int S = bdpt ? mcrt::bdpt_sets(fb, frames_in_flight(fb, f)) : frames_in_flight(fb, f);
     int ks = fb->next % S;
-    if (bdpt && ks != 0 && fb->bdptDepth == p->max_depth && !fb->bset[ks].camV) {
-        // each BDPT set holds ~C x N x 48 B of connection rays (2.5 GB at 1080p, D = 2): when a
-        // second one does not fit, fall back to one frame in flight instead of failing the frame
-        // (zero-filled on slot ks's stream when it exists, else on slot 0's and finished here: set ks
-        // is then first written on slot ks's stream)
-        hipStream_t zs = fb->slot[ks].stream ? fb->slot[ks].stream : fb->slot[0].stream;
-        hipError_t e = bset_alloc(fb->bset[ks], fb->N, bdpt_queue_cap(fb), p->max_depth, count, zs);
-        if (e == hipSuccess && zs != fb->slot[ks].stream) e = hipStreamSynchronize(zs);
-        if (e == hipErrorOutOfMemory) {
-            hipGetLastError();
-            fb->bdptOneSet = true;
-            ks = 0;
-        } else if (e != hipSuccess) {
-            return fail(ctx, MCRT_ERROR_DEVICE, std::string("BDPT buffers: ") + hipGetErrorString(e));
-        }
+    if (bdpt && ks != 0) {   // a BDPT set that does not fit in device memory sends the frame to slot 0
+        bool usable = true;
+        const mcrt_status r = mcrt::bdpt_reserve_set(fb, ks, p->max_depth, count, &usable);
+        if (r != MCRT_OK) return r;
+        if (!usable) ks = 0;
     }
     FrameSlot& slot = fb->slot[ks];
+    // the queues hold at most the batch's paths of the band: size the ray grids to them (PT; BDPT's
+    // queues are its set's)
+    const int bandPaths = f.numTiles * 64 * count;
+    const size_t qNeed = bdpt ? 0 : std::max(fb->N, (size_t)bandPaths);
+    HIPCHK(ctx, slot_ensure(fb, slot, count, qNeed));
     if (bdpt) {   // BDPT frames overlap the same way (set ks)
-        if (!slot.stream) {
-            HIPCHK(ctx, slot_alloc(slot, fb->N, bdpt_queue_cap(fb), count));
-        } else if (slot.frames < count) {   // radiance planes for a larger batch
-            HIPCHK(ctx, hipEventSynchronize(slot.free));
-            HIPCHK(ctx, hipStreamSynchronize(slot.stream));
-            slot_free(slot);
-            HIPCHK(ctx, slot_alloc(slot, fb->N, bdpt_queue_cap(fb), count));
-        }
         HIPCHK(ctx, hipStreamWaitEvent(slot.stream, slot.free, 0));
         fb->cur = ks;
-        fb->next = (ks + 1) % (fb->bdptOneSet ? 1 : S);
+        fb->next = (ks + 1) % mcrt::bdpt_sets(fb, S);
         slot.lastBatch = count;
-        const mcrt_status r = render_bdpt(s, fb, cam, p, f, ks, slot);
+        const mcrt_status r = mcrt::bdpt_render(s, fb, cam, p, f, ks, slot);
         hipEventRecord(slot.done, slot.stream);
         return r;
-    }
-    // the queues hold at most the batch's paths of the band: size the ray grids to them
-    const int bandPaths = f.numTiles * 64 * count;
-    const size_t qNeed = std::max(fb->N, (size_t)bandPaths);
-    if (!slot.stream) {
-        HIPCHK(ctx, slot_alloc(slot, fb->N, bdpt_queue_cap(fb), count, qNeed));
-    } else if (slot.frames < count || slot.queueCap < qNeed) {   // grow for a larger batch
-        HIPCHK(ctx, hipEventSynchronize(slot.free));
-        slot_free(slot);
-        HIPCHK(ctx, slot_alloc(slot, fb->N, bdpt_queue_cap(fb), count, qNeed));
     }
     const int cap = mcrt::accel_spill_cap(s);
     const size_t spillRays = (std::max((size_t)bandPaths, 2 * qNeed + 64) + 63) / 64 * 64;
@@ -1199,12 +896,8 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
     TraceCtx tcs = trace_ctx(s);
     tcs.spill = slot.spill.get();
     const int qCap = bandPaths;
-    const int wcap = tcs.qnodes && !tcs.twoLevel && p->max_depth > 1 && bandPaths >= walk_min_paths() ? walk_cap() : 0;
-    if (wcap > 0) {
-        HIPCHK(ctx, slot.suspend.grow(MCRT_SUSPEND_F4 * (size_t)qCap, st));
-        if (!slot.suspendCnt) HIPCHK(ctx, slot.suspendCnt.alloc(32));
-        HIPCHK(ctx, hipMemsetAsync(slot.suspendCnt.get(), 0, 32 * sizeof(int), st));
-    }
+    TraceCtx tw = tcs;   // the extension walks' stop rule, when it applies: one suspend count per bounce
+    if (p->max_depth > 1) HIPCHK(ctx, mcrt::walk_rule(tw, bandPaths, slot.suspend, slot.suspendCnt, 32, (size_t)qCap, st));
     if (longest_first()) {
         // the camera / first-shading tiles in descending cost of this slot's previous call (same
         // tiles), and this call's costs recorded for the next one -- all on the slot's stream
@@ -1259,10 +952,10 @@ static mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
             if (tse.hint && ctx->countHints) tse.hintHits = counters + 64 + b;
             if (tse.qnodes && ctx->countHints) tse.retraces = counters + 96 + b;
             if (b == 0) tse.waveClock = wave_clock_buf(fb, 1, 2 * (((size_t)qCap + 63) / 64), st);
-            if (wcap > 0 && b <= walk_max_bounce()) {
-                tse.walkCap = wcap;
-                tse.walkLanes = walk_lanes();
-                tse.suspend = slot.suspend.get();
+            if (tw.walkCap > 0 && b <= walk_max_bounce()) {
+                tse.walkCap = tw.walkCap;
+                tse.walkLanes = tw.walkLanes;
+                tse.suspend = tw.suspend;
                 tse.suspendCount = slot.suspendCnt.get() + b;
             }
             mcrt::launch_shadow_extend(tse, extCnt + b, slot.eO[b & 1].get(), slot.eD[b & 1].get(), hitsE, shadowCnt + b,
@@ -1332,7 +1025,7 @@ MCRT_API mcrt_status mcrt_render_aov(mcrt_scene s, mcrt_framebuffer fb, const mc
 static mcrt_status accumulate(mcrt_framebuffer fb, const mcrt_filter* filters, int nfilters, int32_t frame_index) {
     if (!fb || !filters) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
     mcrt_ctx ctx = fb->ctx;
-    if (fb->bdptPendingGather)
+    if (mcrt::bdpt_pending_gather(fb))
         return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
     if (!fb->haveBands) {   // no frame rendered yet: whole image
         mcrt_frame_params p{};
@@ -1469,12 +1162,7 @@ MCRT_API mcrt_status mcrt_framebuffer_bands_pack(mcrt_framebuffer fb, void* d_ds
     return MCRT_OK;
 }
 
-// The largest rank's row count of a band split (whole 8-row blocks): the rows of one packed chunk.
-static int band_max_rows(const FrameArgs& f) {
-    const int blocks = (int)((f.H + 7) / 8), bpb = f.bandRows / 8;
-    const int perCycle = bpb * f.numBands;
-    return 8 * ((blocks / perCycle) * bpb + std::min(blocks % perCycle, bpb));
-}
+static int band_max_rows(const FrameArgs& f) { return mcrt::band_max_rows(f.H, f.bandRows, f.numBands); }
 
 MCRT_API mcrt_status mcrt_framebuffer_band_layout(mcrt_framebuffer fb, int32_t* max_rows, int32_t* num_bands,
                                                   int32_t* band_index) {
@@ -1510,12 +1198,10 @@ MCRT_API mcrt_status mcrt_framebuffer_stats(mcrt_framebuffer fb, int64_t* closes
     HIPCHK(ctx, fb_sync(fb));
     int c[64];
     if (fb->lastIntegrator == MCRT_INTEGRATOR_BDPT) {   // closest: all subpath rays; any: connection rays
-        HIPCHK(ctx, hipMemcpy(c, cur_bset(fb).bdptCounters.get(), sizeof(c), hipMemcpyDeviceToHost));
-        int64_t cl = 0;
-        for (int d = 0; d <= slot.lastMaxDepth; ++d) cl += c[d];
-        cl += c[BDPT_CNT_CAM0];
+        int64_t cl = 0, an = 0;
+        HIPCHK(ctx, mcrt::bdpt_ray_counts(fb, slot.lastMaxDepth, &cl, &an));
         if (closest_rays) *closest_rays = cl;
-        if (any_rays) *any_rays = c[BDPT_CNT_CONN];
+        if (any_rays) *any_rays = an;
         if (shaded_paths) *shaded_paths = cl;
         return MCRT_OK;
     }
@@ -1531,49 +1217,48 @@ MCRT_API mcrt_status mcrt_framebuffer_stats(mcrt_framebuffer fb, int64_t* closes
     return MCRT_OK;
 }
 
-MCRT_API mcrt_status mcrt_framebuffer_queue_counts(mcrt_framebuffer fb, int32_t* shadow, int32_t* extension, int max) {
+// The per-bounce read-backs of the last PT call: the first n ints of the current slot's counter
+// block once every stream has finished.  Which entries are live is each caller's rule.
+static mcrt_status read_counters(mcrt_framebuffer fb, int max, int* c, size_t n) {
     if (!fb || max < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;
-    const FrameSlot& slot = cur_slot(fb);
     hipSetDevice(ctx->device);
     HIPCHK(ctx, fb_sync(fb));
+    HIPCHK(ctx, hipMemcpy(c, cur_slot(fb).counters.get(), sizeof(int) * n, hipMemcpyDeviceToHost));
+    return MCRT_OK;
+}
+// bounces of the last call when it was a PT call, else none
+static int pt_bounces(mcrt_framebuffer fb) {
+    return fb->lastIntegrator == MCRT_INTEGRATOR_PT ? cur_slot(fb).lastMaxDepth : 0;
+}
+
+MCRT_API mcrt_status mcrt_framebuffer_queue_counts(mcrt_framebuffer fb, int32_t* shadow, int32_t* extension, int max) {
     int c[64];
-    HIPCHK(ctx, hipMemcpy(c, slot.counters.get(), sizeof(c), hipMemcpyDeviceToHost));
+    const mcrt_status st = read_counters(fb, max, c, 64);
+    if (st != MCRT_OK) return st;
     for (int b = 0; b < max && b < 32; ++b) {
-        const bool live = b < slot.lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
+        const bool live = b < pt_bounces(fb);
         if (shadow) shadow[b] = live ? c[b] : 0;
-        if (extension) extension[b] = live && b + 1 < slot.lastMaxDepth ? c[32 + b] : 0;
+        if (extension) extension[b] = live && b + 1 < pt_bounces(fb) ? c[32 + b] : 0;
     }
     return MCRT_OK;
 }
 
 MCRT_API mcrt_status mcrt_framebuffer_hint_counts(mcrt_framebuffer fb, int32_t* hits, int max) {
-    if (!fb || max < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    const FrameSlot& slot = cur_slot(fb);
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, fb_sync(fb));
     int c[128];
-    HIPCHK(ctx, hipMemcpy(c, slot.counters.get(), sizeof(c), hipMemcpyDeviceToHost));
-    for (int b = 0; b < max && b < 32; ++b) {
-        const bool live = b < slot.lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
-        if (hits) hits[b] = live ? c[64 + b] : 0;
-    }
+    const mcrt_status st = read_counters(fb, max, c, 128);
+    if (st != MCRT_OK) return st;
+    for (int b = 0; b < max && b < 32; ++b)
+        if (hits) hits[b] = b < pt_bounces(fb) ? c[64 + b] : 0;
     return MCRT_OK;
 }
 
 MCRT_API mcrt_status mcrt_framebuffer_retrace_counts(mcrt_framebuffer fb, int32_t* retraces, int max) {
-    if (!fb || max < 0) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    const FrameSlot& slot = cur_slot(fb);
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, fb_sync(fb));
     int c[128];
-    HIPCHK(ctx, hipMemcpy(c, slot.counters.get(), sizeof(c), hipMemcpyDeviceToHost));
-    for (int b = 0; b < max && b < 32; ++b) {
-        const bool live = b + 1 < slot.lastMaxDepth && fb->lastIntegrator == MCRT_INTEGRATOR_PT;
-        if (retraces) retraces[b] = live ? c[96 + b] : 0;
-    }
+    const mcrt_status st = read_counters(fb, max, c, 128);
+    if (st != MCRT_OK) return st;
+    for (int b = 0; b < max && b < 32; ++b)
+        if (retraces) retraces[b] = b + 1 < pt_bounces(fb) ? c[96 + b] : 0;
     return MCRT_OK;
 }
 
@@ -1616,186 +1301,10 @@ MCRT_API mcrt_status mcrt_framebuffer_read_queue(mcrt_framebuffer fb, int which,
     return MCRT_OK;
 }
 
-// Rank-major splat layout of a band split of H rows into num_bands interleaved sets of band_rows
-// rows: chunks = num_bands, each of (the largest rank's 8-row block count) x 8 rows x W pixels.
-static size_t splat_chunk_pixels(const FrameArgs& f) {
-    const int blocksTotal = (int)((f.H + 7) / 8), bpb = f.bandRows / 8;
-    int maxBlocks = 0;
-    for (int r = 0; r < f.numBands; ++r) {
-        int nb = 0;
-        for (int gb = 0; gb < blocksTotal; ++gb) nb += ((gb / bpb) % f.numBands == r) ? 1 : 0;
-        maxBlocks = std::max(maxBlocks, nb);
-    }
-    return (size_t)maxBlocks * 8 * f.W;
-}
-
-MCRT_API mcrt_status mcrt_bdpt_splat_layout(mcrt_framebuffer fb, uint64_t* chunk_pixels, int32_t* chunks) {
-    if (!fb || !chunk_pixels || !chunks) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    if (!fb->haveBands) return fail(fb->ctx, MCRT_ERROR_NOT_READY, "no frame rendered yet");
-    *chunk_pixels = splat_chunk_pixels(fb->bands) * (size_t)std::max(fb->bands.batch, 1);   // batch frames per chunk
-    *chunks = fb->bands.numBands;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_set_splat_exchange(mcrt_framebuffer fb, int32_t mode) {
-    if (!fb || (mode != MCRT_SPLAT_EXCHANGE_DENSE && mode != MCRT_SPLAT_EXCHANGE_SPARSE))
-        return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "unknown splat exchange mode");
-    if (fb->bdptPendingGather) return fail(fb->ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed");
-    fb->splatExchange = mode;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_bdpt_splats_sparse(mcrt_framebuffer fb, void* d_dst, int64_t capacity, int64_t* counts,
-                                             int32_t num_counts) {
-    if (!fb || !counts) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    const int bands = fb->bands.numBands;
-    if (num_counts < bands) return fail(ctx, MCRT_ERROR_INVALID_ARG, "counts must hold num_bands entries");
-    for (int r = 0; r < num_counts; ++r) counts[r] = 0;
-    if (!fb->bdptPendingGather) return MCRT_OK;   // nothing pending (light-less scene): no splats
-    if (fb->splatExchange != MCRT_SPLAT_EXCHANGE_SPARSE)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame rendered with the dense splat exchange (mcrt_bdpt_splats_copy)");
-    if (bands > 64) return fail(ctx, MCRT_ERROR_INVALID_ARG, "sparse splat exchange: at most 64 bands");
-    hipSetDevice(ctx->device);
-    BdptSet& bs = cur_bset(fb);
-    hipStream_t st = cur_slot(fb).stream;
-    BdptArgs b{};
-    b.splatList = bs.splatList.get();
-    b.splatListCount = bs.bdptCounters.get() + BDPT_CNT_SPLATS;
-    b.splatListCap = (int)std::min(bs.splatList.size(), (size_t)INT32_MAX);
-    b.splatW = (int)fb->bands.W;
-    b.splatN0 = (int)(fb->bands.W * fb->bands.H);
-    b.splatBpb = fb->bands.bandRows / 8;
-    b.splatBands = bands;
-    b.splatBand = fb->bands.bandIndex;
-    int h[64];
-    HIPCHK(ctx, hipMemsetAsync(bs.splatAux.get(), 0, 128 * sizeof(int), st));
-    mcrt::launch_splat_hist(b, bs.splatAux.get(), st);
-    HIPCHK(ctx, hipMemcpyAsync(h, bs.splatAux.get(), sizeof(int) * bands, hipMemcpyDeviceToHost, st));
-    HIPCHK(ctx, hipStreamSynchronize(st));   // the sizes go to the host (an all-to-all's split sizes)
-    mcrt::SplatOffsets off{};
-    int64_t total = 0;
-    for (int r = 0; r < bands; ++r) {
-        off.off[r] = (int)total;
-        counts[r] = h[r];
-        total += h[r];
-    }
-    if (!d_dst || capacity < total) return MCRT_OK;   // sizes only (the caller grows its buffer and calls again)
-    // the caller's send buffer may still be read by an earlier call's all-to-all on another frame
-    // slot's stream (two frames in flight), and that call's unpack must read its receive buffer
-    // before this call's all-to-all (ordered after this grouping on this stream) overwrites it: wait
-    // for every other slot's completed frame, as mcrt_bdpt_splats_copy does
-    for (auto& k : fb->slot)
-        if (k.stream && k.stream != st) HIPCHK(ctx, hipStreamWaitEvent(st, k.done, 0));
-    mcrt::launch_splat_group(b, off, bs.splatAux.get() + 64, (float4*)d_dst, st);
-    HIPCHK(ctx, hipGetLastError());
-    return MCRT_OK;   // grouping enqueued on the frame's stream
-}
-
-MCRT_API mcrt_status mcrt_bdpt_gather_sparse(mcrt_framebuffer fb, const void* d_recv, int64_t records) {
-    if (!fb || (records > 0 && !d_recv)) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    if (!fb->bdptPendingGather) return MCRT_OK;
-    if (fb->splatExchange != MCRT_SPLAT_EXCHANGE_SPARSE)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame rendered with the dense splat exchange (mcrt_bdpt_gather)");
-    if (records < 0 || records > INT32_MAX) return fail(ctx, MCRT_ERROR_INVALID_ARG, "bad record count");
-    hipSetDevice(ctx->device);
-    FrameSlot& slot = cur_slot(fb);
-    const BdptSet& bs = cur_bset(fb);
-    hipStream_t st = slot.stream;
-    mcrt::launch_splat_unpack((const float4*)d_recv, (int)records, bs.splat.get(), st);
-    BdptArgs b{};
-    b.slots = bs.slots.get();
-    b.splat = bs.splat.get();
-    b.ownSlots = bdpt_max_connections(fb->bdptDepth) - fb->bdptDepth;
-    {
-        Timed t(ctx, K_BDPT_GATHER, nullptr, (int64_t)fb->bands.numTiles * 64 * fb->bands.batch, st);
-        mcrt::launch_bdpt_gather(fb->bands, b, slot.radiance.get(), nullptr, 0, st);   // the rank's own plane
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(slot.done, st));
-    fb->bdptPendingGather = false;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_bdpt_splats_copy(mcrt_framebuffer fb, void* d_dst) {
-    if (!fb || !d_dst) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    if (fb->bdptPendingGather && fb->splatExchange == MCRT_SPLAT_EXCHANGE_SPARSE)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame rendered with the sparse splat exchange (mcrt_bdpt_splats_sparse)");
-    if (!fb->haveBands) return fail(ctx, MCRT_ERROR_NOT_READY, "no frame rendered yet");
-    hipSetDevice(ctx->device);
-    const size_t chunk = splat_chunk_pixels(fb->bands);   // per frame; a rank's chunk holds batch of them
-    const size_t total = chunk * (size_t)std::max(fb->bands.batch, 1) * (size_t)fb->bands.numBands;
-    FrameSlot& slot = cur_slot(fb);
-    hipStream_t st = slot.stream ? slot.stream : ctx->stream;
-    // the caller's buffer may still be read by an earlier frame's gather on another slot's stream
-    for (auto& k : fb->slot)
-        if (k.stream && k.stream != st) HIPCHK(ctx, hipStreamWaitEvent(st, k.done, 0));
-    HIPCHK(ctx, hipMemsetAsync(d_dst, 0, sizeof(float) * MCRT_SPLAT_CHANNELS * total, st));
-    if (fb->bdptPendingGather)   // (else, e.g. a scene without lights: the frame is complete, no splats)
-        mcrt::launch_bdpt_splat_pack(fb->bands, chunk, cur_bset(fb).splat.get(), (float*)d_dst, st);
-    HIPCHK(ctx, hipGetLastError());
-    return MCRT_OK;   // enqueued on the frame's stream (mcrt_framebuffer_stream): no host sync
-}
-
 MCRT_API mcrt_status mcrt_framebuffer_stream(mcrt_framebuffer fb, void** stream) {
     if (!fb || !stream) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
     const FrameSlot& slot = cur_slot(fb);
     *stream = (void*)(slot.stream ? slot.stream : fb->ctx->stream);
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_bdpt_gather(mcrt_framebuffer fb, const void* d_own_chunk) {
-    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
-    mcrt_ctx ctx = fb->ctx;
-    if (!fb->bdptPendingGather) return MCRT_OK;   // nothing deferred (whole-image or light-less frame)
-    if (fb->splatExchange == MCRT_SPLAT_EXCHANGE_SPARSE)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame rendered with the sparse splat exchange (mcrt_bdpt_gather_sparse)");
-    hipSetDevice(ctx->device);
-    FrameSlot& slot = cur_slot(fb);
-    hipStream_t st = slot.stream;
-    BdptArgs b{};
-    b.slots = cur_bset(fb).slots.get();
-    b.splat = cur_bset(fb).splat.get();
-    b.ownSlots = bdpt_max_connections(fb->bdptDepth) - fb->bdptDepth;
-    {
-        Timed t(ctx, K_BDPT_GATHER, nullptr, (int64_t)fb->bands.numTiles * 64 * fb->bands.batch, st);
-        mcrt::launch_bdpt_gather(fb->bands, b, slot.radiance.get(), (const float*)d_own_chunk,
-                                 splat_chunk_pixels(fb->bands), st);
-    }
-    HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipEventRecord(slot.done, st));
-    fb->bdptPendingGather = false;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_read_bdpt(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
-                                                uint64_t* needed) {
-    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
-    mcrt_ctx ctx = fb->ctx;
-    if (fb->bdptDepth <= 0) return fail(ctx, MCRT_ERROR_INVALID_ARG, "no BDPT frame rendered yet");
-    // the planes of the last BDPT call's batch (plane stride N x batch)
-    const size_t N = fb->N * (size_t)fb->bdptBatch, D = (size_t)fb->bdptDepth;
-    const size_t C = (size_t)bdpt_max_connections(fb->bdptDepth);
-    const BdptSet& bs = cur_bset(fb);
-    const void* src = nullptr;
-    size_t sz = 0;
-    switch (which) {
-    case 0: src = bs.camV.get(); sz = 16 * N * BDPT_VERTEX_PLANES * (D + 2); break;
-    case 1: src = bs.lightV.get(); sz = 16 * N * BDPT_VERTEX_PLANES * (D + 1); break;
-    case 2: src = bs.camCount.get(); sz = 4 * N; break;
-    case 3: src = bs.lightCount.get(); sz = 4 * N; break;
-    case 4: src = bs.slots.get(); sz = 16 * N * (C - D); break;
-    case 5: src = fb->sampLight.get(); sz = 16 * fb->N * D; break;   // per pixel, carried across frames
-    case 6: src = bs.splat.get(); sz = 16 * N; break;
-    default: return fail(ctx, MCRT_ERROR_INVALID_ARG, "which must be 0..6");
-    }
-    if (needed) *needed = sz;
-    if (!host_dst || bytes == 0) return MCRT_OK;
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, fb_sync(fb));
-    HIPCHK(ctx, hipMemcpy(host_dst, src, std::min<size_t>(sz, bytes), hipMemcpyDeviceToHost));
     return MCRT_OK;
 }
 

@@ -624,7 +624,7 @@ static mcrt_status temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* c
     if (motion && !d.haveMotion)
         return fail(ctx, MCRT_ERROR_NOT_READY,
                     "no motion planes for these guides (mcrt_render_guides_motion / mcrt_framebuffer_set_motion)");
-    if (fb->bdptPendingGather)
+    if (mcrt::bdpt_pending_gather(fb))
         return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
     hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
@@ -735,7 +735,7 @@ static mcrt_status atrous_chain(mcrt_framebuffer fb, const mcrt_guided_denoise_p
     if (feedback_level < -1 || feedback_level > p->levels - 2)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "feedback_level must be -1 .. levels - 2");
     if (!d.haveGuides) return fail(ctx, MCRT_ERROR_NOT_READY, "no guides (mcrt_render_guides / mcrt_framebuffer_set_guides)");
-    if (fb->bdptPendingGather)
+    if (mcrt::bdpt_pending_gather(fb))
         return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
     hipSetDevice(ctx->device);
     AtrousIn in;

@@ -2,9 +2,9 @@
 // the few helpers of mcrt_capi.cpp that host code in another file may call.  Not part of the ABI.
 //
 // This is the boundary for host code outside mcrt_capi.cpp: a subsystem with entry points of its
-// own (mcrt_denoise.hip, mcrt_accel.cpp) includes it, reaches the runtime through what is declared
-// here and nothing else, and keeps its state in one struct held by the frame buffer (DenoiseState)
-// or the scene (AccelState).  It compiles as plain
+// own (mcrt_denoise.hip, mcrt_accel.cpp, mcrt_bdpt_host.cpp) includes it, reaches the runtime
+// through what is declared here and nothing else, and keeps its state in one struct held by the
+// frame buffer (DenoiseState, BdptState) or the scene (AccelState).  It compiles as plain
 // C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip translation unit.
 #pragma once
 #include <climits>
@@ -179,6 +179,29 @@ struct BdptSet {
     DevBuf<int> suspendCnt;
 };
 
+// The bidirectional integrator's host state (mcrt_bdpt_host.cpp), allocated by the first BDPT frame
+// of a max depth.  Only mcrt_bdpt_host.cpp names its fields; the rest of the runtime goes through
+// the functions declared below.  The per-frame arrays exist once per frame slot; the
+// sampled-light-vertex planes carry state from frame to frame (BDPT.cl:585), so they are shared and
+// the connect launches stay in frame order.
+struct BdptState {
+    int depth = 0;                 // max depth the arrays are sized for (0: none)
+    BdptSet set[MCRT_MAX_FRAMES_IN_FLIGHT];
+    hipEvent_t connect = nullptr;  // recorded after the last enqueued frame's connect launch
+    DevBuf<float4> sampLight;      // the sampled-light-vertex planes (D x N)
+    int batch = 1;                 // frames of the last BDPT call (plane stride N x batch)
+    bool oneSet = false;           // a second set did not fit in HBM: BDPT frames use slot 0 only
+    bool pendingGather = false;    // band-split frame waiting for the ranks' summed splats
+    int splatExchange = MCRT_SPLAT_EXCHANGE_DENSE;   // mcrt_framebuffer_set_splat_exchange
+    int cur = 0;                   // the set of the last BDPT call, as mcrt_framebuffer_s::cur is its slot
+    // frees the sets, the shared planes and the event (the next frame allocates for its depth);
+    // the caller has finished every stream that may use them
+    void reset();
+    ~BdptState() { reset(); }
+};
+// strategies (s, t) of a path of max depth D (RTBDPTPass.cpp:404-408)
+inline int bdpt_max_connections(int D) { const int t = D + 2; return t * (t + 1) / 2 - 2; }
+
 // The denoiser's state (mcrt_denoise.hip), every plane allocated on first use.
 struct DenoiseState {
     // Guided denoiser (mcrt_denoise_guided): the guides of the camera-ray hits, the luminance
@@ -228,22 +251,11 @@ struct mcrt_framebuffer_s {
     DevBuf<uint32_t> hintPix;    // occluder hint of each pixel's bounce-0 shadow ray (TraceCtx::hint)
     FrameArgs bands{};      // band layout of the last mcrt_render_frame (used by mcrt_accumulate)
     bool haveBands = false;
-    // BDPT state (allocated on the first BDPT frame for a max depth; mcrt_bdpt.hip has the layout):
-    // per-frame arrays per frame slot; the sampled-light-vertex planes carry state from frame to
-    // frame (BDPT.cl:585), so they are shared and the connect launches stay in frame order
-    int bdptDepth = 0;
-    BdptSet bset[MCRT_MAX_FRAMES_IN_FLIGHT];
-    hipEvent_t bdptConnect = nullptr;   // recorded after the last enqueued frame's connect launch
     // diagnostics (MCRT_WAVE_CLOCK=1): per-workgroup (start, end) clocks of the last PT call's camera,
     // shadow+extension and last shadow launches (mcrt_framebuffer_wave_clock)
     DevBuf<uint32_t> waveClk[3];   // 2 words per workgroup
-    DevBuf<float4> sampLight;      // the sampled-light-vertex planes (D x N)
     int lastIntegrator = MCRT_INTEGRATOR_PT;
-    int bdptBatch = 1;           // frames of the last BDPT call (plane stride N x bdptBatch)
-    bool bdptOneSet = false;     // a second BDPT set did not fit in HBM: BDPT frames use slot 0 only
-    bool bdptPendingGather = false;   // band-split BDPT frame waiting for the ranks' summed splats
-    int splatExchange = MCRT_SPLAT_EXCHANGE_DENSE;   // mcrt_framebuffer_set_splat_exchange
-    int bdptSet = 0;             // the BDPT set of the last BDPT call
+    BdptState bd;
     DenoiseState dn;
 };
 // The slot of the last rendered frame: what the read-back entry points show.  After a failed
@@ -267,6 +279,29 @@ hipError_t fb_sync(mcrt_framebuffer fb);
 // that reads or rewrites slot buffers: BDPT, AOVs, device copies).
 void ctx_wait_slots(mcrt_framebuffer fb);
 bool frame_args(mcrt_framebuffer fb, const mcrt_frame_params* p, FrameArgs& f, std::string& err);
+// Lanes of the 8x8 tiles covering the image (>= N): the packed camera-hit slots of a frame and one
+// start-queue entry per lane of BDPT's tile walk
+inline size_t tile_lanes(mcrt_framebuffer fb) { return (size_t)((fb->W + 7) / 8) * ((fb->H + 7) / 8) * 64; }
+// Stop rule of the extension rays' compact walks (TraceCtx::walkCap) for a call of `paths` paths:
+// when the tree has compact records and the call is large enough (MCRT_WALK_CAP, MCRT_WALK_MIN_PATHS),
+// sizes `suspend` for `entries` queue entries, zeroes the `counts` suspend counters on st and fills
+// c.walkCap / walkLanes / suspend; otherwise c.walkCap stays 0.  Whether the rule is wanted at all,
+// and for which launches, is the caller's.
+hipError_t walk_rule(TraceCtx& c, int64_t paths, DevBuf<float4>& suspend, DevBuf<int>& suspendCnt, int counts,
+                     size_t entries, hipStream_t st);
+// mcrt_bdpt_host.cpp: the bidirectional integrator
+// One BDPT call of f.batch frames in frame slot `slot` with set k, enqueued on the slot's stream
+// (the caller has made the slot ready and records its `done`).
+mcrt_status bdpt_render(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam, const mcrt_frame_params* p,
+                        const FrameArgs& f, int k, FrameSlot& slot);
+// Set k > 0 for a call of `frames` frames at this depth, allocated here if the frame buffer's arrays
+// are of that depth and lack it.  *usable = false: it did not fit in device memory, and BDPT frames
+// of this frame buffer use set 0 alone from now on (bdpt_sets).
+mcrt_status bdpt_reserve_set(mcrt_framebuffer fb, int k, int depth, int frames, bool* usable);
+int bdpt_sets(mcrt_framebuffer fb, int slots);   // sets BDPT frames rotate over, of `slots` frame slots: 1 or `slots`
+bool bdpt_pending_gather(mcrt_framebuffer fb);   // a band-split frame waits for mcrt_bdpt_gather(_sparse)
+// rays of the last BDPT call (max depth `depth`), read from its set: all subpath rays, connection rays
+hipError_t bdpt_ray_counts(mcrt_framebuffer fb, int depth, int64_t* closest, int64_t* any);
 // mcrt_accel.cpp: the views of the scene's acceleration structure and the little else of it that
 // the rest of the runtime reads
 bool accel_ready(mcrt_scene s);            // mcrt_accel_build has made a structure

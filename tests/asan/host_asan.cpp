@@ -2,7 +2,7 @@
 // (mcrt_camera.cpp), the host Bvh2 restatement (mcrt_bvh.cpp), the acceleration structure's host layer
 // (mcrt_accel_host.cpp over mcrt_bvh.cpp and mcrt_bvh2l.cpp) and the oracle (oracle/mcrt_oracle.c:
 // BVH build, closest / any-hit traversal against brute force, one PT and one BDPT frame, accumulate,
-// denoise, tone map), the scene-table check (check_scene_tables) and the runtime's owning device-buffer type (mcrt_devbuf.h, over malloc / free), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
+// denoise, tone map), the scene-table check (check_scene_tables), the band split's arithmetic (mcrt_bands.h) and the runtime's owning device-buffer type (mcrt_devbuf.h, over malloc / free), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
 // every check held and the sanitizers reported nothing (they abort on the first finding).
 #include <unistd.h>
 
@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "../../monte-carlo-raytracer_amd/csrc/mcrt_bands.h"
 #include "../../monte-carlo-raytracer_amd/csrc/mcrt_devbuf.h"
 #include "../../monte-carlo-raytracer_amd/csrc/mcrt_internal.h"
 extern "C" {
@@ -429,9 +430,39 @@ static void write_file(const std::string& p, const char* text) {
     std::fclose(f);
 }
 
+// The band split's closed forms (mcrt_bands.h) against the plain counting loops they replaced: a
+// rank's 8-row blocks (the loop of frame_args), the largest rank's rows and the splat layout's
+// chunk pixels (the loops of the former splat_chunk_pixels), for every image height up to 399
+// rows, bands of 1..4 blocks and 1..16 ranks.
+static int band_checks() {
+    const uint32_t W = 37;
+    int cases = 0;
+    for (uint32_t H = 1; H < 400; ++H)
+        for (int bandRows = 8; bandRows <= 32; bandRows += 8)
+            for (int nb = 1; nb <= 16; ++nb) {
+                const int blocksTotal = (int)((H + 7) / 8), bpb = bandRows / 8;
+                int sum = 0, maxBlocks = 0;
+                for (int r = 0; r < nb; ++r) {
+                    int n = 0;
+                    for (int gb = 0; gb < blocksTotal; ++gb) n += ((gb / bpb) % nb == r) ? 1 : 0;
+                    CHECK(mcrt::band_blocks(H, bandRows, nb, r) == n);
+                    CHECK(n <= mcrt::band_blocks(H, bandRows, nb, 0));   // rank 0 holds the most
+                    sum += n;
+                    maxBlocks = std::max(maxBlocks, n);
+                }
+                CHECK(sum == blocksTotal);
+                CHECK(mcrt::band_max_rows(H, bandRows, nb) == 8 * maxBlocks);
+                CHECK((size_t)mcrt::band_max_rows(H, bandRows, nb) * W == (size_t)maxBlocks * 8 * W);
+                ++cases;
+            }
+    CHECK(cases == 399 * 4 * 16);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc == 3 && std::strcmp(argv[1], "--tables") == 0) return tables_file(argv[2]);
     if (devbuf_checks() != 0) return 1;
+    if (band_checks() != 0) return 1;
     if (table_checks() != 0) return 1;
     // a room (floor, back wall), a box, an emissive quad and a quad fan, with an MTL
     char tmpl[] = "/tmp/mcrt_asan_XXXXXX";

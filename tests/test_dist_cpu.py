@@ -314,6 +314,23 @@ def test_rank_major_splat_layout(height, band_rows, world):
     assert (seen == 1).all()
 
 
+@pytest.mark.parametrize("height,band_rows,world", [(36, 8, 2), (64, 8, 3), (1080, 8, 8), (1080, 16, 3), (100, 24, 4)])
+def test_splat_chunk_rows_is_the_runtime_closed_form(height, band_rows, world):
+    """mcrt.dist.splat_chunk_rows (a maximum over the ranks' counted blocks) against the closed form
+    the host runtime sizes its chunks with (csrc/mcrt_bands.h band_blocks / band_max_rows, restated
+    here: mcrt_framebuffer_band_layout, which reports it, needs a frame buffer and so a GPU): every
+    rank's block count, their sum, and rank 0 as the largest."""
+    blocks, bpb = (height + 7) // 8, band_rows // 8
+
+    def band_blocks(r):
+        return (blocks // (bpb * world)) * bpb + min(max(blocks % (bpb * world) - r * bpb, 0), bpb)
+
+    counts = [band_blocks(r) for r in range(world)]
+    assert counts == [len(mdist.band_blocks(height, band_rows, world, r)) for r in range(world)]
+    assert sum(counts) == blocks and max(counts) == counts[0]
+    assert mdist.splat_chunk_rows(height, band_rows, world) == 8 * counts[0]
+
+
 class _FakeSparseFB:
     """The splat-list side of a band-split BDPT frame (mcrt_bdpt_splats_sparse / gather_sparse) on
     the CPU: random splat records of this rank, each owned by the rank whose 8-row bands hold its

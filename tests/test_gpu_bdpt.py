@@ -548,3 +548,95 @@ def test_sparse_exchange_two_frames_in_flight(hip_ctx):
         close = np.abs(x[fin] - y[fin]) <= REL_TOL * (np.abs(x[fin]) + np.abs(y[fin])) + 1e-30
         assert close.all(), (r, int((~close).sum()))
     ds.close()
+
+
+def _refused(call, status, text):
+    """`call` raises MCRTError with this status code and exactly this message."""
+    from mcrt import lib
+    with pytest.raises(lib.MCRTError) as e:
+        call()
+    assert str(e.value) == f"mcrt status {status}: {text}", str(e.value)
+
+
+def test_bdpt_call_order_refusals(hip_ctx):
+    """The order in which the band-split BDPT calls may follow each other, with the status code and
+    message of every refusal (the strings of mcrt_capi.cpp before the integrator's host side became
+    mcrt_bdpt_host.cpp, quoted here): one frame buffer, rank 0 of two bands, depth 2.  A frame waiting
+    for its splat exchange refuses the next render, the accumulation and a change of the exchange;
+    a dense frame refuses the sparse calls and a sparse frame the dense ones; a light-less scene's
+    frame is complete at once, so every exchange call returns OK with nothing to do.  Every refused
+    call returns before it touches the device."""
+    import torch
+    from mcrt import lib
+    INVALID_ARG, NOT_READY = 1, 4
+    pending = "band-split BDPT frame not completed (mcrt_bdpt_gather)"
+    name, W, H, D, ranks = "mixed", 96, 64, 2, 2
+    sc = build_scene(name)
+    ds = lib.DeviceScene(hip_ctx, sc)
+    cam = scene_camera(name, W, H)
+    filt = T.make_filter(T.BOX)
+    fb = lib.FrameBuffer(hip_ctx, W, H)
+    _refused(lambda: fb.read_bdpt("splat"), INVALID_ARG, "no BDPT frame rendered yet")
+
+    def render(scene=ds):
+        fb.render(scene, cam, frame=0, max_depth=D, integrator=T.INTEGRATOR_BDPT, band_rows=8, num_bands=ranks,
+                  band_index=0)
+
+    def refuses_next_steps():
+        _refused(render, NOT_READY, pending)
+        _refused(lambda: fb.accumulate(filt, 0), NOT_READY, pending)
+        for sparse in (False, True):
+            _refused(lambda: fb.set_splat_exchange(sparse), NOT_READY, "band-split BDPT frame not completed")
+
+    chunk_pixels, chunks = None, None
+    # a dense frame, before mcrt_bdpt_gather
+    render()
+    refuses_next_steps()
+    _refused(fb.bdpt_splats_sparse, INVALID_ARG,
+             "frame rendered with the dense splat exchange (mcrt_bdpt_splats_copy)")
+    _refused(lambda: fb.bdpt_gather_sparse(None, 0), INVALID_ARG,
+             "frame rendered with the dense splat exchange (mcrt_bdpt_gather)")
+    chunk_pixels, chunks = fb.bdpt_splat_layout()
+    assert chunks == ranks
+    buf = torch.zeros(3 * chunk_pixels * chunks, dtype=torch.float32, device="cuda")
+    fb.bdpt_splats_copy(buf.data_ptr())
+    fb.bdpt_gather(buf.data_ptr())   # chunk 0: this rank's rows of its own splats
+    # ... and after it: nothing is pending, so the sparse calls have nothing to do
+    fb.accumulate(filt, 0)
+    assert not fb.bdpt_splats_sparse().any()
+    fb.bdpt_gather_sparse(None, 0)
+    fb.set_splat_exchange(True)
+    # a sparse frame: the mirror image
+    render()
+    refuses_next_steps()
+    _refused(lambda: fb.bdpt_splats_copy(buf.data_ptr()), INVALID_ARG,
+             "frame rendered with the sparse splat exchange (mcrt_bdpt_splats_sparse)")
+    _refused(lambda: fb.bdpt_gather(buf.data_ptr()), INVALID_ARG,
+             "frame rendered with the sparse splat exchange (mcrt_bdpt_gather_sparse)")
+    counts = fb.bdpt_splats_sparse()
+    assert counts.shape == (ranks,) and counts[0] == 0
+    send = torch.zeros(4 * max(int(counts.sum()), 1), dtype=torch.float32, device="cuda")
+    np.testing.assert_array_equal(fb.bdpt_splats_sparse(send.data_ptr(), send.numel() // 4), counts)
+    fb.bdpt_gather_sparse(None, 0)   # nothing received: the rank's own plane
+    fb.accumulate(filt, 1)
+    fb.bdpt_splats_copy(buf.data_ptr())
+    fb.bdpt_gather(buf.data_ptr())
+    fb.set_splat_exchange(False)
+    assert np.isfinite(fb.read(2)).all() and fb.read(2)[..., :3].max() > 0
+    # a scene without lights: the frame is complete when mcrt_render_frame returns
+    dark = lib.DeviceScene(hip_ctx, sc)
+    shapes = sc.shapes.copy()
+    shapes["lightID"] = -1   # (an empty light table is legal only when no shape names a light)
+    dark.update_shapes(shapes)
+    dark.update_lights(np.zeros(0, T.LIGHT_DTYPE))
+    for sparse in (False, True):
+        fb.set_splat_exchange(sparse)
+        render(dark)
+        fb.bdpt_gather(None)
+        fb.bdpt_gather_sparse(None, 0)
+        assert not fb.bdpt_splats_sparse().any()
+        fb.accumulate(filt, 2)   # nothing was pending
+        assert not fb.read(0).any()
+    fb.close()
+    dark.close()
+    ds.close()

@@ -2,7 +2,7 @@
 bench.py's timed region take on the host (camera records, mcrt_render_frames, mcrt_accumulate), and
 the wall time of a whole synchronised call against its GPU span (HIP events on the frame's stream).
 Small scene so the GPU work is short and the fixed host costs stand out.
-usage: python tools/host_overhead.py [frames_per_call] [repeats]"""
+usage: python tools/host_overhead.py [frames_per_call] [repeats] [pt|bdpt]"""
 import json
 import os
 import sys
@@ -21,6 +21,8 @@ def main():
     from mcrt.camera import scene_camera
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 20
+    name = sys.argv[3] if len(sys.argv) > 3 else "pt"
+    integ = {"pt": T.INTEGRATOR_PT, "bdpt": T.INTEGRATOR_BDPT}[name]
     W, H = 480, 272
     sc = scenes.dragon_proxy(tris=200_000)
     cams = [scene_camera("dragon_proxy", W, H, frame=f, jitter=True) for f in range(64)]
@@ -28,7 +30,7 @@ def main():
     ds = lib.DeviceScene(ctx, sc)
     fb = lib.FrameBuffer(ctx, W, H)
     filt = T.make_filter(T.BOX)
-    out = {"frames_per_call": n, "W": W, "H": H}
+    out = {"integrator": name, "frames_per_call": n, "W": W, "H": H}
     rec, call, acc, wall = [], [], [], []
     for r in range(reps + 3):
         f0 = r * n
@@ -37,7 +39,7 @@ def main():
         t0 = time.perf_counter()
         cl = [cams[(f0 + k) % 64] for k in range(n)]
         t1 = time.perf_counter()
-        fb.render_frames(ds, cl, frame=f0, max_depth=2)
+        fb.render_frames(ds, cl, frame=f0, max_depth=2, integrator=integ)
         t2 = time.perf_counter()
         fb.accumulate(filt, f0)
         t3 = time.perf_counter()
@@ -53,7 +55,7 @@ def main():
     ctx.reset_stats()
     fb.set_frames_in_flight(1)
     for r in range(reps):
-        fb.render_frames(ds, [cams[(k + r) % 64] for k in range(n)], frame=r * n, max_depth=2)
+        fb.render_frames(ds, [cams[(k + r) % 64] for k in range(n)], frame=r * n, max_depth=2, integrator=integ)
         fb.accumulate(filt, r * n)
     ctx.sync()
     ks = ctx.kernel_stats()
