@@ -754,6 +754,9 @@ MCRT_API mcrt_status mcrt_framebuffer_read_frame(mcrt_framebuffer fb, int32_t k,
  * 2 image (float4), 3 weight sum (float).  Enqueued on the context stream, ordered after the
  * last render; the radiance copy keeps that frame's slot from taking a new frame until read. */
 MCRT_API mcrt_status mcrt_framebuffer_copy_device(mcrt_framebuffer fb, int which, void* d_dst);
+/* mcrt_framebuffer_copy_device 0 for frame k (0 <= k < count) of the last mcrt_render_frames call:
+ * W*H float4, enqueued on the context stream with the same ordering and slot hold. */
+MCRT_API mcrt_status mcrt_framebuffer_copy_device_frame(mcrt_framebuffer fb, int32_t k, void* d_dst);
 /* Inverse for multi-GPU: overwrite the weighted sums (float4) and weights (float) from device
  * memory (after a reduce) and recompute the image = sum / weight on the device. */
 MCRT_API mcrt_status mcrt_framebuffer_set_accumulation(mcrt_framebuffer fb, const void* d_wsum, const void* d_wts);

@@ -1022,9 +1022,14 @@ MCRT_DEV void connectOne(const SceneArgs& s, const FrameArgs& f, const BdptArgs&
         const f3 c = L * misWeight;
         const bool nonzero = c.x != 0.0f || c.y != 0.0f || c.z != 0.0f;
         if (CLS != CONN_EMIT && nonzero) push = needRay;   // no connection ray = not visible (contributes 0)
+        // A NaN contribution (a light subpath whose throughput is 0 / 0, BDPT.cl:310) is neither black
+        // nor not black: the reference splats a light-tracing strategy only if isNotBlack (BDPT.cl:893),
+        // so a NaN one is dropped, and adds an own strategy unguarded as radiance * visibility * weight
+        // (BDPT.cl:734, 904-906), so one without a ray is NaN * 0 = NaN, not 0
+        if (CLS == CONN_LIGHT && !isNotBlack(L)) push = false;
         if (CLS != CONN_LIGHT) {
             const int own = ownSlotOf(t, sI, D);
-            const f3 o = (CLS == CONN_EMIT || push) ? c : splat3(0.0f);
+            const f3 o = (CLS == CONN_EMIT || push) ? c : c * 0.0f;
             b.slots[(size_t)own * N + pix] = make_float4(o.x, o.y, o.z, 0.0f);
             if (push) code = own * N + pix;
         }

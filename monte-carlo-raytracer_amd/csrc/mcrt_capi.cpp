@@ -1141,6 +1141,21 @@ MCRT_API mcrt_status mcrt_framebuffer_copy_device(mcrt_framebuffer fb, int which
     return MCRT_OK;
 }
 
+MCRT_API mcrt_status mcrt_framebuffer_copy_device_frame(mcrt_framebuffer fb, int32_t k, void* d_dst) {
+    if (!fb || !d_dst) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
+    mcrt_ctx ctx = fb->ctx;
+    FrameSlot& slot = cur_slot(fb);
+    if (k < 0 || k >= std::max(slot.lastBatch, 1))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame index outside the last mcrt_render_frames batch");
+    if (!slot.radiance) return fail(ctx, MCRT_ERROR_NOT_READY, "no frame rendered yet");
+    hipSetDevice(ctx->device);
+    ctx_wait_slots(fb);
+    HIPCHK(ctx, hipMemcpyAsync(d_dst, slot.radiance.get() + (size_t)k * fb->N, 16 * fb->N, hipMemcpyDeviceToDevice,
+                               ctx->stream));
+    HIPCHK(ctx, hipEventRecord(slot.free, ctx->stream));   // as mcrt_framebuffer_copy_device 0
+    return MCRT_OK;
+}
+
 MCRT_API mcrt_status mcrt_framebuffer_set_accumulation(mcrt_framebuffer fb, const void* d_wsum, const void* d_wts) {
     if (!fb || !d_wsum || !d_wts) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
     mcrt_ctx ctx = fb->ctx;

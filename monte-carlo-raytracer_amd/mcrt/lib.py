@@ -83,6 +83,7 @@ SIGNATURES = {
     "mcrt_framebuffer_read_frame": (_c.c_int, [_vp, _c.c_int32, _vp]),
     "mcrt_framebuffer_stats": (_c.c_int, [_vp, _vp, _vp, _vp]),
     "mcrt_framebuffer_copy_device": (_c.c_int, [_vp, _c.c_int, _vp]),
+    "mcrt_framebuffer_copy_device_frame": (_c.c_int, [_vp, _c.c_int32, _vp]),
     "mcrt_framebuffer_set_accumulation": (_c.c_int, [_vp, _vp, _vp]),
     "mcrt_framebuffer_bands_pack": (_c.c_int, [_vp, _vp]),
     "mcrt_framebuffer_bands_unpack": (_c.c_int, [_vp, _vp, _c.c_int32]),
@@ -572,6 +573,11 @@ class FrameBuffer:
 
     def copy_device(self, which, dst_ptr):
         _check(lib().mcrt_framebuffer_copy_device(self.h, which, dst_ptr), self.ctx.h)
+
+    def copy_device_frame(self, k, dst_ptr):
+        """Radiance of frame k of the last render_frames batch into device memory, on the context
+        stream (mcrt_framebuffer_copy_device_frame)."""
+        _check(lib().mcrt_framebuffer_copy_device_frame(self.h, k, dst_ptr), self.ctx.h)
 
     def bdpt_splat_layout(self):
         """(chunk_pixels, chunks) of the rank-major splat layout of the last band split."""

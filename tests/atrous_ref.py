@@ -39,11 +39,17 @@ def guides_from_arrays(normals, points, albedo, hit, cam_pos):
     return npl, ad
 
 
+def cl_clamp(x, lo, hi):
+    """The device's clamp (v_med3_f32) = OpenCL's fmin(fmax(x, lo), hi): a NaN x gives lo (np.clip
+    would pass the NaN on)."""
+    return np.fmin(np.fmax(np.asarray(x, F), F(lo)), F(hi))
+
+
 def accumulate_moments(frames, moments=None):
     """k_moments: sequential float32 sums over `frames` (each (H, W, >=3) radiance); moments None
-    starts at frame 0 (overwrite)."""
+    starts at frame 0 (overwrite).  A NaN radiance counts as 0, as in k_accumulate."""
     for k, fr in enumerate(frames):
-        l = luminance(np.clip(np.asarray(fr, F)[..., :3], F(0), F(1000)))
+        l = luminance(cl_clamp(np.asarray(fr, F)[..., :3], 0, 1000))
         ll = l * l
         if moments is None:
             moments = np.stack([l, ll], -1).astype(F)

@@ -37,21 +37,35 @@ BDPT_CASES = [  # (scene, W, H, frames rendered in order from fresh buffers, max
 ]
 
 
+# The same, each frame with its TAA-jittered camera (scene_camera(..., frame=f, jitter=True)): frames
+# 0..11 of the mixed scene cross frame 10, whose pixel (row 35, column 78) is NaN (BDPT.cl:310 divides
+# 0 by 0 for a light ray leaving an area light at cos = 0; tests/test_oracle_bdpt_cpu.py)
+BDPT_TAA_CASES = [
+    ("mixed", 96, 64, tuple(range(12)), 2),
+]
+BDPT_NAN_FRAME, BDPT_NAN_PIXEL = 10, (35, 78)   # (row, column), as the oracle finds it
+
+
 def bdpt_key(case):
     name, W, H, frames, D = case
-    return f"bdpt_{name}_{W}x{H}_d{D}"
+    return f"bdpt_{name}_{W}x{H}_d{D}" + ("_taa" if case in BDPT_TAA_CASES else "")
+
+
+def bdpt_camera(case, f):
+    """Camera of frame f of a BDPT case: fixed, or the frame's TAA jitter for a BDPT_TAA_CASES case."""
+    name, W, H, frames, D = case
+    return scene_camera(name, W, H, frame=f, jitter=True) if case in BDPT_TAA_CASES else scene_camera(name, W, H)
 
 
 def bdpt_job(out_path, variant):
     """RTBDPTPass frames (fresh buffers per case) + the last frame's vertex arrays and counts."""
     res = {}
-    for case in BDPT_CASES:
+    for case in BDPT_CASES + BDPT_TAA_CASES:
         name, W, H, frames, D = case
         cs = po.CLRefScene(build_scene(name), variant)
-        cam = scene_camera(name, W, H)
         key = bdpt_key(case)
         for f in frames:
-            res[f"{key}_f{f}"] = cs.render_bdpt(cam, frame=f, max_depth=D)
+            res[f"{key}_f{f}"] = cs.render_bdpt(bdpt_camera(case, f), frame=f, max_depth=D)
         for which in ("camera_vertices", "light_vertices", "camera_counts", "light_counts", "temp_radiance",
                       "visibility", "connection_rays"):
             res[f"{key}_{which}"] = cs.read_bdpt(which)
@@ -61,9 +75,11 @@ def bdpt_job(out_path, variant):
 
 def strip_bdpt_golden(src, dst):
     """Keeps the radiance frames and the vertex counts of a bdpt_job output (the committed
-    tests/golden/clref_bdpt_*.npz fixtures)."""
+    tests/golden/clref_bdpt_*.npz fixtures, BDPT_CASES only: the TAA case is compared live)."""
     z = np.load(src, allow_pickle=False)
+    taa = tuple(bdpt_key(c) + "_" for c in BDPT_TAA_CASES)
     keep = {k: z[k] for k in z.files if k.endswith("_counts") or k.rsplit("_", 1)[-1][1:].isdigit()}
+    keep = {k: v for k, v in keep.items() if not k.startswith(taa)}
     np.savez_compressed(dst, **keep)
 
 

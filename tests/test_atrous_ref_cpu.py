@@ -105,6 +105,12 @@ def test_moments_are_sequential_float32_sums_and_frame_zero_resets():
     l0 = ar.luminance(np.minimum(frames[0, ..., :3], F(1000)))
     np.testing.assert_array_equal(ar.accumulate_moments(frames[:1])[..., 0], l0)
     assert m.dtype == F
+    # a NaN radiance counts as 0 (the device's clamp returns its lower bound for NaN)
+    holed = frames.copy()
+    holed[2, 1, 1, :3] = np.nan
+    zeroed = frames.copy()
+    zeroed[2, 1, 1, :3] = 0
+    np.testing.assert_array_equal(ar.accumulate_moments(holed), ar.accumulate_moments(zeroed))
 
 
 def test_library_exports_guided_denoise():

@@ -10,7 +10,14 @@ the reference's s = 1 strategy reads the previous frame's sampled light vertex, 
   * the frame radiance: the reference sums each pixel's strategies with float atomics whose
     order depends on thread scheduling (light-tracing splats from other pixels interleave,
     BDPT.cl:888-907), so the image is compared with a relative tolerance of 4e-6 (a few ulp of
-    a sum of <= ~30 non-negative terms) and the bit-exact fraction is reported."""
+    a sum of <= ~30 non-negative terms) and the bit-exact fraction is reported.
+
+Non-finite radiance is part of what is compared (radiance_mismatch below, the one criterion of every
+radiance comparison in this file): frame 10 of the mixed scene at 96 x 64 holds one NaN pixel, (row 35,
+column 78), in the reference itself -- BDPT.cl:310 divides 0 by 0 for a light ray that leaves an area
+light at cos = 0 (tests/test_oracle_bdpt_cpu.py pins it on the CPU) -- and the frame ranges of the
+in-flight, batched, band-split and sparse-exchange tests cross that frame, so a path that loses, moves
+or spreads the NaN fails."""
 import os
 import subprocess
 import sys
@@ -18,7 +25,7 @@ import sys
 import numpy as np
 import pytest
 
-from clref_job import BDPT_CASES, bdpt_key, build_scene
+from clref_job import BDPT_CASES, BDPT_NAN_FRAME, BDPT_NAN_PIXEL, BDPT_TAA_CASES, bdpt_camera, bdpt_key, build_scene
 from mcrt import types as T
 from mcrt.camera import scene_camera
 from oracle import pyoracle as po
@@ -26,6 +33,49 @@ from oracle import pyoracle as po
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 REL_TOL = 4e-6
+REF_CASES = BDPT_CASES + BDPT_TAA_CASES
+
+
+def bit_equal(a, b):
+    """Element-wise: the same float32 bits, or NaN on both sides."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    return (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+
+
+def radiance_mismatch(a, b, exact=None):
+    """The criterion of every radiance comparison here; returns a list of messages, empty when
+      * the non-finite masks of a and b are equal element for element (a NaN or an infinity on one
+        side only is a mismatch; nothing non-finite is masked out);
+      * an element non-finite on both sides is the same on both (NaN with NaN, or the same infinity);
+      * finite elements are within REL_TOL * (|a| + |b|) + 1e-30;
+      * with `exact` (a boolean mask over a.shape[:-1], e.g. the pixels no splat landed on): those
+        pixels are bit-exact."""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    na, nb = ~np.isfinite(a), ~np.isfinite(b)
+    same = bit_equal(a, b)
+    bad = []
+    if not np.array_equal(na, nb):
+        d = np.argwhere(na != nb)
+        bad.append(f"non-finite on one side only at {len(d)} elements, first {d[:4].tolist()}")
+    with np.errstate(invalid="ignore"):
+        close = same | (~na & ~nb & (np.abs(a - b) <= REL_TOL * (np.abs(a) + np.abs(b)) + 1e-30))
+    if not close.all():
+        d = np.argwhere(~close)
+        bad.append(f"{len(d)} elements outside tolerance, first {d[:4].tolist()}")
+    if exact is not None and not same.all(-1)[exact].all():
+        bad.append(f"{int((~same.all(-1)[exact]).sum())} of {int(exact.sum())} pixels outside bit-exactness")
+    return bad
+
+
+def assert_radiance(a, b, label, exact=None):
+    bad = radiance_mismatch(a, b, exact)
+    assert not bad, (label, bad)
+
+
+def nonfinite_pixels(img):
+    """[(row, column)] of the pixels of an (H, W, C) image with a non-finite channel."""
+    return [(int(y), int(x)) for y, x in np.argwhere(~np.isfinite(np.asarray(img)).all(-1))]
 
 
 @pytest.fixture(scope="module")
@@ -86,39 +136,53 @@ def compare_vertices(ours, ref, counts, depths, N, label):
     return bad
 
 
-@pytest.mark.parametrize("case", BDPT_CASES, ids=[bdpt_key(c) for c in BDPT_CASES])
+@pytest.mark.parametrize("case", REF_CASES, ids=[bdpt_key(c) for c in REF_CASES])
 def test_bdpt_matches_reference(hip_ctx, clref_bdpt, case):
+    """Every frame's radiance against the reference run live (radiance_mismatch: equal non-finite
+    masks, no-splat pixels bit-exact), then the last frame's counts and vertices.
+
+    The TAA case (BDPT_TAA_CASES: mixed 96 x 64, D = 2, frames 0..11, each with its jittered camera) is
+    the one whose frames hold a non-finite pixel; which pixels are non-finite is what the reference
+    says here, not the oracle and not the product.  Recorded from the run on the MI355X (printed by
+    this test): the reference's frames 0..9 and 11 hold no non-finite pixel and its frame 10 holds
+    [(35, 78)], the pixel the oracle finds too; the product's lists are the same.  (Before
+    connectOne treated a NaN contribution as the reference does, the product's frame 10 held
+    [(1, 38), (59, 37)] instead: the NaN light subpath's two light-tracing splats, which the reference
+    drops, and 0 at (35, 78), where the reference adds the NaN own strategy.)"""
     from mcrt import lib
     name, W, H, frames, D = case
     key = bdpt_key(case)
     N = W * H
     ds = lib.DeviceScene(hip_ctx, build_scene(name))
     fb = lib.FrameBuffer(hip_ctx, W, H)
-    cam = scene_camera(name, W, H)
-    report = []
+    report, bad = [], []
+    nf_ref, nf_got = {}, {}
     for f in frames:
-        fb.render(ds, cam, frame=f, max_depth=D, sampler=T.SAMPLER_RANDOM, integrator=T.INTEGRATOR_BDPT)
+        fb.render(ds, bdpt_camera(case, f), frame=f, max_depth=D, sampler=T.SAMPLER_RANDOM,
+                  integrator=T.INTEGRATOR_BDPT)
         g = fb.read(0)[..., :3]
         ref = clref_bdpt[f"{key}_f{f}"][..., :3]
-        exact = (g.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(g) & np.isnan(ref))
-        close = np.abs(g - ref) <= REL_TOL * (np.abs(g) + np.abs(ref)) + 1e-30
-        close |= exact
         # pixels no light-tracing splat landed on: the reference's sum order is the own (t, s)
         # order there, so they must be bit-exact
         nosplat = (fb.read_bdpt("splat").view(np.float32).reshape(H, W, 4)[..., :3] == 0).all(-1)
-        ex_ns = exact.all(-1)[nosplat]
-        report.append(f"frame {f}: bit-exact {exact.mean():.5f} (no-splat pixels {ex_ns.mean():.5f} of "
-                      f"{int(nosplat.sum())}), within {REL_TOL:g} {close.mean():.5f}, mean {g.mean():.6f} vs {ref.mean():.6f}")
-        if not ex_ns.all():
-            report.append(f"frame {f}: {int((~ex_ns).sum())} no-splat pixels outside bit-exactness")
-        if not close.all():
-            report.append(f"frame {f}: {int((~close).sum())} pixels outside tolerance")
+        exact = bit_equal(g, ref)
+        nf_ref[f], nf_got[f] = nonfinite_pixels(ref), nonfinite_pixels(g)
+        report.append(f"frame {f}: bit-exact {exact.mean():.5f} (no-splat pixels {exact.all(-1)[nosplat].mean():.5f} of "
+                      f"{int(nosplat.sum())}), mean {np.nanmean(g):.6f} vs {np.nanmean(ref):.6f}, "
+                      f"non-finite {nf_got[f]} vs {nf_ref[f]}")
+        bad += [f"frame {f}: {m}" for m in radiance_mismatch(g, ref, exact=nosplat)]
+    if case in BDPT_TAA_CASES:
+        print(key, "reference non-finite pixels per frame:", nf_ref)
+        print(key, "product non-finite pixels per frame:", nf_got)
+        if not any(nf_ref.values()):   # the NaN-carrying tests below would be vacuous
+            bad.append("the reference's frames hold no non-finite pixel")
+        if nf_ref[BDPT_NAN_FRAME] != [BDPT_NAN_PIXEL]:
+            bad.append(f"the reference's frame {BDPT_NAN_FRAME} is non-finite at {nf_ref[BDPT_NAN_FRAME]}")
     # state of the last frame: counts and vertices
     cc = fb.read_bdpt("camera_counts").view(np.int32)
     lc = fb.read_bdpt("light_counts").view(np.int32)
     rcc = clref_bdpt[f"{key}_camera_counts"].view(np.int32)
     rlc = clref_bdpt[f"{key}_light_counts"].view(np.int32)
-    bad = [r for r in report if "outside" in r]
     if (cc != rcc).any():
         bad.append(f"camera counts differ at {int((cc != rcc).sum())} pixels")
     if (lc != rlc).any():
@@ -142,10 +206,13 @@ def test_bdpt_frames_in_flight(hip_ctx):
     mcrt_accumulate between the frames and one read-back at the end, against one slot:
       * the sampled-light planes after the last frame, both subpaths' vertex counts and the
         camera vertices: bit-exact (no atomics involved);
-      * the last radiance and the accumulated image: within the splat tolerance (light-tracing
-        splats are float atomics, so their order varies from run to run even with one slot)."""
+      * every frame's radiance (copied on the device into one buffer, mcrt_framebuffer_copy_device,
+        so the frames still overlap) and the accumulated image: within the splat tolerance
+        (light-tracing splats are float atomics, so their order varies from run to run even with
+        one slot), with equal non-finite masks: the 12 frames cross frame 10 and its NaN pixel."""
+    import torch
     from mcrt import lib
-    name, W, H, D, frames = "mixed", 96, 64, 2, 7
+    name, W, H, D, frames = "mixed", 96, 64, 2, 12
     ds = lib.DeviceScene(hip_ctx, build_scene(name))
     cam = scene_camera(name, W, H)
     filt = T.make_filter(T.BOX)
@@ -153,16 +220,22 @@ def test_bdpt_frames_in_flight(hip_ctx):
     for fif in (1, 2, 4):
         fb = lib.FrameBuffer(hip_ctx, W, H)
         fb.set_frames_in_flight(fif)
+        rads = torch.zeros((frames, H, W, 4), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
         for f in range(frames):
             fb.render(ds, cam, frame=f, max_depth=D, integrator=T.INTEGRATOR_BDPT)
+            fb.copy_device(0, rads[f].data_ptr())
             fb.accumulate(filt, f)
-        out[fif] = {"rad": fb.read(0), "img": fb.read(2), "wts": fb.read(1),
+        hip_ctx.sync()   # the one wait: the device copies ran on the context stream
+        out[fif] = {"rad": fb.read(0), "img": fb.read(2), "wts": fb.read(1), "rads": rads.cpu().numpy(),
                     **{k: fb.read_bdpt(k) for k in ("sampled_light", "camera_counts", "light_counts",
                                                     "camera_vertices")}}
         fb.close()
     ds.close()
     ref = out[1]
-    assert ref["img"][..., :3].max() > 0
+    assert ref["img"][..., :3].max() > 0 and np.isfinite(ref["img"]).all()
+    assert np.array_equal(ref["rads"][frames - 1], ref["rad"])
+    assert nonfinite_pixels(ref["rads"][BDPT_NAN_FRAME]) == [BDPT_NAN_PIXEL]
     N = W * H
     live = ref["camera_counts"].view(np.int32)[None, :] > np.arange(D + 2)[:, None]   # (depth, N)
     for fif in (2, 4):
@@ -174,10 +247,8 @@ def test_bdpt_frames_in_flight(hip_ctx):
         b = our_planes(ref["camera_vertices"], D + 2, N).view(np.uint32)[:, :8]
         ne = (a != b).any(-1).any(1)   # (depth, N)
         assert not (ne & live).any(), (fif, int((ne & live).sum()))
-        for k in ("rad", "img"):
-            a, b = o[k][..., :3], ref[k][..., :3]
-            close = np.abs(a - b) <= REL_TOL * (np.abs(a) + np.abs(b)) + 1e-30
-            assert close.all(), (fif, k, int((~close).sum()))
+        for k in ("rad", "img", "rads"):
+            assert_radiance(o[k][..., :3], ref[k][..., :3], (fif, k))
 
 
 @pytest.mark.parametrize("D", [2, 4])
@@ -211,8 +282,7 @@ def test_light_strategies_in_vertex_launch(hip_ctx, monkeypatch, D):
     sa, sb = a["splat"].view(np.float32), b["splat"].view(np.float32)
     assert (sb != 0).mean() > 0.01   # light-tracing splats landed
     for x, y, k in ((sa, sb, "splat"), (a["rad"][..., :3], b["rad"][..., :3], "rad")):
-        close = np.abs(x - y) <= REL_TOL * (np.abs(x) + np.abs(y)) + 1e-30
-        assert close.all(), (k, int((~close).sum()))
+        assert_radiance(x, y, k)
 
 
 @pytest.mark.parametrize("ranks", [2, 3])
@@ -222,15 +292,15 @@ def test_bdpt_band_split_matches_whole_frames(hip_ctx, ranks):
     are summed (mcrt.dist.exchange_splats' reduce-scatter, in rank order here) and every rank
     completes its bands with ITS chunk of the sum (mcrt_bdpt_gather); the accumulators are summed
     at the end.  Against whole frames in
-    one framebuffer, over 5 frames (the sampled-light state, BDPT.cl:585-586, persists on the
-    pixel's owner):
+    one framebuffer, over 11 frames (the sampled-light state, BDPT.cl:585-586, persists on the
+    pixel's owner; the last one is frame 10, whose pixel (35, 78) is NaN: rank 0 of 2, rank 1 of 3):
       * camera / light vertex counts and the sampled-light planes of every pixel: bit-exact;
       * each frame's radiance and the reduced accumulation: within the splat tolerance (sums of
-        the same splats in another order)."""
+        the same splats in another order), the radiance with equal non-finite masks."""
     import torch
     from mcrt import lib
     from mcrt import dist as mdist
-    name, W, H, D, frames = "mixed", 96, 64, 2, 5
+    name, W, H, D, frames = "mixed", 96, 64, 2, 11
     ds = lib.DeviceScene(hip_ctx, build_scene(name))
     cam = scene_camera(name, W, H)
     filt = T.make_filter(T.BOX)
@@ -267,10 +337,10 @@ def test_bdpt_band_split_matches_whole_frames(hip_ctx, ranks):
             fb.bdpt_gather(chunks[r].data_ptr())
             fb.accumulate(filt, f)
         ref = full.read(0)
+        if f == BDPT_NAN_FRAME:
+            assert nonfinite_pixels(ref) == [BDPT_NAN_PIXEL]
         for r, fb in enumerate(fbs):
-            a, b = fb.read(0)[rows[r], :, :3], ref[rows[r], :, :3]
-            close = np.abs(a - b) <= REL_TOL * (np.abs(a) + np.abs(b)) + 1e-30
-            assert close.all(), (ranks, f, r, int((~close).sum()))
+            assert_radiance(fb.read(0)[rows[r], :, :3], ref[rows[r], :, :3], (ranks, f, r))
         want = {k: full.read_bdpt(k) for k in ("camera_counts", "light_counts", "sampled_light")}
         for k, w in want.items():
             got = np.zeros_like(w)
@@ -301,7 +371,7 @@ def _frame_planes(raw, depths, frames, N):
     return f.reshape(depths, f.size // (depths * frames * N * 4), frames, N, 4)
 
 
-@pytest.mark.parametrize("calls", [(3, 4), (1, 2, 4)])
+@pytest.mark.parametrize("calls", [(3, 4), (1, 2, 4), (3, 4, 4)])   # (3, 4, 4): the NaN frame 10 at batch index 3
 def test_bdpt_batched_frames_match_single_calls(hip_ctx, calls):
     """mcrt_render_frames with the BDPT integrator (frame k of a call = path k*N + pixel in every
     plane; the s = 1 strategies walk the call's frames in order, BDPT.cl:585-586) against one
@@ -353,9 +423,9 @@ def test_bdpt_batched_frames_match_single_calls(hip_ctx, calls):
                                           err_msg=f"f{f0 + k} own-strategy slots")
             g, r = fb.read_frame(k)[..., :3], s["rad"][..., :3]
             nosplat = (splat[k][..., :3] == 0).all(-1) & (s["splat"].view(np.float32).reshape(H, W, 4)[..., :3] == 0).all(-1)
-            assert (g[nosplat].view(np.uint32) == r[nosplat].view(np.uint32)).all(), f0 + k
-            close = np.abs(g - r) <= REL_TOL * (np.abs(g) + np.abs(r)) + 1e-30
-            assert close.all(), (f0 + k, int((~close).sum()))
+            assert_radiance(g, r, f0 + k, exact=nosplat)
+            if f0 + k == BDPT_NAN_FRAME:   # (through the batched plane stride, k > 0 in the (3, 4, 4) split)
+                assert nonfinite_pixels(g) == [BDPT_NAN_PIXEL]
         np.testing.assert_array_equal(fb.read_bdpt("sampled_light"), single[f0 + B - 1]["sampled_light"],
                                       err_msg=f"sampled-light planes after frames {f0}..{f0 + B - 1}")
         f0 += B
@@ -402,9 +472,7 @@ def test_bdpt_batched_band_split(hip_ctx):
         torch.cuda.synchronize()
         fb.bdpt_gather(chunk.data_ptr())
         for k in range(B):
-            a, b = fb.read_frame(k)[rows[r], :, :3], ref[k][rows[r], :, :3]
-            close = np.abs(a - b) <= REL_TOL * (np.abs(a) + np.abs(b)) + 1e-30
-            assert close.all(), (r, k, int((~close).sum()))
+            assert_radiance(fb.read_frame(k)[rows[r], :, :3], ref[k][rows[r], :, :3], (r, k))
     for fb in fbs:
         fb.close()
     ds.close()
@@ -415,12 +483,13 @@ def test_bdpt_band_split_sparse_exchange(hip_ctx, ranks):
     """The sparse splat exchange (mcrt_framebuffer_set_splat_exchange, mcrt.dist.exchange_splats_sparse)
     emulated on one GPU: rank r lists the splats landing in other ranks' rows, the lists are routed
     to the rows' owners as an all-to-all would (here in Python), and every rank adds what it receives
-    (mcrt_bdpt_gather_sparse).  Every frame's radiance within the splat tolerance of whole frames;
+    (mcrt_bdpt_gather_sparse).  Every frame's radiance within the splat tolerance of whole frames, with
+    equal non-finite masks, over 11 frames (the last one is frame 10 with its NaN pixel);
     the records are few (the dense exchange moves every pixel), each lands in its receiver's rows."""
     import torch
     from mcrt import lib
     from mcrt import dist as mdist
-    name, W, H, D, frames = "mixed", 96, 64, 2, 4
+    name, W, H, D, frames = "mixed", 96, 64, 2, 11
     ds = lib.DeviceScene(hip_ctx, build_scene(name))
     cam = scene_camera(name, W, H)
     filt = T.make_filter(T.BOX)
@@ -463,10 +532,10 @@ def test_bdpt_band_split_sparse_exchange(hip_ctx, ranks):
             fb.bdpt_gather_sparse(recv.data_ptr(), len(mine))
             fb.accumulate(filt, f)
         ref = full.read(0)
+        if f == BDPT_NAN_FRAME:
+            assert nonfinite_pixels(ref) == [BDPT_NAN_PIXEL]
         for r, fb in enumerate(fbs):
-            a, b = fb.read(0)[rows[r], :, :3], ref[rows[r], :, :3]
-            close = np.abs(a - b) <= REL_TOL * (np.abs(a) + np.abs(b)) + 1e-30
-            assert close.all(), (ranks, f, r, int((~close).sum()))
+            assert_radiance(fb.read(0)[rows[r], :, :3], ref[rows[r], :, :3], (ranks, f, r))
     assert 0 < sent_total < frames * W * H   # few records against a dense exchange of every pixel
     for fb in fbs + [full]:
         fb.close()
@@ -478,9 +547,14 @@ def test_sparse_exchange_two_frames_in_flight(hip_ctx):
     (ADVICE r5): two band frame buffers (2 ranks emulated on one GPU) exchange their records through
     growable mcrt.dist.SparseSplatBuffers with device copies ordered on the frame streams, as the
     RCCL all-to-all runs (mcrt.dist.exchange_splats_sparse).  Each call's grouping must wait for the
-    other slot's call (mcrt_bdpt_splats_sparse), and a grown buffer must outlive its last use; the
-    accumulated images equal a run that synchronises the device after every step, within the splat
-    tolerance."""
+    other slot's call (mcrt_bdpt_splats_sparse), and a grown buffer must outlive its last use.
+
+    The radiance of every frame of every call (frames 0..11; copied on the device after the call's
+    gather, mcrt_framebuffer_copy_device_frame, and read back after the final wait), each rank on its
+    rows: the run without waits against a run that synchronises the device after every step, and
+    both against whole frames rendered in one frame buffer -- within the splat tolerance, with equal
+    non-finite masks; rank 0's frame 10 is NaN at (35, 78).  The accumulated images of both runs
+    likewise (they are finite: k_accumulate's clamp turns the NaN into 0)."""
     import torch
     from mcrt import lib
     from mcrt import dist as mdist
@@ -488,14 +562,23 @@ def test_sparse_exchange_two_frames_in_flight(hip_ctx):
     ds = lib.DeviceScene(hip_ctx, build_scene(name))
     filt = T.make_filter(T.BOX)
     rows = [mdist.band_rows_of(H, 8, ranks, r) for r in range(ranks)]
+    all_cams = [scene_camera(name, W, H, frame=f, jitter=True) for f in range(calls * B)]
+    full = lib.FrameBuffer(hip_ctx, W, H)
+    whole = []
+    for f, cam in enumerate(all_cams):
+        full.render(ds, cam, frame=f, max_depth=D, integrator=T.INTEGRATOR_BDPT)
+        whole.append(full.read(0))
+    full.close()
 
     def run(sync):
         fbs = [lib.FrameBuffer(hip_ctx, W, H) for _ in range(ranks)]
         bufs = [mdist.SparseSplatBuffers("cuda") for _ in range(ranks)]
+        rads = [torch.zeros((calls * B, H, W, 4), dtype=torch.float32, device="cuda") for _ in range(ranks)]
+        torch.cuda.synchronize()   # (before the first call: the buffers are zeroed on torch's stream)
         for fb in fbs:
             fb.set_splat_exchange(True)
         for c in range(calls):
-            cams = [scene_camera(name, W, H, frame=c * B + k, jitter=True) for k in range(B)]
+            cams = all_cams[c * B:(c + 1) * B]
             sends, counts, done = [], [], []
             for r, fb in enumerate(fbs):
                 fb.render_frames(ds, cams, frame=c * B, max_depth=D, integrator=T.INTEGRATOR_BDPT, band_rows=8,
@@ -529,25 +612,81 @@ def test_sparse_exchange_two_frames_in_flight(hip_ctx):
                 if sync:
                     torch.cuda.synchronize()
                 fb.bdpt_gather_sparse(recv.data_ptr(), total)
+                for k in range(B):   # device copies on the context stream, ordered after the gather
+                    fb.copy_device_frame(k, rads[q][c * B + k].data_ptr())
                 fb.accumulate_frames([filt] * B, c * B)
         hip_ctx.sync()
         torch.cuda.synchronize()
         out = [fb.read(2) for fb in fbs]   # the accumulated image of the 12 frames
         for fb in fbs:
             fb.close()
-        return out, sum(len(b.retired) for b in bufs)
+        return out, [t.cpu().numpy() for t in rads], sum(len(b.retired) for b in bufs)
 
-    a, retired = run(False)
-    b, _ = run(True)
-    assert retired > 0   # buffers grew while earlier calls could still use them
-    for r in range(ranks):
-        x, y = a[r][rows[r], :, :3], b[r][rows[r], :, :3]
-        fin = np.isfinite(x)
-        # (a BDPT pixel can be NaN in the reference too: the same pixels in both runs)
-        assert np.array_equal(fin, np.isfinite(y)) and fin.mean() > 0.99 and x[fin].max() > 0
-        close = np.abs(x[fin] - y[fin]) <= REL_TOL * (np.abs(x[fin]) + np.abs(y[fin])) + 1e-30
-        assert close.all(), (r, int((~close).sum()))
+    a, ra, retired = run(False)
+    b, rb, _ = run(True)
     ds.close()
+    assert retired > 0   # buffers grew while earlier calls could still use them
+    assert nonfinite_pixels(whole[BDPT_NAN_FRAME]) == [BDPT_NAN_PIXEL]
+    for r in range(ranks):
+        for f in range(calls * B):
+            x, y, w = (v[f][rows[r], :, :3] for v in (ra[r], rb[r], whole))
+            assert_radiance(x, y, ("unsynchronised vs synchronised", r, f))
+            assert_radiance(x, w, ("unsynchronised vs whole frames", r, f))
+            assert_radiance(y, w, ("synchronised vs whole frames", r, f))
+        x, y = a[r][rows[r], :, :3], b[r][rows[r], :, :3]
+        assert np.isfinite(x).all() and np.isfinite(y).all() and x.max() > 0
+        assert_radiance(x, y, ("accumulated image", r))
+    for rad in (ra, rb):   # row 35 is rank 0's
+        assert not np.isfinite(rad[0][BDPT_NAN_FRAME][BDPT_NAN_PIXEL][:3]).any()
+
+
+def test_bdpt_nonfinite_pixel_downstream(hip_ctx):
+    """What the NaN pixel of frame 10 becomes after the radiance: whole frames 0..11 accumulated with
+    the box filter (weight 1), luminance moments on.  reconstruction.cl:21 clamps the radiance to
+    [0, 1000] first; the device's clamp (v_med3_f32) and the oracle's fminf(fmaxf(x, 0), 1000) both
+    return 0 for NaN, as OpenCL's clamp = fmin(fmax(x, lo), hi) does.  So:
+      * the weighted sums and the weight sums equal the oracle's accumulate_w over the product's own
+        radiance frames bit for bit, the image within 3 ulp (as tests/test_gpu_accumulate.py);
+      * at (35, 78) frame 10 adds 0 to the sum and its weight to the weight sum;
+      * the image and the moments plane are finite everywhere, and the moments equal the numpy
+        restatement of k_moments (tests/atrous_ref.py) over the same frames bit for bit."""
+    import torch
+    import atrous_ref as ar
+    from mcrt import lib
+    name, W, H, D, frames = "mixed", 96, 64, 2, 12
+    y, x = BDPT_NAN_PIXEL
+    ds = lib.DeviceScene(hip_ctx, build_scene(name))
+    fb = lib.FrameBuffer(hip_ctx, W, H)
+    fb.enable_moments(True)
+    filt = T.make_filter(T.BOX)
+    wdev = torch.zeros(W * H, dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    rads, wsum, wts, img = [], None, None, None
+    for f in range(frames):
+        fb.render(ds, scene_camera(name, W, H, frame=f, jitter=True), frame=f, max_depth=D,
+                  integrator=T.INTEGRATOR_BDPT)
+        rads.append(fb.read(0))
+        fb.accumulate(filt, f)
+        before = None if wsum is None else (wsum[y, x].copy(), wts[y, x].copy())
+        wsum, wts, img = po.accumulate_w(rads[-1], f, 1.0, wsum, wts)
+        g_wsum = fb.read(1)
+        fb.copy_device(3, wdev.data_ptr())
+        hip_ctx.sync()
+        g_wts = wdev.cpu().numpy().reshape(H, W)
+        np.testing.assert_array_equal(g_wsum.view(np.uint32), wsum.view(np.uint32), err_msg=f"weighted sum, frame {f}")
+        np.testing.assert_array_equal(g_wts.view(np.uint32), wts.view(np.uint32), err_msg=f"weight sum, frame {f}")
+        if f == BDPT_NAN_FRAME:
+            assert np.isnan(rads[-1][y, x, :3]).all()
+            assert np.array_equal(g_wsum[y, x], before[0]) and g_wts[y, x] == before[1] + np.float32(1.0)
+    g_img = fb.read(2)
+    moments = fb.read_guides(T.GUIDE_MOMENTS)
+    fb.close()
+    ds.close()
+    assert np.isfinite(g_img).all() and np.isfinite(img).all() and g_img[..., :3].max() > 0
+    ulp = np.abs(g_img.view(np.int32).astype(np.int64) - img.view(np.int32).astype(np.int64))
+    assert ulp.max() <= 3, int(ulp.max())
+    assert np.isfinite(moments).all()
+    np.testing.assert_array_equal(moments.view(np.uint32), ar.accumulate_moments(rads).view(np.uint32))
 
 
 def _refused(call, status, text):
