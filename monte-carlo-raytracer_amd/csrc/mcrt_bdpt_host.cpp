@@ -217,7 +217,7 @@ mcrt_status mcrt::bdpt_render(mcrt_scene s, mcrt_framebuffer fb, const mcrt_came
     fb->haveBands = true;
     fb->lastIntegrator = MCRT_INTEGRATOR_BDPT;
     bd.batch = B;
-    mcrt_camera* dCam = slot.cameras();
+    mcrt_camera* dCam = slot.block.get()->cam;
     HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera) * B, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(bs.bdptCounters.get(), 0, 64 * sizeof(int), st));
     if (s->numLights == 0) {   // RTBDPTPass.cpp:69: no lights -> pass skipped

@@ -495,7 +495,7 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal_var(int 
 
 }  // namespace
 
-// called by mcrt_accumulate (mcrt_capi.cpp) while fb->dn.momentsOn
+// called by mcrt_accumulate (mcrt_pt_host.cpp) while fb->dn.momentsOn
 void mcrt::launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st) {
     const int blocks = (f.numTiles * 64 + 255) / 256;
     hipLaunchKernelGGL(k_moments, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, f, frame, radiance, moments);
@@ -541,26 +541,21 @@ static mcrt_status render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
     DenoiseState& d = fb->dn;
     HIPCHK(ctx, ensure_guides(fb));
     if (motion) HIPCHK(ctx, ensure_motion(fb));
-    FrameSlot& slot = cur_slot(fb);   // as mcrt_render_aov: its camera and primary-hit buffers are reused
-    if (!slot.counters) return fail(ctx, MCRT_ERROR_NOT_READY, kNoSlotBuffers);
-    mcrt::ctx_wait_slots(fb);
-    mcrt_camera* dCam = slot.cameras();
-    HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera), hipMemcpyHostToDevice, st));
-    if (!mcrt::ensure_spill(s, std::max((size_t)f.numTiles * 64, 2 * fb->N + 64)))
-        return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "traversal spill buffer");
-    const TraceCtx tcs = mcrt::packet_ctx(s);
-    mcrt::launch_primary(tcs, f, dCam, slot.hitsP.get(), st);
+    mcrt_camera* dCam = nullptr;   // as mcrt_render_aov: the current slot's camera and primary-hit buffers are reused
+    float4* hits = nullptr;
+    const mcrt_status borrowed = mcrt::borrow_camera_hits(s, fb, cam, f, &dCam, &hits);
+    if (borrowed != MCRT_OK) return borrowed;
     if (motion) {
         Timed t(ctx, K_GUIDES_MOTION, nullptr, (int64_t)f.numTiles * 64);
-        mcrt::launch_guides_motion(mcrt::scene_args(s), f, dCam, slot.hitsP.get(), d.guideNormal.get(), d.guideAlbedo.get(),
+        mcrt::launch_guides_motion(mcrt::scene_args(s), f, dCam, hits, d.guideNormal.get(), d.guideAlbedo.get(),
                                    s->dPrevPose.get(), d.motion.get(), d.motionNormal.get(), st);
     } else {
         Timed t(ctx, K_GUIDES, nullptr, (int64_t)f.numTiles * 64);
-        mcrt::launch_guides(mcrt::scene_args(s), f, dCam, slot.hitsP.get(), d.guideNormal.get(), d.guideAlbedo.get(), st);
+        mcrt::launch_guides(mcrt::scene_args(s), f, dCam, hits, d.guideNormal.get(), d.guideAlbedo.get(), st);
     }
     HIPCHK(ctx, hipGetLastError());
     // the slot's next render (its own stream) may overwrite those buffers only after this pass
-    HIPCHK(ctx, hipEventRecord(slot.free, st));
+    HIPCHK(ctx, mcrt::release_slot(fb, st));
     d.haveGuides = true;
     d.haveMotion = motion;
     return MCRT_OK;

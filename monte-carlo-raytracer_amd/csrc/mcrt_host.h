@@ -1,13 +1,16 @@
 // mcrt_host.h -- the host runtime's objects behind the opaque handles of include/mcrt_capi.h, and
-// the few helpers of mcrt_capi.cpp that host code in another file may call.  Not part of the ABI.
+// the few helpers that host code in another file may call.  Not part of the ABI.
 //
-// This is the boundary for host code outside mcrt_capi.cpp: a subsystem with entry points of its
-// own (mcrt_denoise.hip, mcrt_accel.cpp, mcrt_bdpt_host.cpp) includes it, reaches the runtime
-// through what is declared here and nothing else, and keeps its state in one struct held by the
-// frame buffer (DenoiseState, BdptState) or the scene (AccelState).  It compiles as plain
-// C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip translation unit.
+// This is the boundary between the host files.  mcrt_capi.cpp holds the context, the scene tables,
+// the ray queries and the frame buffer's own planes.  A subsystem with entry points of its own
+// (mcrt_denoise.hip, mcrt_accel.cpp, mcrt_bdpt_host.cpp, mcrt_pt_host.cpp) includes this header,
+// reaches the rest of the runtime through what is declared here and nothing else, and keeps its
+// state in one struct that only it names the fields of: DenoiseState, BdptState and the frame slots
+// (FrameSlot, mcrt_pt_host.cpp) held by the frame buffer, AccelState held by the scene.  It compiles
+// as plain C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip translation unit.
 #pragma once
 #include <climits>
+#include <cstddef>
 #include <string>
 #include <vector>
 
@@ -109,27 +112,49 @@ struct mcrt_scene_s {
     DevBuf<PrevPose> dPrevPose;
 };
 
-// One frame in flight (PT): the per-frame buffers of mcrt_render_frame, its own stream and
+// The small device block of a frame slot.  Its head, the per-bounce counters of a PT call, is what
+// the call zeroes and the read-backs copy; the batch's cameras (mcrt_render_frames) and filters
+// (mcrt_accumulate_frames) follow.  The kernels see these addresses, so the byte layout is pinned.
+struct SlotCounts {
+    int shadow[MCRT_MAX_BOUNCES];     // shadow rays queued by bounce b
+    int ext[MCRT_MAX_BOUNCES];        // extension rays queued by bounce b, traced for bounce b + 1
+    int hintHits[MCRT_MAX_BOUNCES];   // of shadow[b], answered by their occluder hint (profiling level 2)
+    int retraces[MCRT_MAX_BOUNCES];   // of ext[b], walks repeated on the exact records (profiling level 2)
+};
+struct SlotBlock {
+    SlotCounts n;
+    mcrt_camera cam[MCRT_MAX_BATCH_FRAMES];
+    mcrt_filter filt[MCRT_MAX_BATCH_FRAMES];
+    char slack[1536];
+};
+static_assert(MCRT_MAX_BOUNCES == 32 && sizeof(SlotCounts::shadow) == sizeof(int) * MCRT_MAX_BOUNCES, "one count per bounce");
+static_assert(offsetof(SlotCounts, shadow) == 0 && offsetof(SlotCounts, ext) == 128 && offsetof(SlotCounts, hintHits) == 256 &&
+                  offsetof(SlotCounts, retraces) == 384 && offsetof(SlotBlock, n) == 0,
+              "the four counter arrays");
+static_assert(offsetof(SlotBlock, cam) == 512 && sizeof(SlotCounts) == 512, "cameras from byte 512 (176 B each)");
+static_assert(offsetof(SlotBlock, filt) == 512 + 176 * MCRT_MAX_BATCH_FRAMES, "then the filters");
+static_assert(sizeof(SlotBlock) == 512 + 176 * MCRT_MAX_BATCH_FRAMES + sizeof(mcrt_filter) * MCRT_MAX_BATCH_FRAMES + 1536,
+              "the block's size");
+
+// One frame in flight: the per-frame buffers of mcrt_render_frame(s), its own stream and
 // spill columns.  Frame i renders in slot i mod S on that slot's stream while mcrt_accumulate
 // runs on the context stream in frame order (it waits for the slot's `done` event and records
 // `free` after reading the slot's radiance), so S frames overlap on the GPU -- each frame's
 // arithmetic and the per-pixel accumulation order are unchanged, so the image is the same bit
 // for bit.  Small per-rank frames (tile split over many GPUs) do not fill 256 CUs alone.
-#define SLOT_FILTER_OFFSET (512 + 176 * MCRT_MAX_BATCH_FRAMES)   // the batch's filters (mcrt_accumulate_frames)
-#define SLOT_COUNTER_BYTES (SLOT_FILTER_OFFSET + (int)sizeof(mcrt_filter) * MCRT_MAX_BATCH_FRAMES + 1536)
+// The slots are mcrt_pt_host.cpp's: it allocates and frees them, chooses one per call, and alone
+// names the queues, the block, the spill columns, the tile order, the suspended walks and -- apart
+// from ctx_wait_slots -- the events.  mcrt_capi.cpp reads radiance, lastBatch and stream;
+// mcrt_bdpt_host.cpp, handed a ready slot by the entry function, also writes radiance, the block's
+// cameras, lastMaxDepth and lastPixels and records `done` after a gather; everything else borrows
+// the current slot through borrow_camera_hits and release_slot below.
 struct FrameSlot {
     DevBuf<float4> radiance;
     DevBuf<float4> hitsP;        // primary hits (mcrt_kernels.hip hitSlot)
     DevBuf<float4> hitsE;        // extension hits by queue slot
     DevBuf<float4> eO[2], eD[2], eT[2];
     DevBuf<float4> sO, sD, sL;
-    // [0..31] shadow counts, [32..63] ext counts, [64..127] work counters, then the batch's cameras
-    // (176 B each) from byte 512 and its filters from SLOT_FILTER_OFFSET
-    DevBuf<int> counters;
-    mcrt_camera* cameras() const { return reinterpret_cast<mcrt_camera*>(counters.get() + 128); }
-    mcrt_filter* filters() const {
-        return reinterpret_cast<mcrt_filter*>(reinterpret_cast<char*>(counters.get()) + SLOT_FILTER_OFFSET);
-    }
+    DevBuf<SlotBlock> block;     // one: counters, cameras, filters
     DevBuf<uint32_t> spill;      // per-ray traversal spill columns of this slot's launches
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;   // recorded after the slot's last render
@@ -148,7 +173,6 @@ struct FrameSlot {
     DevBuf<float4> suspend;
     DevBuf<int> suspendCnt;
 };
-static_assert(SLOT_COUNTER_BYTES % sizeof(int) == 0, "the counter block is allocated as ints");
 
 // Per-frame BDPT arrays (RTBDPTPass::createBuffers, RTBDPTPass.cpp:442-479), one set per frame
 // slot so BDPT frames overlap like PT frames; layouts in mcrt_bdpt.hip.
@@ -261,7 +285,6 @@ struct mcrt_framebuffer_s {
 // The slot of the last rendered frame: what the read-back entry points show.  After a failed
 // regrow its buffers are empty, never stale.
 inline FrameSlot& cur_slot(mcrt_framebuffer fb) { return fb->slot[fb->cur]; }
-static const char* const kNoSlotBuffers = "the frame slot has no buffers (its last allocation failed)";
 
 // mcrt_capi.cpp's helpers that host code in other files may call
 namespace mcrt {
@@ -287,8 +310,23 @@ inline size_t tile_lanes(mcrt_framebuffer fb) { return (size_t)((fb->W + 7) / 8)
 // sizes `suspend` for `entries` queue entries, zeroes the `counts` suspend counters on st and fills
 // c.walkCap / walkLanes / suspend; otherwise c.walkCap stays 0.  Whether the rule is wanted at all,
 // and for which launches, is the caller's.
-hipError_t walk_rule(TraceCtx& c, int64_t paths, DevBuf<float4>& suspend, DevBuf<int>& suspendCnt, int counts,
+hipError_t walk_rule(TraceCtx& c, int64_t paths, DevBuf<float4>& suspend, DevBuf<int>& suspended, int counts,
                      size_t entries, hipStream_t st);
+// mcrt_pt_host.cpp: the frame slots and the path tracer
+// A slot's buffers, stream and events: planes for `frames` frames of N pixels (T: the lanes of the
+// frame's tiles) and ray queues of Q entries (at least N).  After a failure the slot is empty.
+hipError_t slot_alloc(FrameSlot& k, size_t N, size_t T, int frames = 1, size_t Q = 0);
+// the slots' streams, events and buffers; the frame buffer's own planes and its BDPT state go with it
+void fb_free(mcrt_framebuffer fb);
+// The current slot's camera record and primary-hit buffer, borrowed for a pass on the context
+// stream: waits for every slot's last render, uploads `cam`, sizes the scene's spill columns and
+// traces the camera rays of `f` (wave packets).  MCRT_ERROR_NOT_READY when the slot has no buffers.
+// The slot's next render may overwrite both, so a pass that leaves work on the stream ends with
+// release_slot.
+mcrt_status borrow_camera_hits(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam, const FrameArgs& f,
+                               mcrt_camera** dCam, float4** hits);
+// records on st that the current slot's buffers were read: the slot may take its next frame after it
+hipError_t release_slot(mcrt_framebuffer fb, hipStream_t st);
 // mcrt_bdpt_host.cpp: the bidirectional integrator
 // One BDPT call of f.batch frames in frame slot `slot` with set k, enqueued on the slot's stream
 // (the caller has made the slot ready and records its `done`).

@@ -54,6 +54,8 @@ struct FrameArgs {
 // its calls stay at 32 frames.
 #define MCRT_MAX_BATCH_FRAMES 256
 #define MCRT_MAX_BDPT_BATCH_FRAMES 32
+// Bounces of a PT call (max_depth): the per-bounce counters of a frame slot (SlotCounts, mcrt_host.h)
+#define MCRT_MAX_BOUNCES 32
 
 // A shape's previous pose (mcrt_scene_motion_snapshot): the matrices and mesh key its mcrt_shape
 // record began with when the snapshot was taken, 144 B

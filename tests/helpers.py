@@ -50,6 +50,15 @@ def random_rays(scene, n, seed, tmax=1000.0, inside=True):
     return rays
 
 
+def refused(call, status, text):
+    """`call` raises MCRTError with this status code and exactly this message."""
+    import pytest
+    from mcrt import lib
+    with pytest.raises(lib.MCRTError) as e:
+        call()
+    assert str(e.value) == f"mcrt status {status}: {text}", str(e.value)
+
+
 def closest_agreement(a, b, tol_dt2=1e-5):
     """RadeonRays conformance criterion (radeon_rays_conformance_test_cl.h:532-542):
     shapeid equal and (dt)^2 <= 1e-5 where hit.  Returns (fraction shapeid equal, max dt^2)."""

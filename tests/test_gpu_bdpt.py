@@ -26,6 +26,7 @@ import numpy as np
 import pytest
 
 from clref_job import BDPT_CASES, BDPT_NAN_FRAME, BDPT_NAN_PIXEL, BDPT_TAA_CASES, bdpt_camera, bdpt_key, build_scene
+from helpers import refused as _refused
 from mcrt import types as T
 from mcrt.camera import scene_camera
 from oracle import pyoracle as po
@@ -687,14 +688,6 @@ def test_bdpt_nonfinite_pixel_downstream(hip_ctx):
     assert ulp.max() <= 3, int(ulp.max())
     assert np.isfinite(moments).all()
     np.testing.assert_array_equal(moments.view(np.uint32), ar.accumulate_moments(rads).view(np.uint32))
-
-
-def _refused(call, status, text):
-    """`call` raises MCRTError with this status code and exactly this message."""
-    from mcrt import lib
-    with pytest.raises(lib.MCRTError) as e:
-        call()
-    assert str(e.value) == f"mcrt status {status}: {text}", str(e.value)
 
 
 def test_bdpt_call_order_refusals(hip_ctx):
