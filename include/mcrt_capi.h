@@ -742,6 +742,67 @@ MCRT_API mcrt_status mcrt_framebuffer_read_motion(mcrt_framebuffer fb, int which
                                                   uint64_t* needed);
 MCRT_API mcrt_status mcrt_temporal_accumulate_motion(mcrt_framebuffer fb, const mcrt_camera* camera,
                                                      const mcrt_temporal_params* params);
+
+/* ---- Adaptive sampling: render only the tiles above an error target (opt-in) --------------------
+ * Without these calls nothing else launches, allocates or changes.  In adaptive mode a path-tracing
+ * call renders, and the accumulate after it touches, only the tiles of an active list; every other
+ * pixel keeps its accumulators, image and moments.  A tile is 8x8 pixels (one wave); tile t is
+ * column-block t % ceil(W/8) of row-block t / ceil(W/8).  The loop of a host:
+ *   mcrt_framebuffer_set_adaptive(fb, &params);            -- mode on, moments on, reset
+ *   do { render + accumulate a round of frames (frame_index counts on from 0);
+ *        mcrt_adaptive_update(fb, &active); } while (active > 0);
+ * A tile holds n samples (its own count: tiles differ).  mcrt_adaptive_update judges every tile from
+ * the luminance moments (m1, m2) of its pixels, in float32 and in this order (IEEE division and
+ * square root, no contraction; tests/adaptive_ref.py restates it):
+ *   per pixel inside the image:  mean = m1 / n;  v = max(0, m2 / n - mean * mean) / (n - 1)
+ *   Sv = sum v, Sm = sum mean over the tile's 64 lanes (lane l = pixel (l & 7, l >> 3), 0 outside
+ *        the image), each by the butterfly s = s + s[lane ^ d], d = 32, 16, 8, 4, 2, 1
+ *   err = sqrt(Sv / c) / (Sm / c + luminance_floor),  c = the tile's pixels inside the image;
+ *         +inf while n < 2
+ *   active = n < min_samples ? 1 : (max_samples > 0 && n >= max_samples) ? 0 : err > error_threshold
+ * and rebuilds the list: the active tiles in ascending order.  It waits for the frame slots and the
+ * context stream -- the one host synchronisation per round -- and returns the list's length.
+ *
+ * mcrt_framebuffer_set_adaptive: non-NULL params turn the mode on, turn the moments on (allocating
+ *   the plane as mcrt_framebuffer_set_moments_enabled does) and reset; NULL turns the mode off and
+ *   frees its state (moments stay as they are).
+ * mcrt_adaptive_reset: zeroes the tile counts and the frame count, lists every tile and drops a
+ *   rendered frame that was not accumulated.  The host calls it when it restarts the accumulation.
+ * mcrt_framebuffer_set_active_tiles: installs a host list of n tile ids, strictly ascending and below
+ *   the tile count; n = 0 is legal.  This is region rendering; the next update replaces the list.
+ * mcrt_framebuffer_read_adaptive: which 0 the tile errors (float), 1 the tile sample counts
+ *   (uint32), one per tile; 2 the active list (uint32, its current length).  needed / host_dst /
+ *   bytes as mcrt_framebuffer_read_guides.
+ *
+ * In adaptive mode:
+ *  - mcrt_render_frame(s) launches over the list only; with an empty list it launches nothing.  The
+ *    radiance of an unlisted tile is NOT written: mcrt_framebuffer_read 0, mcrt_framebuffer_read_frame
+ *    and the device copies of the radiance are defined only on the tiles of the list the call
+ *    rendered with.  mcrt_framebuffer_stats counts the listed tiles' paths.
+ *  - mcrt_accumulate(_frames) needs a rendered frame; frame_index must equal the frames accumulated
+ *    since the reset, and frame_index 0 needs the full list (mcrt_adaptive_reset).  Per listed pixel
+ *    it runs the operations of the plain call in the same order; "first sample" is the tile's count
+ *    being 0.  Then every listed tile's count grows by the batch.
+ *  - mcrt_denoise_guided with use_variance takes n per pixel from its tile's count (n < 2: var = 1).
+ *  - mcrt_framebuffer_set_moments also sets every tile's count and the frame count to `frames`.
+ * MCRT_ERROR_INVALID_ARG, before anything changes: parameters out of range; a BDPT render (its
+ * light-tracing splats land in any tile); num_bands > 1; mcrt_temporal_accumulate(_motion); turning
+ * the moments off; a wrong frame_index; a list that is not strictly ascending or names a tile past
+ * the image; mcrt_adaptive_reset / _update / mcrt_framebuffer_set_active_tiles with the mode off.
+ * MCRT_ERROR_NOT_READY: mcrt_adaptive_update or mcrt_framebuffer_set_active_tiles with a rendered
+ * frame not yet accumulated; mcrt_accumulate without one. */
+typedef struct {
+    float   error_threshold;   /* a tile is done when its error <= this; >= 0 */
+    int32_t min_samples;       /* a tile is not judged before it has this many; >= 2 */
+    int32_t max_samples;       /* a tile stops at this many whatever its error; 0 = no cap, else >= min_samples */
+    float   luminance_floor;   /* added to the tile's mean luminance in the denominator; > 0, default 1e-3 */
+} mcrt_adaptive_params;
+MCRT_API mcrt_status mcrt_framebuffer_set_adaptive(mcrt_framebuffer fb, const mcrt_adaptive_params* params);
+MCRT_API mcrt_status mcrt_adaptive_reset(mcrt_framebuffer fb);
+MCRT_API mcrt_status mcrt_adaptive_update(mcrt_framebuffer fb, int32_t* active_tiles);
+MCRT_API mcrt_status mcrt_framebuffer_set_active_tiles(mcrt_framebuffer fb, const uint32_t* tiles, int32_t n);
+MCRT_API mcrt_status mcrt_framebuffer_read_adaptive(mcrt_framebuffer fb, int which, void* host_dst, uint64_t bytes,
+                                                    uint64_t* needed);
 /* Copies device -> host (RGBA32F, W*H*4 floats).  which: 0 radiance, 1 weighted sum, 2 image,
  * 3 display image (mcrt_postprocess, mcrt_denoise_guided). */
 MCRT_API mcrt_status mcrt_framebuffer_read(mcrt_framebuffer fb, int which, float* host_rgba);

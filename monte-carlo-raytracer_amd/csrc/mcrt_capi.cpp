@@ -45,7 +45,8 @@ const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN"
                                      "k_shadow_extend", "k_guides",      "k_moments",    "k_atrous_prep",
                                      "k_atrous_s1",   "k_atrous_s2",   "k_atrous_s4",  "k_atrous_s8",
                                      "k_atrous_s16",  "k_atrous_s32",  "k_atrous_s64", "k_atrous_s128",
-                                     "k_temporal",    "k_temporal_var", "k_guides_motion", "k_temporal_motion"};
+                                     "k_temporal",    "k_temporal_var", "k_guides_motion", "k_temporal_motion",
+                                     "k_tile_error",  "k_tile_list"};
 
 }  // namespace
 

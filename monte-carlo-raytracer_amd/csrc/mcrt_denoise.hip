@@ -30,12 +30,17 @@ __device__ __forceinline__ float lum3(float r, float g, float b) {
 //   l = lum3(clamp(radiance.rgb, 0, 1000));  m1 += l;  m2 += l * l;   frame 0 overwrites.
 // Unweighted on purpose: the reconstruction filter weight is one number per frame, and a variance
 // of the samples, not of the weighted estimate, is what the edge-stopping term wants.
+// LIST (adaptive sampling) as k_accumulate's: tile list[j], the tile's sample count for `frame`.
+template <bool LIST>
 __global__ __launch_bounds__(256) void k_moments(FrameArgs f, int frame, const float4* __restrict__ radiance,
-                                                 float2* __restrict__ moments) {
+                                                 float2* __restrict__ moments, const uint32_t* __restrict__ list,
+                                                 const uint32_t* __restrict__ tileCount) {
     const int lane = threadIdx.x & 63;
-    const int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (LIST) tile = (int)list[tile];
     int x, y;
     if (tile >= f.numTiles || !tilePixel(f, tile, lane, x, y)) return;
+    if (LIST) frame = (int)tileCount[tile];
     const int pix = y * (int)f.W + x;
     float m1 = 0.0f, m2 = 0.0f;
     if (frame != 0) {
@@ -82,6 +87,37 @@ __global__ __launch_bounds__(256) void k_atrous_prep(int n, const float4* __rest
         const float2 m = moments[i];
         const float mean = m.x / frames;
         v = fmaxf(0.0f, m.y / frames - mean * mean) / (frames - 1.0f);
+    }
+    cOut[i] = c;
+    vOut[i] = v;
+}
+
+// k_atrous_prep in adaptive mode: the same lines with n the sample count of the pixel's 8x8 tile
+// (tiles differ); n < 2 gives var = 1.  `moments` NULL: var = 1 everywhere.
+__global__ __launch_bounds__(256) void k_atrous_prep_tiles(int W, int H, const float4* __restrict__ image,
+                                                           const float4* __restrict__ albedoDepth,
+                                                           const float2* __restrict__ moments,
+                                                           const uint32_t* __restrict__ tileCount, int demod,
+                                                           float4* __restrict__ cOut, float* __restrict__ vOut) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= W * H) return;
+    float4 c = image[i];
+    if (demod) {
+        const float4 a = albedoDepth[i];
+        c.x = c.x / demodChannel(a.x);
+        c.y = c.y / demodChannel(a.y);
+        c.z = c.z / demodChannel(a.z);
+    }
+    float v = 1.0f;
+    if (moments) {
+        const int y = i / W, x = i - y * W;
+        const uint32_t cnt = tileCount[(y >> 3) * ((W + 7) >> 3) + (x >> 3)];
+        if (cnt >= 2u) {
+            const float frames = (float)cnt;
+            const float2 m = moments[i];
+            const float mean = m.x / frames;
+            v = fmaxf(0.0f, m.y / frames - mean * mean) / (frames - 1.0f);
+        }
     }
     cOut[i] = c;
     vOut[i] = v;
@@ -496,9 +532,16 @@ __global__ __launch_bounds__(ATROUS_TILE * ATROUS_TILE) void k_temporal_var(int 
 }  // namespace
 
 // called by mcrt_accumulate (mcrt_pt_host.cpp) while fb->dn.momentsOn
-void mcrt::launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st) {
+void mcrt::launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st,
+                          const uint32_t* list, int listLen, const uint32_t* tileCount) {
+    if (list) {
+        hipLaunchKernelGGL(k_moments<true>, dim3((listLen * 64 + 255) / 256), dim3(256), 0, st, f, frame, radiance, moments,
+                           list, tileCount);
+        return;
+    }
     const int blocks = (f.numTiles * 64 + 255) / 256;
-    hipLaunchKernelGGL(k_moments, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, f, frame, radiance, moments);
+    hipLaunchKernelGGL(k_moments<false>, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, f, frame, radiance, moments, list,
+                       tileCount);
 }
 
 // ---------------------------------------------------------------------------
@@ -607,6 +650,8 @@ static mcrt_status temporal_accumulate(mcrt_framebuffer fb, const mcrt_camera* c
     if (!fb || !cam || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
     mcrt_ctx ctx = fb->ctx;
     DenoiseState& d = fb->dn;
+    if (mcrt::adaptive_on(fb))   // the history integrates whole images of one sample count
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "mcrt_temporal_accumulate is not available in adaptive mode");
     if (!(p->alpha >= 0.0f && p->alpha <= 1.0f) || !(p->alpha_moments >= 0.0f && p->alpha_moments <= 1.0f))
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "alpha and alpha_moments must be in 0 .. 1");
     if (p->max_history < 1 || p->min_history < 1)
@@ -832,6 +877,8 @@ MCRT_API mcrt_status mcrt_framebuffer_set_moments_enabled(mcrt_framebuffer fb, i
     if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
     mcrt_ctx ctx = fb->ctx;
     DenoiseState& d = fb->dn;
+    if (!on && mcrt::adaptive_on(fb))
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "adaptive mode needs the moments (mcrt_framebuffer_set_adaptive(fb, NULL) first)");
     hipSetDevice(ctx->device);
     if (on && !d.moments) {
         HIPCHK(ctx, ensure_plane(fb, d.moments));
@@ -849,6 +896,7 @@ MCRT_API mcrt_status mcrt_framebuffer_set_moments(mcrt_framebuffer fb, const voi
     HIPCHK(ctx, ensure_plane(fb, d.moments));
     HIPCHK(ctx, hipMemcpyAsync(d.moments.get(), d_m1m2, 8 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
     d.momentFrames = frames;
+    HIPCHK(ctx, mcrt::adaptive_set_counts(fb, frames));   // adaptive mode: every tile holds `frames` samples
     return MCRT_OK;
 }
 
@@ -869,9 +917,17 @@ MCRT_API mcrt_status mcrt_denoise_guided(mcrt_framebuffer fb, const mcrt_guided_
         mcrt_ctx ctx = fb->ctx;
         DenoiseState& d = fb->dn;
         HIPCHK(ctx, ensure_atrous(fb));   // k_atrous_prep writes level 0's input to the first scratch planes
-        const bool useVar = p->use_variance && d.moments && d.momentFrames >= 2;
         const int n = (int)fb->N;
         Timed t(ctx, K_ATROUS_PREP, nullptr, (int64_t)fb->N);
+        const bool useVar = p->use_variance && d.moments && d.momentFrames >= 2;
+        if (mcrt::adaptive_on(fb)) {   // n per pixel from its tile's count
+            hipLaunchKernelGGL(k_atrous_prep_tiles, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (int)fb->W, (int)fb->H,
+                               fb->image.get(), d.guideAlbedo.get(), useVar ? d.moments.get() : nullptr,
+                               mcrt::adaptive_counts(fb), p->demodulate_albedo ? 1 : 0, d.atrousC[0].get(),
+                               d.atrousV[0].get());
+            in = {d.atrousC[0].get(), d.atrousV[0].get(), useVar ? 1 : 0};
+            return MCRT_OK;
+        }
         hipLaunchKernelGGL(k_atrous_prep, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, n, fb->image.get(),
                            d.guideAlbedo.get(), useVar ? d.moments.get() : nullptr, (float)d.momentFrames,
                            p->demodulate_albedo ? 1 : 0, d.atrousC[0].get(), d.atrousV[0].get());

@@ -3,10 +3,11 @@
 //
 // This is the boundary between the host files.  mcrt_capi.cpp holds the context, the scene tables,
 // the ray queries and the frame buffer's own planes.  A subsystem with entry points of its own
-// (mcrt_denoise.hip, mcrt_accel.cpp, mcrt_bdpt_host.cpp, mcrt_pt_host.cpp) includes this header,
-// reaches the rest of the runtime through what is declared here and nothing else, and keeps its
-// state in one struct that only it names the fields of: DenoiseState, BdptState and the frame slots
-// (FrameSlot, mcrt_pt_host.cpp) held by the frame buffer, AccelState held by the scene.  It compiles
+// (mcrt_denoise.hip, mcrt_adaptive.hip, mcrt_accel.cpp, mcrt_bdpt_host.cpp, mcrt_pt_host.cpp)
+// includes this header, reaches the rest of the runtime through what is declared here and nothing
+// else, and keeps its state in one struct that only it names the fields of: DenoiseState,
+// AdaptiveState, BdptState and the frame slots (FrameSlot, mcrt_pt_host.cpp) held by the frame
+// buffer, AccelState held by the scene.  It compiles
 // as plain C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip translation unit.
 #pragma once
 #include <climits>
@@ -27,6 +28,7 @@ enum KernelId {
     K_GUIDES, K_MOMENTS, K_ATROUS_PREP,
     K_ATROUS,   // one entry per level: K_ATROUS + i is the launch of step 2^i
     K_TEMPORAL = K_ATROUS + MCRT_ATROUS_MAX_LEVELS, K_TEMPORAL_VAR, K_GUIDES_MOTION, K_TEMPORAL_MOTION,
+    K_TILE_ERROR, K_TILE_LIST,
     K_COUNT
 };
 
@@ -260,6 +262,25 @@ struct DenoiseState {
     bool haveMotion = false;
 };
 
+// Adaptive sampling (mcrt_adaptive.hip): the tiles a PT call renders and an accumulate touches.  A
+// tile is 8x8 pixels, tile t = row-block (t / tilesX), column-block (t % tilesX) of the whole image
+// (tilePixel's numbering without a band split).  Only mcrt_adaptive.hip names the fields; the path
+// tracer and the denoiser go through the adaptive_* functions declared below.
+struct AdaptiveState {
+    bool on = false;
+    mcrt_adaptive_params p = {};
+    int numTiles = 0;
+    DevBuf<uint32_t> tileCount;   // samples accumulated per tile
+    DevBuf<float> tileErr;        // k_tile_error's result per tile (+inf below 2 samples)
+    // the active tiles, ascending; entries from listLen to the buffer's end hold numTiles, so a launch
+    // rounded up to whole workgroups (k_shade0: 8 waves) finds no real tile in its surplus waves
+    DevBuf<uint32_t> list;        // numTiles rounded up to 8, and 8 more
+    DevBuf<int> listLenDev;       // k_tile_list's count, read back by mcrt_adaptive_update
+    int listLen = 0;
+    int frames = 0;               // frames accumulated since the last reset
+    int pending = 0;              // frames rendered and not yet accumulated
+};
+
 struct mcrt_framebuffer_s {
     mcrt_ctx ctx = nullptr;
     uint32_t W = 0, H = 0;
@@ -281,6 +302,7 @@ struct mcrt_framebuffer_s {
     int lastIntegrator = MCRT_INTEGRATOR_PT;
     BdptState bd;
     DenoiseState dn;
+    AdaptiveState ad;
 };
 // The slot of the last rendered frame: what the read-back entry points show.  After a failed
 // regrow its buffers are empty, never stale.
@@ -340,6 +362,19 @@ int bdpt_sets(mcrt_framebuffer fb, int slots);   // sets BDPT frames rotate over
 bool bdpt_pending_gather(mcrt_framebuffer fb);   // a band-split frame waits for mcrt_bdpt_gather(_sparse)
 // rays of the last BDPT call (max depth `depth`), read from its set: all subpath rays, connection rays
 hipError_t bdpt_ray_counts(mcrt_framebuffer fb, int depth, int64_t* closest, int64_t* any);
+// mcrt_adaptive.hip: adaptive sampling, as the path tracer and the denoiser see it
+inline bool adaptive_on(mcrt_framebuffer fb) { return fb->ad.on; }
+// the active-tile table of the next PT call (padded, see AdaptiveState::list) and its length
+const uint32_t* adaptive_list(mcrt_framebuffer fb, int* len);
+const uint32_t* adaptive_counts(mcrt_framebuffer fb);   // samples per tile
+void adaptive_rendered(mcrt_framebuffer fb, int batch);   // a PT call of `batch` frames was enqueued over the list
+// mcrt_accumulate's checks in adaptive mode, before anything is enqueued: a rendered frame is
+// waiting, frame_index is the frame count since the reset, and frame 0 covers every tile
+mcrt_status adaptive_check_accumulate(mcrt_framebuffer fb, int32_t frame_index);
+// after k_accumulate and k_moments over the list: `batch` more samples in each listed tile (on st)
+void adaptive_accumulated(mcrt_framebuffer fb, int batch, hipStream_t st);
+// mcrt_framebuffer_set_moments: every tile holds `frames` samples (on the context stream)
+hipError_t adaptive_set_counts(mcrt_framebuffer fb, int frames);
 // mcrt_accel.cpp: the views of the scene's acceleration structure and the little else of it that
 // the rest of the runtime reads
 bool accel_ready(mcrt_scene s);            // mcrt_accel_build has made a structure

@@ -166,7 +166,10 @@ void launch_trace_rays(bool any, const TraceCtx& c, const mcrt_ray* rays, int n,
 void launch_surface_records(const uint32_t* meshStartIdx, const uint32_t* meshStartVertex, const uint32_t* meshBase,
                             int numMeshes, uint32_t numRecords, const uint32_t* indices, const float4* positions,
                             const float2* uvs, const float4* normals, float4* surf, hipStream_t st);
-void launch_primary(const TraceCtx& c, const FrameArgs& f, const mcrt_camera* cam, float4* hits, hipStream_t st);
+// tileSlots >= 0: the wave-packet launch covers that many tile slots of f.tileOrder instead of all
+// f.numTiles (adaptive sampling); the per-ray camera kernels take no table and cover every tile
+void launch_primary(const TraceCtx& c, const FrameArgs& f, const mcrt_camera* cam, float4* hits, hipStream_t st,
+                    int tileSlots = -1);
 // closest hit over two queues in one launch: queue 0 over cc's records, queue 1 over c's
 // the light-start queue of a BDPT call sorted by cell (keys, slots from k_bdpt_start) -> perm
 size_t bdpt_light_sort_temp_bytes(int n);
@@ -185,8 +188,9 @@ void launch_shadow_extend(const TraceCtx& c, const int* extCount, const float4* 
 // the walks k_shadow_extend suspended (c.walkCap > 0): at most maxExt of them
 void launch_walk_resume(const TraceCtx& c, const float4* qO, const float4* qD, float4* hits, int maxExt,
                         hipStream_t st);
+// tileSlots as launch_primary's
 void launch_shade0(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
-                   float4* radiance, const QueueArgs& q, hipStream_t st);
+                   float4* radiance, const QueueArgs& q, hipStream_t st, int tileSlots = -1);
 void launch_shadeN(const SceneArgs& s, const FrameArgs& f, int bounce, const int* countIn, const float4* qO,
                    const float4* qD, const float4* qT, const float4* hits, float4* radiance, const QueueArgs& q,
                    int maxCount, hipStream_t st);
@@ -203,11 +207,15 @@ void launch_guides_motion(const SceneArgs& s, const FrameArgs& f, const mcrt_cam
                           float4* normalPlane, float4* albedoDepth, const PrevPose* prev, float4* motion,
                           float4* prevNormal, hipStream_t st);
 // mcrt_denoise.hip: the luminance moments (sum l, sum l*l) of the frames k_accumulate just added
-void launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st);
+// list (adaptive sampling, listLen > 0 padded entries): only its tiles, a tile's count as its frame
+void launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st,
+                    const uint32_t* list = nullptr, int listLen = 0, const uint32_t* tileCount = nullptr);
 // filters: the reconstruction filter of each batch frame in device memory (KRN/kernel_data.h:63-80), k_accumulate
 // evaluates its weight like ReconstructionPass (reconstruction.cl:21-42); filterStride 0 = one filter for all frames
+// list, listLen, tileCount as launch_moments'
 void launch_accumulate(const FrameArgs& f, int frame, const mcrt_filter* filters, int filterStride, const float4* radiance, float4* wsum, float* wts,
-                       float4* image, hipStream_t st);
+                       float4* image, hipStream_t st, const uint32_t* list = nullptr, int listLen = 0,
+                       const uint32_t* tileCount = nullptr);
 void launch_resolve(uint32_t W, uint32_t H, const float4* wsum, const float* wts, float4* image, hipStream_t st);
 void launch_band_pack(const FrameArgs& f, const float4* wsum, const float* wts, float* out, hipStream_t st);
 void launch_band_unpack(const FrameArgs& f, int maxRows, const float* recv, float4* wsum, float* wts, float4* image,

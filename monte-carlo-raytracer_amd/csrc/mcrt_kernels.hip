@@ -890,13 +890,20 @@ MCRT_DEV float filterWeight(const mcrt_filter& fp) {
 
 // A batch of f.batch frames (mcrt_render_frames) is accumulated in frame order, frame + k with
 // filter filters[k * fstride]: per pixel the same operations as f.batch single-frame launches.
+// LIST (adaptive sampling): wave j takes tile list[j] (padded with numTiles past the list's end) and
+// the tile's sample count stands for `frame`, so "first sample" is the count being 0; the pixels of
+// other tiles are not touched.
+template <bool LIST>
 __global__ __launch_bounds__(256) void k_accumulate(FrameArgs f, int frame, const mcrt_filter* __restrict__ filters, int fstride,
                                                     const float4* __restrict__ radiance, float4* __restrict__ wsum,
-                                                    float* __restrict__ wts, float4* __restrict__ image) {
+                                                    float* __restrict__ wts, float4* __restrict__ image,
+                                                    const uint32_t* __restrict__ list, const uint32_t* __restrict__ tileCount) {
     const int lane = threadIdx.x & 63;
-    const int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    if (LIST) tile = (int)list[tile];
     int x, y;
     if (tile >= f.numTiles || !tilePixel(f, tile, lane, x, y)) return;
+    if (LIST) frame = (int)tileCount[tile];
     const int pix = y * (int)f.W + x;
     f4 s;
     float ws;
@@ -1297,9 +1304,12 @@ void launch_surface_records(const uint32_t* meshStartIdx, const uint32_t* meshSt
                                                                 numRecords, indices, positions, uvs, normals, surf);
 }
 
-void launch_primary(const TraceCtx& c, const FrameArgs& f, const mcrt_camera* cam, float4* hits, hipStream_t st) {
+void launch_primary(const TraceCtx& c, const FrameArgs& f, const mcrt_camera* cam, float4* hits, hipStream_t st,
+                    int tileSlots) {
     if (c.packet && !c.twoLevel) {
-        hipLaunchKernelGGL(k_primary_pk, dim3(f.numTiles * f.batch), dim3(64), 0, st, c, f, cam, hits);
+        // only this kernel takes its tile from f.tileOrder, so only it can run over a shorter table
+        const int slots = tileSlots >= 0 ? tileSlots : f.numTiles;
+        hipLaunchKernelGGL(k_primary_pk, dim3(slots * f.batch), dim3(64), 0, st, c, f, cam, hits);
         return;
     }
     hipLaunchKernelGGL(pickLayout(c, k_primary<LAY_TWO_LEVEL>, k_primary<LAY_PLAIN>), dim3(f.numTiles * f.batch), dim3(64), 0, st, c, f, cam,
@@ -1346,8 +1356,8 @@ void launch_walk_resume(const TraceCtx& c, const float4* qO, const float4* qD, f
     hipLaunchKernelGGL(k_walk_resume, dim3(blocks), dim3(64), 0, st, c, qO, qD, hits);
 }
 void launch_shade0(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
-                   float4* radiance, const QueueArgs& q, hipStream_t st) {
-    const int blocks = (f.numTiles * f.batch * 64 + SHADE0_BLOCK - 1) / SHADE0_BLOCK;
+                   float4* radiance, const QueueArgs& q, hipStream_t st, int tileSlots) {
+    const int blocks = ((tileSlots >= 0 ? tileSlots : f.numTiles) * f.batch * 64 + SHADE0_BLOCK - 1) / SHADE0_BLOCK;
     auto k = f.russianRoulette ? (f.textureLod ? k_shade0<true, true> : k_shade0<false, true>)
                                : (f.textureLod ? k_shade0<true, false> : k_shade0<false, false>);
     hipLaunchKernelGGL(k, dim3(blocks), dim3(SHADE0_BLOCK), 0, st, s, f, cam, hits, radiance, q);
@@ -1385,10 +1395,16 @@ void launch_pose_snapshot(const mcrt_shape* shapes, PrevPose* out, int n, hipStr
     hipLaunchKernelGGL(k_pose_snapshot, dim3((words + 255) / 256), dim3(256), 0, st, shapes, out, n);
 }
 void launch_accumulate(const FrameArgs& f, int frame, const mcrt_filter* filters, int filterStride, const float4* radiance,
-                       float4* wsum, float* wts, float4* image, hipStream_t st) {
+                       float4* wsum, float* wts, float4* image, hipStream_t st, const uint32_t* list, int listLen,
+                       const uint32_t* tileCount) {
+    if (list) {   // listLen > 0: whole workgroups of 4 waves, the surplus ones find numTiles in the table
+        hipLaunchKernelGGL(k_accumulate<true>, dim3((listLen * 64 + 255) / 256), dim3(256), 0, st, f, frame, filters,
+                           filterStride, radiance, wsum, wts, image, list, tileCount);
+        return;
+    }
     const int blocks = (f.numTiles * 64 + 255) / 256;
-    hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(256), 0, st, f, frame, filters, filterStride, radiance, wsum,
-                       wts, image);
+    hipLaunchKernelGGL(k_accumulate<false>, dim3(blocks), dim3(256), 0, st, f, frame, filters, filterStride, radiance, wsum,
+                       wts, image, list, tileCount);
 }
 
 void launch_denoise(int W, int H, int r, float ss, float sr, const float4* in, float4* out, hipStream_t st) {

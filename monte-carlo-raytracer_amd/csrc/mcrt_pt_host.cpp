@@ -89,8 +89,16 @@ mcrt_status pt_render(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
                       FrameArgs f, FrameSlot& slot) {
     mcrt_ctx ctx = s->ctx;
     const int count = f.batch;
-    const int bandPaths = f.numTiles * 64 * count;
+    // Adaptive sampling: the camera and first-shading launches cover the K tiles of the active list
+    // (slot j takes tile list[j] through f.tileOrder, the table padded with numTiles so that a
+    // surplus wave is invalid), and everything sized by the call's paths is sized by K.  The buffers
+    // keep the whole image's capacity.
+    const bool listed = mcrt::adaptive_on(fb);
+    int tileSlots = f.numTiles;
+    const uint32_t* const list = listed ? mcrt::adaptive_list(fb, &tileSlots) : nullptr;
+    const int bandPaths = tileSlots * 64 * count;
     hipStream_t st = slot.stream;
+    if (listed) mcrt::adaptive_rendered(fb, count);
     slot.lastMaxDepth = p->max_depth;
     slot.lastPixels = 0;
     fb->bands = f;
@@ -111,13 +119,20 @@ mcrt_status pt_render(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
         HIPCHK(ctx, hipEventRecord(slot.done, st));
         return MCRT_OK;
     }
+    if (tileSlots == 0) {   // an empty list: no launch at all (never a zero-sized grid)
+        HIPCHK(ctx, hipEventRecord(slot.done, st));
+        return MCRT_OK;
+    }
     TraceCtx tcs = trace_ctx(s);
     tcs.spill = slot.spill.get();
     const int qCap = bandPaths;
     TraceCtx tw = tcs;   // the extension walks' stop rule, when it applies: one suspend count per bounce
     if (p->max_depth > 1)
         HIPCHK(ctx, mcrt::walk_rule(tw, bandPaths, slot.suspend, slot.suspendCnt, MCRT_MAX_BOUNCES, (size_t)qCap, st));
-    if (longest_first()) {
+    if (listed) {
+        // the list takes the place of the longest-first order; no costs are recorded
+        f.tileOrder = list;
+    } else if (longest_first()) {
         // the camera / first-shading tiles in descending cost of this slot's previous call (same
         // tiles), and this call's costs recorded for the next one -- all on the slot's stream
         if (slot.tileOrder.size() < (size_t)f.numTiles) {   // (the one allocated last)
@@ -138,7 +153,15 @@ mcrt_status pt_render(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
         TraceCtx tcp = packet_ctx(s);   // coherent camera rays: wave packets
         tcp.spill = slot.spill.get();
         tcp.waveClock = wave_clock_buf(fb, 0, (size_t)f.numTiles * count, st);
-        mcrt::launch_primary(tcp, f, dCam, hitsP, st);
+        if (listed && !(tcp.packet && !tcp.twoLevel)) {
+            // the per-ray camera kernels take no tile table: every tile's camera ray, the hits of
+            // the unlisted ones unused
+            FrameArgs fc = f;
+            fc.tileOrder = nullptr;
+            mcrt::launch_primary(tcp, fc, dCam, hitsP, st);
+        } else {
+            mcrt::launch_primary(tcp, f, dCam, hitsP, st, listed ? tileSlots : -1);
+        }
     }
     // a shadow launch's view for bounce b: this slot's spill columns, the occluder hints (bounce 0: by
     // pixel) and, at profiling level 2, their counter
@@ -161,8 +184,8 @@ mcrt_status pt_render(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
             // trims the extension launch's tail, on a whole 1080p image it costs the shading's
             // spatial locality (+2.8 % k_shade0, +1.2 % k_shadow_extend; profiles/r05/ab/longest_first)
             FrameArgs fs = f;
-            if ((int64_t)bandPaths > MCRT_LPT_SHADE_MAX_PATHS) fs.tileOrder = nullptr;
-            mcrt::launch_shade0(sa, fs, dCam, hitsP, radiance, q, st);
+            if (!listed && (int64_t)bandPaths > MCRT_LPT_SHADE_MAX_PATHS) fs.tileOrder = nullptr;
+            mcrt::launch_shade0(sa, fs, dCam, hitsP, radiance, q, st, listed ? tileSlots : -1);
         } else {
             Timed t(ctx, K_SHADEN, extCnt + b - 1, 0, st);
             mcrt::launch_shadeN(sa, f, b, extCnt + b - 1, slot.eO[(b - 1) & 1].get(), slot.eD[(b - 1) & 1].get(),
@@ -225,6 +248,11 @@ mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* 
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "Sobol sampler requires the 1024x52 Sobol matrices in the scene");
     if (p->integrator != MCRT_INTEGRATOR_PT && p->integrator != MCRT_INTEGRATOR_BDPT)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "unknown integrator");
+    if (mcrt::adaptive_on(fb)) {
+        if (p->integrator == MCRT_INTEGRATOR_BDPT)   // its light-tracing splats land in any tile
+            return fail(ctx, MCRT_ERROR_INVALID_ARG, "adaptive mode renders with the path tracer only (no BDPT)");
+        if (p->num_bands > 1) return fail(ctx, MCRT_ERROR_INVALID_ARG, "adaptive mode takes no band split (num_bands > 1)");
+    }
     if (mcrt::bdpt_pending_gather(fb))
         return fail(ctx, MCRT_ERROR_NOT_READY, "band-split BDPT frame not completed (mcrt_bdpt_gather)");
     FrameArgs f;
@@ -285,6 +313,16 @@ mcrt_status accumulate(mcrt_framebuffer fb, const mcrt_filter* filters, int nfil
     if (nfilters != 1 && nfilters != batch)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "one filter, or one per frame of the last mcrt_render_frames");
     if (!slot.block) return fail(ctx, MCRT_ERROR_NOT_READY, kNoSlotBuffers);
+    // adaptive sampling: only the tiles of the list the call rendered with, each at its own count
+    const bool listed = mcrt::adaptive_on(fb);
+    int tiles = fb->bands.numTiles;
+    const uint32_t *list = nullptr, *tileCount = nullptr;
+    if (listed) {
+        const mcrt_status ok = mcrt::adaptive_check_accumulate(fb, frame_index);
+        if (ok != MCRT_OK) return ok;
+        list = mcrt::adaptive_list(fb, &tiles);
+        tileCount = mcrt::adaptive_counts(fb);
+    }
     FrameArgs f = fb->bands;
     f.batch = batch;
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, slot.done, 0));   // the frame's render (its slot stream)
@@ -292,16 +330,19 @@ mcrt_status accumulate(mcrt_framebuffer fb, const mcrt_filter* filters, int nfil
     // block, which its next render (after slot.free below) does not touch before this launch
     mcrt_filter* dFilt = slot.block.get()->filt;
     HIPCHK(ctx, hipMemcpyAsync(dFilt, filters, sizeof(mcrt_filter) * nfilters, hipMemcpyHostToDevice, ctx->stream));
-    {
-        Timed t(ctx, K_ACCUM, nullptr, (int64_t)f.numTiles * 64 * batch);
+    if (tiles > 0) {   // (an empty list: nothing to add)
+        Timed t(ctx, K_ACCUM, nullptr, (int64_t)tiles * 64 * batch);
         mcrt::launch_accumulate(f, frame_index, dFilt, nfilters == 1 ? 0 : 1, slot.radiance.get(), fb->wsum.get(), fb->wts.get(),
-                                fb->image.get(), ctx->stream);
+                                fb->image.get(), ctx->stream, list, tiles, tileCount);
     }
     if (fb->dn.momentsOn) {   // the same frames' luminance moments, before the slot is released
-        Timed t(ctx, K_MOMENTS, nullptr, (int64_t)f.numTiles * 64 * batch);
-        mcrt::launch_moments(f, frame_index, slot.radiance.get(), fb->dn.moments.get(), ctx->stream);
+        if (tiles > 0) {
+            Timed t(ctx, K_MOMENTS, nullptr, (int64_t)tiles * 64 * batch);
+            mcrt::launch_moments(f, frame_index, slot.radiance.get(), fb->dn.moments.get(), ctx->stream, list, tiles, tileCount);
+        }
         fb->dn.momentFrames = frame_index == 0 ? batch : fb->dn.momentFrames + batch;
     }
+    if (listed) mcrt::adaptive_accumulated(fb, batch, ctx->stream);   // after both: they read the counts
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipEventRecord(slot.free, ctx->stream));   // the slot may take its next frame
     return MCRT_OK;

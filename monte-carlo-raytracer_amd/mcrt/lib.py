@@ -112,6 +112,11 @@ SIGNATURES = {
     "mcrt_framebuffer_set_motion": (_c.c_int, [_vp, _vp, _vp]),
     "mcrt_framebuffer_read_motion": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     "mcrt_temporal_accumulate_motion": (_c.c_int, [_vp, _vp, _c.POINTER(T.TemporalParams)]),
+    "mcrt_framebuffer_set_adaptive": (_c.c_int, [_vp, _c.POINTER(T.AdaptiveParams)]),
+    "mcrt_adaptive_reset": (_c.c_int, [_vp]),
+    "mcrt_adaptive_update": (_c.c_int, [_vp, _c.POINTER(_c.c_int32)]),
+    "mcrt_framebuffer_set_active_tiles": (_c.c_int, [_vp, _vp, _c.c_int32]),
+    "mcrt_framebuffer_read_adaptive": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     "mcrt_framebuffer_read_bdpt": (_c.c_int, [_vp, _c.c_int, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64)]),
     "mcrt_make_pinhole_camera": (_c.c_int, [_vp, _vp, _vp, _c.c_float, _c.c_float, _c.c_float, _c.c_uint32,
                                             _c.c_uint32, _vp, _vp]),
@@ -552,6 +557,43 @@ class FrameBuffer:
         1 moments history, 3 previous normal-plane (H, W, 4), 2 the variance (H, W)."""
         out = np.zeros((self.H, self.W) + (() if which == T.TEMPORAL_VARIANCE else (4,)), np.float32)
         _check(lib().mcrt_framebuffer_read_temporal(self.h, which, _p(out), out.nbytes, None), self.ctx.h)
+        return out
+
+    def set_adaptive(self, error_threshold=0.05, min_samples=8, max_samples=0, luminance_floor=1e-3, on=True):
+        """mcrt_framebuffer_set_adaptive: adaptive sampling on (moments on, reset) or, on=False, off.
+        A tile (8x8 pixels) is done once it has min_samples samples and its error is <=
+        error_threshold, or once it has max_samples (0: no cap)."""
+        if not on:
+            _check(lib().mcrt_framebuffer_set_adaptive(self.h, None), self.ctx.h)
+            return
+        p = T.AdaptiveParams(error_threshold, int(min_samples), int(max_samples), luminance_floor)
+        _check(lib().mcrt_framebuffer_set_adaptive(self.h, _c.byref(p)), self.ctx.h)
+
+    def adaptive_reset(self):
+        """mcrt_adaptive_reset: tile counts and the frame count to 0, every tile listed."""
+        _check(lib().mcrt_adaptive_reset(self.h), self.ctx.h)
+
+    def adaptive_update(self):
+        """mcrt_adaptive_update: judges every tile, rebuilds the active list, returns its length
+        (the one host synchronisation of a round)."""
+        n = _c.c_int32()
+        _check(lib().mcrt_adaptive_update(self.h, _c.byref(n)), self.ctx.h)
+        return n.value
+
+    def set_active_tiles(self, ids):
+        """mcrt_framebuffer_set_active_tiles: the tiles the next calls render and accumulate,
+        strictly ascending ids (region rendering); the next adaptive_update replaces them."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        _check(lib().mcrt_framebuffer_set_active_tiles(self.h, _p(ids) if len(ids) else None, len(ids)), self.ctx.h)
+
+    def read_adaptive(self, which):
+        """mcrt_framebuffer_read_adaptive: 0 tile errors (float32), 1 tile sample counts (uint32), one
+        per tile in tile order; 2 the active list (uint32)."""
+        need = _c.c_uint64()
+        _check(lib().mcrt_framebuffer_read_adaptive(self.h, which, None, 0, _c.byref(need)), self.ctx.h)
+        out = np.zeros(need.value // 4, np.float32 if which == T.ADAPTIVE_TILE_ERROR else np.uint32)
+        if out.size:
+            _check(lib().mcrt_framebuffer_read_adaptive(self.h, which, _p(out), out.nbytes, None), self.ctx.h)
         return out
 
     def read(self, which=0):

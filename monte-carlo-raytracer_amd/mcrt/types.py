@@ -169,6 +169,16 @@ class TemporalParams(ctypes.Structure):
                 ("plane_threshold", ctypes.c_float), ("demodulate_albedo", ctypes.c_int32)]
 
 
+class AdaptiveParams(ctypes.Structure):
+    """mcrt_adaptive_params (include/mcrt_capi.h)."""
+    _fields_ = [("error_threshold", ctypes.c_float), ("min_samples", ctypes.c_int32),
+                ("max_samples", ctypes.c_int32), ("luminance_floor", ctypes.c_float)]
+
+
+# mcrt_framebuffer_read_adaptive `which`
+ADAPTIVE_TILE_ERROR, ADAPTIVE_TILE_SAMPLES, ADAPTIVE_ACTIVE_LIST = 0, 1, 2
+
+
 # mcrt_framebuffer_read_temporal `which`
 TEMPORAL_COLOUR, TEMPORAL_MOMENTS, TEMPORAL_VARIANCE, TEMPORAL_NORMAL_PLANE = 0, 1, 2, 3
 
