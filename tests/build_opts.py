@@ -191,6 +191,30 @@ def _levels(child, internal):
     return level
 
 
+def check_leaves(rec, scene, tri, lf, parent):
+    """The leaf checks of check_tree and lbvh_truth.check_lbvh: the leaf records `lf` of `rec` hold
+    every triangle of `scene` (tri: its world triangles) once, with its float32 vertex and edges,
+    and their id words are a leaf's.  parent: the parent index of every record.  Returns the triangle
+    number of every leaf."""
+    ids = rec.view(np.int32)
+    n = len(tri)
+    # (shape, prim) pairs are a permutation of the scene's triangles; vertex and edges
+    first = np.concatenate([[0], np.cumsum(scene.shapes["numTriangles"])[:-1]]).astype(np.int64)
+    shape, prim = ids[lf, 3].astype(np.int64), ids[lf, 7].astype(np.int64)
+    assert ((shape >= 0) & (shape < len(scene.shapes))).all()
+    assert ((prim >= 0) & (prim < scene.shapes["numTriangles"][shape])).all()
+    g = first[shape] + prim
+    assert (np.sort(g) == np.arange(n)).all(), "the leaves are not a permutation of the triangles"
+    t = tri[g]
+    assert same_words(rec[lf, 0:3], t[:, 0]).all()
+    assert same_words(rec[lf, 4:7], t[:, 1] - t[:, 0]).all()
+    assert same_words(rec[lf, 8:11], t[:, 2] - t[:, 0]).all()
+    assert (ids[lf, 11] == 0).all() and (ids[lf, 12] == -1).all() and (ids[lf, 14:16] == 0).all()
+    # word 13 of a leaf: -1 as built, its parent's index once the scene is on the device
+    assert ((ids[lf, 13] == -1) | (ids[lf, 13] == parent[lf])).all()
+    return g
+
+
 def check_tree(rec, scene, depth=None):
     """Asserts that the flat records `rec` are a correct BVH of `scene` (identity transforms), whatever
     the split policy: 2n - 1 records, n leaves that hold every triangle once with its float32 vertex
@@ -221,24 +245,11 @@ def check_tree(rec, scene, depth=None):
     assert (np.sort(child[p].ravel()) == np.arange(1, N)).all(), "a record has no parent or two"
     level = _levels(child, internal)
     assert (level >= 0).all()
-    # leaves: (shape, prim) pairs are a permutation of the scene's triangles; vertex and edges
-    first = np.concatenate([[0], np.cumsum(scene.shapes["numTriangles"])[:-1]]).astype(np.int64)
-    lf = idx[leaf]
-    shape, prim = ids[lf, 3].astype(np.int64), ids[lf, 7].astype(np.int64)
-    assert ((shape >= 0) & (shape < len(scene.shapes))).all()
-    assert ((prim >= 0) & (prim < scene.shapes["numTriangles"][shape])).all()
-    g = first[shape] + prim
-    assert (np.sort(g) == np.arange(n)).all(), "the leaves are not a permutation of the triangles"
-    t = tri[g]
-    assert same_words(rec[lf, 0:3], t[:, 0]).all()
-    assert same_words(rec[lf, 4:7], t[:, 1] - t[:, 0]).all()
-    assert same_words(rec[lf, 8:11], t[:, 2] - t[:, 0]).all()
-    assert (ids[lf, 11] == 0).all() and (ids[lf, 12] == -1).all() and (ids[lf, 14:16] == 0).all()
-    # word 13 of a leaf: -1 as built, its parent's index once the scene is on the device
     parent = np.zeros(N, np.int64)
     parent[child[p, 0]] = p
     parent[child[p, 1]] = p
-    assert ((ids[lf, 13] == -1) | (ids[lf, 13] == parent[lf])).all()
+    lf = idx[leaf]
+    t = tri[check_leaves(rec, scene, tri, lf, parent)]
     # bottom-up: leaves and exact box below every record
     lo = np.zeros((N, 3), np.float32)
     hi = np.zeros((N, 3), np.float32)
@@ -265,4 +276,4 @@ def check_tree(rec, scene, depth=None):
 
 
 __all__ = ["GRID", "HOST_ONLY", "FLT_MAX", "ROOT_SIZES", "FLAT_SCENES", "opts", "tuple_id", "flat_scene", "geo",
-           "geo_tame", "same_words", "check_tree", "check_nesting", "leaf_depth"]
+           "geo_tame", "same_words", "check_leaves", "check_tree", "check_nesting", "leaf_depth"]

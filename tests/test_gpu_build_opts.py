@@ -202,13 +202,18 @@ def test_deep_tree_compact_walk_equals_64b_walk(deep):
     np.testing.assert_array_equal(ac, ap)
 
 
-def test_deep_tree_against_the_oracle(deep):
+def deep_camera(W, H):
+    """The camera of the deep-tree frames (here and in tests/test_gpu_lbvh.py)."""
+    return make_camera((0.4, 0.05, -1.5), (0.4, 0.0, 0.0), W, H, fovy=45.0, near=0.1, far=30.0)
+
+
+def deep_answers_against_the_oracle(sc, rays, answers):
     """tests/test_gpu_trace.py's test_closest_vs_oracle / test_any_vs_oracle criteria, unchanged, on
-    the 64-B walk's answers against the oracle's walk of the same tree."""
-    sc, rays = deep["scene"], deep["rays"]
+    `answers` (closest hits, any-hit answers of `rays`) against the oracle's walk of the host tree
+    of `sc` with SAH off."""
     o = po.OracleScene(sc)
     o.build(10.0, 64, False)
-    ho, hg = o.closest(rays), deep["plain64"][0]
+    ho, hg = o.closest(rays), answers[0]
     same = (ho["shapeid"] == hg["shapeid"]) & (ho["primid"] == hg["primid"])
     assert same.mean() > 0.999, same.mean()
     hit = same & (ho["shapeid"] >= 0)
@@ -218,9 +223,14 @@ def test_deep_tree_against_the_oracle(deep):
     if diff.any():
         np.testing.assert_allclose(hg["uvwt"][diff, 3], ho["uvwt"][diff, 3], rtol=1e-3)
     _no_unexplained_ray(sc, rays, ~same, "closest_det")
-    a, g = o.any(rays), deep["plain64"][1]
+    a, g = o.any(rays), answers[1]
     assert (a == g).mean() > 0.999
     _no_unexplained_ray(sc, rays, a != g, "any_det")
+
+
+def test_deep_tree_against_the_oracle(deep):
+    """The 64-B walk's answers against the oracle's walk of the same tree."""
+    deep_answers_against_the_oracle(deep["scene"], deep["rays"], deep["plain64"])
 
 
 def test_deep_tree_frames_bit_identical(hip_ctx):
@@ -229,7 +239,7 @@ def test_deep_tree_frames_bit_identical(hip_ctx):
     from mcrt import lib
     sc = bo.flat_scene("geo_tame")
     W, H = 64, 48
-    cam = make_camera((0.4, 0.05, -1.5), (0.4, 0.0, 0.0), W, H, fovy=45.0, near=0.1, far=30.0)
+    cam = deep_camera(W, H)
     out = []
     for device in (3, 2):
         ds = lib.DeviceScene(hip_ctx, sc, device_build=device, **bo.opts(MID))
