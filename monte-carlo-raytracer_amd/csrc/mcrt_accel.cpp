@@ -170,11 +170,10 @@ static mcrt_status finish(mcrt_scene s, bool boxFromRoot) {
     // cannot take (LBVH numbering) or a device without room for it (~0.8 GB at 10 M triangles)
     // keeps the 64-B walk: the same answers.
     if (!t.twoLevel && env_int("MCRT_QUANT_NODES", 1) != 0) {
-        float4* q = nullptr;
-        size_t units = 0;
-        const hipError_t e = mcrt::build_qnodes(a.dNodes.get(), (uint32_t)t.numNodes, &q, &units, ctx->stream);
+        DevBuf<float4> q;
+        const hipError_t e = mcrt::build_qnodes(a.dNodes.get(), (uint32_t)t.numNodes, q, ctx->stream);
         if (e == hipSuccess) {
-            a.dQNodes.adopt(q, units);
+            a.dQNodes = std::move(q);
         } else if (e != hipErrorNotSupported && e != hipErrorOutOfMemory) {
             return fail(ctx, MCRT_ERROR_DEVICE, std::string("compact records: ") + hipGetErrorString(e));
         } else {

@@ -1,6 +1,7 @@
 // mcrt_capi.cpp -- host runtime behind include/mcrt_capi.h: the context, the scene tables, the ray
-// queries and the frame buffer's own planes (create and destroy, read and copy, postprocess, AOV,
-// bands).  The integrators' drivers are mcrt_pt_host.cpp and mcrt_bdpt_host.cpp.
+// queries and mcrt_render_aov, and the helpers the other host files share (mcrt_host.h).  The
+// integrators' drivers are mcrt_pt_host.cpp and mcrt_bdpt_host.cpp, the frame buffer's planes are
+// mcrt_film.hip's, the roofline probes mcrt_probe.hip's.
 //
 // Replaces the reference's OpenCL host plumbing (PlatformManager / KernelManager /
 // RTBufferManager, RTScene uploads, RadeonRays IntersectionApi, and the per-pass
@@ -57,6 +58,21 @@ mcrt_status mcrt::fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg) {
     g_lastError = msg;
     if (ctx) ctx->error = msg;
     return code;
+}
+
+// Device-side error flags raised by kernels since the last check (call after a synchronisation):
+// a traversal whose stack needed more entries than its spill column holds drops entries
+// (mcrt_traverse.h), so its hits may be wrong -- reported, never silent.
+mcrt_status mcrt::check_device_flags(mcrt_ctx ctx) {
+    int f = 0;
+    HIPCHK(ctx, hipMemcpy(&f, ctx->dFlags, sizeof(int), hipMemcpyDeviceToHost));
+    if (f != 0) {
+        HIPCHK(ctx, hipMemset(ctx->dFlags, 0, sizeof(int)));
+        return fail(ctx, MCRT_ERROR_DEVICE,
+                    "traversal stack overflow: a ray needed more stack entries than its spill column holds "
+                    "(results of the affected launches are unreliable)");
+    }
+    return MCRT_OK;
 }
 
 static void drain_pending(mcrt_ctx ctx) {
@@ -253,21 +269,6 @@ MCRT_API mcrt_status mcrt_ctx_create(int device, mcrt_ctx* out) {
     return MCRT_OK;
 }
 
-// Device-side error flags raised by kernels since the last check (call after a synchronisation):
-// a traversal whose stack needed more entries than its spill column holds drops entries
-// (mcrt_traverse.h), so its hits may be wrong -- reported, never silent.
-static mcrt_status check_device_flags(mcrt_ctx ctx) {
-    int f = 0;
-    HIPCHK(ctx, hipMemcpy(&f, ctx->dFlags, sizeof(int), hipMemcpyDeviceToHost));
-    if (f != 0) {
-        HIPCHK(ctx, hipMemset(ctx->dFlags, 0, sizeof(int)));
-        return fail(ctx, MCRT_ERROR_DEVICE,
-                    "traversal stack overflow: a ray needed more stack entries than its spill column holds "
-                    "(results of the affected launches are unreliable)");
-    }
-    return MCRT_OK;
-}
-
 MCRT_API mcrt_status mcrt_ctx_destroy(mcrt_ctx ctx) {
     if (!ctx) return MCRT_OK;
     hipSetDevice(ctx->device);
@@ -284,7 +285,7 @@ MCRT_API mcrt_status mcrt_ctx_synchronize(mcrt_ctx ctx) {
     hipSetDevice(ctx->device);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipDeviceSynchronize());   // frame-slot streams of the context's frame buffers
-    return check_device_flags(ctx);
+    return mcrt::check_device_flags(ctx);
 }
 
 MCRT_API mcrt_status mcrt_ctx_set_stream(mcrt_ctx ctx, void* stream) {
@@ -321,81 +322,6 @@ MCRT_API mcrt_status mcrt_ctx_kernel_stats(mcrt_ctx ctx, int max, const char** n
         ++k;
     }
     if (count) *count = k;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_ctx_stream_copy(mcrt_ctx ctx, uint64_t bytes, int iters, double* gbps) {
-    if (!ctx || !gbps || bytes < 4096 || iters < 1) return fail(ctx, MCRT_ERROR_INVALID_ARG, "bad stream-copy args");
-    hipSetDevice(ctx->device);
-    const size_t n4 = (size_t)(bytes / 2 / 16);   // half the bytes read, half written
-    float4 *a = nullptr, *b = nullptr;
-    HIPCHK(ctx, hipMalloc(&a, n4 * 16));
-    if (hipMalloc(&b, n4 * 16) != hipSuccess) { hipFree(a); return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "stream copy"); }
-    hipMemsetAsync(a, 0, n4 * 16, ctx->stream);
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    float best = 1e30f;
-    for (int i = 0; i < iters + 1; ++i) {
-        hipEventRecord(e0, ctx->stream);
-        mcrt::launch_stream_copy(a, b, n4, ctx->numCUs, ctx->stream);
-        hipEventRecord(e1, ctx->stream);
-        hipEventSynchronize(e1);
-        float ms = 0.0f;
-        hipEventElapsedTime(&ms, e0, e1);
-        if (i > 0 && ms < best) best = ms;   // launch 0 warms up
-    }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    hipFree(a);
-    hipFree(b);
-    HIPCHK(ctx, hipGetLastError());
-    *gbps = (double)(2 * n4 * 16) / (best * 1e-3) / 1e9;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_ctx_gather_chase(mcrt_ctx ctx, uint64_t records, int steps, int iters, double* gsteps) {
-    if (!ctx || !gsteps || records < 64 || records > 0xffffffffull || steps < 1 || iters < 1)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "bad gather-chase args");
-    hipSetDevice(ctx->device);
-    void* rec = nullptr;
-    uint32_t* sink = nullptr;
-    HIPCHK(ctx, hipMalloc(&rec, 64 * records));
-    if (hipMalloc(&sink, 4) != hipSuccess) { hipFree(rec); return fail(ctx, MCRT_ERROR_OUT_OF_MEMORY, "gather chase"); }
-    mcrt::launch_chase_init(rec, (uint32_t)records, ctx->stream);
-    const int waves = ctx->numCUs * 32;
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0);
-    hipEventCreate(&e1);
-    float best = 1e30f;
-    for (int i = 0; i < iters + 1; ++i) {
-        hipEventRecord(e0, ctx->stream);
-        mcrt::launch_chase(rec, (uint32_t)records, i == 0 ? std::max(1, steps / 4) : steps, waves, sink, ctx->stream);
-        hipEventRecord(e1, ctx->stream);
-        hipEventSynchronize(e1);
-        float ms = 0.0f;
-        hipEventElapsedTime(&ms, e0, e1);
-        if (i > 0 && ms < best) best = ms;   // launch 0 warms caches and translations
-    }
-    hipEventDestroy(e0);
-    hipEventDestroy(e1);
-    hipFree(rec);
-    hipFree(sink);
-    HIPCHK(ctx, hipGetLastError());
-    *gsteps = (double)waves * 64.0 * steps / (best * 1e-3) / 1e9;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_ctx_gather_chase_compact(mcrt_ctx ctx, uint64_t records, double leaf_frac, int steps,
-                                                   int iters, double* gsteps) {
-    if (!ctx || !gsteps || records < 64 || records > 0x3fffffffull || steps < 1 || iters < 1 || !(leaf_frac >= 0.0) ||
-        leaf_frac > 1.0)
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "bad gather-chase args");
-    hipSetDevice(ctx->device);
-    const int waves = ctx->numCUs * 32;
-    float best = 0.0f;
-    HIPCHK(ctx, mcrt::chase_compact((uint32_t)records, leaf_frac, steps, waves, iters, ctx->stream, &best));
-    *gsteps = (double)waves * 64.0 * steps / (best * 1e-3) / 1e9;
     return MCRT_OK;
 }
 
@@ -660,51 +586,8 @@ MCRT_API mcrt_status mcrt_event_destroy(mcrt_event ev) {
 }
 
 // ---------------------------------------------------------------------------
-// frame buffer
+// AOVs: a shading pass over borrowed camera hits (the frame buffer's planes: mcrt_film.hip)
 // ---------------------------------------------------------------------------
-MCRT_API mcrt_status mcrt_framebuffer_create(mcrt_ctx ctx, uint32_t width, uint32_t height, mcrt_framebuffer* out) {
-    if (!ctx || !out || width == 0 || height == 0 || (uint64_t)width * height > (1ull << 30))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "invalid frame buffer size");
-    hipSetDevice(ctx->device);
-    auto* fb = new mcrt_framebuffer_s();
-    fb->ctx = ctx;
-    fb->W = width;
-    fb->H = height;
-    fb->N = (size_t)width * height;
-    const size_t N = fb->N;
-    hipError_t e = hipSuccess;
-    for (auto* img : {&fb->wsum, &fb->image, &fb->denoised, &fb->display})
-        if (e == hipSuccess) e = (hipError_t)img->alloc(N);
-    if (e == hipSuccess) e = (hipError_t)fb->wts.alloc(N);
-    if (e == hipSuccess) e = (hipError_t)fb->hintPix.alloc(N);
-    fb->slot.resize(MCRT_MAX_FRAMES_IN_FLIGHT);
-    if (e == hipSuccess) e = mcrt::slot_alloc(fb->slot[0], N, N);   // one frame: hits by pixel
-    // zero-fills on slot 0's (private) stream, finished before the frame buffer is handed out:
-    // only this buffer's work is waited for, not the device (other contexts, a captured caller stream)
-    for (auto* img : {&fb->wsum, &fb->image, &fb->denoised, &fb->display})
-        if (e == hipSuccess) e = hipMemsetAsync(img->get(), 0, 16 * N, fb->slot[0].stream);
-    if (e == hipSuccess) e = hipMemsetAsync(fb->wts.get(), 0, 4 * N, fb->slot[0].stream);
-    if (e == hipSuccess) e = mcrt::fill_hints(fb->hintPix.get(), N, 1u << 22, fb->slot[0].stream);   // no hints
-    if (e == hipSuccess) e = hipStreamSynchronize(fb->slot[0].stream);
-    if (e != hipSuccess) {
-        mcrt::fb_free(fb);
-        delete fb;
-        return fail(ctx, e == hipErrorOutOfMemory ? MCRT_ERROR_OUT_OF_MEMORY : MCRT_ERROR_DEVICE,
-                    std::string("frame buffer: ") + hipGetErrorString(e));
-    }
-    *out = fb;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_destroy(mcrt_framebuffer fb) {
-    if (!fb) return MCRT_OK;
-    hipSetDevice(fb->ctx->device);
-    fb_sync(fb);
-    mcrt::fb_free(fb);
-    delete fb;
-    return MCRT_OK;
-}
-
 MCRT_API mcrt_status mcrt_render_aov(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
                                      const mcrt_frame_params* p, int aov, float* host_out) {
     if (!s || !fb || !cam || !p || !host_out) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
@@ -733,138 +616,6 @@ MCRT_API mcrt_status mcrt_render_aov(mcrt_scene s, mcrt_framebuffer fb, const mc
     hipFreeAsync(dOut, st);
     hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(ctx, MCRT_ERROR_DEVICE, std::string("aov: ") + hipGetErrorString(e));
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_device_ptrs(mcrt_framebuffer fb, void** radiance, void** weighted_sum,
-                                                  void** weight_sum, void** image) {
-    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
-    if (radiance) *radiance = cur_slot(fb).radiance.get();
-    if (weighted_sum) *weighted_sum = fb->wsum.get();
-    if (weight_sum) *weight_sum = fb->wts.get();
-    if (image) *image = fb->image.get();
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_postprocess(mcrt_framebuffer fb, const mcrt_postprocess_params* p) {
-    if (!fb || !p) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    const int W = (int)fb->W, H = (int)fb->H;
-    const float4* src = fb->image.get();
-    if (p->use_denoise) {
-        // RTDenoisePass (RTDenoisePass.cpp:21-60): the kernel writes nothing for a non-positive
-        // radius or sigma (Denoise.cl:18-19), so the pass then shows its image's old content.
-        if (p->denoise_radius > 16) return fail(ctx, MCRT_ERROR_INVALID_ARG, "denoise_radius > 16 (the GUI allows <= 10)");
-        if (p->denoise_radius > 0 && p->sigma_spatial > 0.0f && p->sigma_range > 0.0f)
-            mcrt::launch_denoise(W, H, p->denoise_radius, p->sigma_spatial, p->sigma_range, fb->image.get(), fb->denoised.get(),
-                                 ctx->stream);
-        src = fb->denoised.get();
-    }
-    if (p->use_tonemapping)   // RTToneMappingPass::applyReinhardToneMapping (RTToneMappingPass.cpp:38-72)
-        mcrt::launch_tonemap(W * H, p->min_luminance, src, fb->display.get(), ctx->stream);
-    else
-        HIPCHK(ctx, hipMemcpyAsync(fb->display.get(), src, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipGetLastError());
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_read(mcrt_framebuffer fb, int which, float* host_rgba) {
-    if (!fb || !host_rgba || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    const void* src = which == 0 ? (const void*)cur_slot(fb).radiance.get() : which == 1 ? (const void*)fb->wsum.get()
-                      : which == 2 ? (const void*)fb->image.get() : (const void*)fb->display.get();
-    HIPCHK(ctx, fb_sync(fb));
-    HIPCHK(ctx, hipMemcpy(host_rgba, src, 16 * fb->N, hipMemcpyDeviceToHost));
-    return check_device_flags(ctx);
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_read_frame(mcrt_framebuffer fb, int32_t k, float* host_rgba) {
-    if (!fb || !host_rgba) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    const int batch = cur_slot(fb).lastBatch;
-    if (k < 0 || k >= std::max(batch, 1))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame index outside the last mcrt_render_frames batch");
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, fb_sync(fb));
-    HIPCHK(ctx, hipMemcpy(host_rgba, cur_slot(fb).radiance.get() + (size_t)k * fb->N, 16 * fb->N, hipMemcpyDeviceToHost));
-    return check_device_flags(ctx);
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_copy_device(mcrt_framebuffer fb, int which, void* d_dst) {
-    if (!fb || !d_dst || which < 0 || which > 3) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    const void* src = which == 0 ? (const void*)cur_slot(fb).radiance.get() : which == 1 ? (const void*)fb->wsum.get()
-                      : which == 2 ? (const void*)fb->image.get() : (const void*)fb->wts.get();
-    if (which == 0) ctx_wait_slots(fb);
-    HIPCHK(ctx, hipMemcpyAsync(d_dst, src, (which == 3 ? 4 : 16) * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    // the slot may take its next frame only after this copy has read its radiance
-    if (which == 0) HIPCHK(ctx, mcrt::release_slot(fb, ctx->stream));
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_copy_device_frame(mcrt_framebuffer fb, int32_t k, void* d_dst) {
-    if (!fb || !d_dst) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    FrameSlot& slot = cur_slot(fb);
-    if (k < 0 || k >= std::max(slot.lastBatch, 1))
-        return fail(ctx, MCRT_ERROR_INVALID_ARG, "frame index outside the last mcrt_render_frames batch");
-    if (!slot.radiance) return fail(ctx, MCRT_ERROR_NOT_READY, "no frame rendered yet");
-    hipSetDevice(ctx->device);
-    ctx_wait_slots(fb);
-    HIPCHK(ctx, hipMemcpyAsync(d_dst, slot.radiance.get() + (size_t)k * fb->N, 16 * fb->N, hipMemcpyDeviceToDevice,
-                               ctx->stream));
-    HIPCHK(ctx, mcrt::release_slot(fb, ctx->stream));   // as mcrt_framebuffer_copy_device 0
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_set_accumulation(mcrt_framebuffer fb, const void* d_wsum, const void* d_wts) {
-    if (!fb || !d_wsum || !d_wts) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    HIPCHK(ctx, hipMemcpyAsync(fb->wsum.get(), d_wsum, 16 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(fb->wts.get(), d_wts, 4 * fb->N, hipMemcpyDeviceToDevice, ctx->stream));
-    mcrt::launch_resolve(fb->W, fb->H, fb->wsum.get(), fb->wts.get(), fb->image.get(), ctx->stream);
-    HIPCHK(ctx, hipGetLastError());
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_bands_pack(mcrt_framebuffer fb, void* d_dst) {
-    if (!fb || !d_dst) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    if (!fb->haveBands) return fail(fb->ctx, MCRT_ERROR_NOT_READY, "no frame rendered");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    mcrt::launch_band_pack(fb->bands, fb->wsum.get(), fb->wts.get(), static_cast<float*>(d_dst), ctx->stream);
-    HIPCHK(ctx, hipGetLastError());
-    return MCRT_OK;
-}
-
-static int band_max_rows(const FrameArgs& f) { return mcrt::band_max_rows(f.H, f.bandRows, f.numBands); }
-
-MCRT_API mcrt_status mcrt_framebuffer_band_layout(mcrt_framebuffer fb, int32_t* max_rows, int32_t* num_bands,
-                                                  int32_t* band_index) {
-    if (!fb) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "fb is NULL");
-    if (!fb->haveBands) return fail(fb->ctx, MCRT_ERROR_NOT_READY, "no frame rendered");
-    if (max_rows) *max_rows = band_max_rows(fb->bands);
-    if (num_bands) *num_bands = fb->bands.numBands;
-    if (band_index) *band_index = fb->bands.bandIndex;
-    return MCRT_OK;
-}
-
-MCRT_API mcrt_status mcrt_framebuffer_bands_unpack(mcrt_framebuffer fb, const void* d_recv, int32_t max_rows) {
-    if (!fb || !d_recv) return fail(fb ? fb->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "bad args");
-    if (!fb->haveBands) return fail(fb->ctx, MCRT_ERROR_NOT_READY, "no frame rendered");
-    const FrameArgs& f = fb->bands;
-    // every chunk of d_recv must hold the largest rank's rows
-    if (max_rows < band_max_rows(f))
-        return fail(fb->ctx, MCRT_ERROR_INVALID_ARG, "max_rows below the largest rank's row count");
-    mcrt_ctx ctx = fb->ctx;
-    hipSetDevice(ctx->device);
-    mcrt::launch_band_unpack(f, max_rows, static_cast<const float*>(d_recv), fb->wsum.get(), fb->wts.get(), fb->image.get(),
-                             ctx->stream);
-    HIPCHK(ctx, hipGetLastError());
     return MCRT_OK;
 }
 

@@ -2,12 +2,15 @@
 // the few helpers that host code in another file may call.  Not part of the ABI.
 //
 // This is the boundary between the host files.  mcrt_capi.cpp holds the context, the scene tables,
-// the ray queries and the frame buffer's own planes.  A subsystem with entry points of its own
-// (mcrt_denoise.hip, mcrt_adaptive.hip, mcrt_accel.cpp, mcrt_bdpt_host.cpp, mcrt_pt_host.cpp)
-// includes this header, reaches the rest of the runtime through what is declared here and nothing
-// else, and keeps its state in one struct that only it names the fields of: DenoiseState,
-// AdaptiveState, BdptState and the frame slots (FrameSlot, mcrt_pt_host.cpp) held by the frame
-// buffer, AccelState held by the scene.  It compiles
+// the ray queries and mcrt_render_aov.  A subsystem with entry points of its own
+// (mcrt_denoise.hip, mcrt_adaptive.hip, mcrt_accel.cpp, mcrt_bdpt_host.cpp, mcrt_pt_host.cpp,
+// mcrt_film.hip, mcrt_probe.hip) includes this header, reaches the rest of the runtime through what
+// is declared here and nothing else, and keeps its state in one struct that only it names the fields
+// of: DenoiseState, AdaptiveState, BdptState and the frame slots (FrameSlot, mcrt_pt_host.cpp) held
+// by the frame buffer, AccelState held by the scene.  Two have no such struct: the probes keep no
+// state, and the film's planes (wsum, wts, image, denoised, display, bands) are plain fields of the
+// frame buffer, which the integrators' hosts and the denoiser read; mcrt_film.hip creates,
+// zero-fills, reads back, packs and post-processes them.  It compiles
 // as plain C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip translation unit.
 #pragma once
 #include <climits>
@@ -146,7 +149,7 @@ static_assert(sizeof(SlotBlock) == 512 + 176 * MCRT_MAX_BATCH_FRAMES + sizeof(mc
 // for bit.  Small per-rank frames (tile split over many GPUs) do not fill 256 CUs alone.
 // The slots are mcrt_pt_host.cpp's: it allocates and frees them, chooses one per call, and alone
 // names the queues, the block, the spill columns, the tile order, the suspended walks and -- apart
-// from ctx_wait_slots -- the events.  mcrt_capi.cpp reads radiance, lastBatch and stream;
+// from ctx_wait_slots -- the events.  mcrt_film.hip reads radiance and lastBatch, mcrt_capi.cpp stream;
 // mcrt_bdpt_host.cpp, handed a ready slot by the entry function, also writes radiance, the block's
 // cameras, lastMaxDepth and lastPixels and records `done` after a gather; everything else borrows
 // the current slot through borrow_camera_hits and release_slot below.
@@ -312,6 +315,9 @@ inline FrameSlot& cur_slot(mcrt_framebuffer fb) { return fb->slot[fb->cur]; }
 namespace mcrt {
 // records msg as the thread's and the context's (may be NULL) last error; returns code
 mcrt_status fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg);
+// Reports and clears the device-side error flags kernels raised since the last check (a traversal
+// stack overflow); call after a synchronisation
+mcrt_status check_device_flags(mcrt_ctx ctx);
 // The shapes of an update (same count and topology as the scene's, checked by the caller) against
 // the scene's current table counts (check_scene_tables), and a moved startVertex against the host
 // copies of the indices and the vertex count.  Changes nothing; MCRT_ERROR_INVALID_ARG names the shape.

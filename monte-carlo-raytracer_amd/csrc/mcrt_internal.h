@@ -1,5 +1,6 @@
-// mcrt_internal.h -- structures shared by the host runtime (mcrt_capi.cpp) and the
-// HIP kernels (mcrt_kernels.hip).  Not part of the public ABI.
+// mcrt_internal.h -- structures shared by the host runtime (mcrt_capi.cpp and the subsystems' host
+// files) and the HIP translation units (mcrt_kernels.hip, mcrt_bdpt.hip, mcrt_film.hip,
+// mcrt_qnodes.hip, ...), and the launchers one file offers another.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -134,7 +135,7 @@ struct TraceCtx {
     float hintLo[3], hintInvExt[3];   // cell = (o - hintLo) * hintInvExt * MCRT_HINT_GRID
     uint32_t numNodes;      // records in `nodes` (hints are range-checked against it)
     int* hintHits;          // rays answered by their hint are counted here (NULL: not counted)
-    // Compact records of the same tree (mcrt_kernels.hip k_qnodes_convert; the per-ray walks of the
+    // Compact records of the same tree (mcrt_qnodes.hip k_qnodes_convert; the per-ray walks of the
     // LAY_QUANT instantiations, mcrt_traverse.h traverseQOct): 32-B internal records with 8-bit
     // outward-rounded child boxes, 48-B leaves; a record reference is (offset / 16) << 1 | leaf.
     // NULL: not built (two-level, non-DFS trees, MCRT_QUANT_NODES=0).
@@ -210,30 +211,28 @@ void launch_guides_motion(const SceneArgs& s, const FrameArgs& f, const mcrt_cam
 // list (adaptive sampling, listLen > 0 padded entries): only its tiles, a tile's count as its frame
 void launch_moments(const FrameArgs& f, int frame, const float4* radiance, float2* moments, hipStream_t st,
                     const uint32_t* list = nullptr, int listLen = 0, const uint32_t* tileCount = nullptr);
-// filters: the reconstruction filter of each batch frame in device memory (KRN/kernel_data.h:63-80), k_accumulate
-// evaluates its weight like ReconstructionPass (reconstruction.cl:21-42); filterStride 0 = one filter for all frames
+// mcrt_film.hip's k_accumulate for mcrt_pt_host.cpp.  filters: the reconstruction filter of each batch frame in
+// device memory (KRN/kernel_data.h:63-80), k_accumulate evaluates its weight like ReconstructionPass (reconstruction.cl:21-42); filterStride 0 = one filter for all frames
 // list, listLen, tileCount as launch_moments'
 void launch_accumulate(const FrameArgs& f, int frame, const mcrt_filter* filters, int filterStride, const float4* radiance, float4* wsum, float* wts,
                        float4* image, hipStream_t st, const uint32_t* list = nullptr, int listLen = 0,
                        const uint32_t* tileCount = nullptr);
-void launch_resolve(uint32_t W, uint32_t H, const float4* wsum, const float* wts, float4* image, hipStream_t st);
-void launch_band_pack(const FrameArgs& f, const float4* wsum, const float* wts, float* out, hipStream_t st);
-void launch_band_unpack(const FrameArgs& f, int maxRows, const float* recv, float4* wsum, float* wts, float4* image,
-                        hipStream_t st);
-void launch_denoise(int W, int H, int r, float ss, float sr, const float4* in, float4* out, hipStream_t st);
+// mcrt_film.hip's k_tonemap for mcrt_denoise.hip
 void launch_tonemap(int n, float Lwhite, const float4* in, float4* out, hipStream_t st);
-void launch_stream_copy(const float4* src, float4* dst, size_t n4, int numCUs, hipStream_t st);
-// parent index of each triangle leaf into its record's word 13 (flat trees, mcrt_accel.cpp finish)
+// mcrt_qnodes.hip: parent index of each triangle leaf into its record's word 13 (flat trees, mcrt_accel.cpp finish)
 void launch_leaf_parents(float4* nodes, uint32_t n, hipStream_t st);
 // order[0..n) = tiles by descending cost[tile] (bucketed; one workgroup)
 void launch_tile_order(const uint32_t* cost, int n, uint32_t* order, hipStream_t st);
-// compact records of a flat DFS tree (after launch_leaf_parents): *qOut (16-B units, caller frees),
-// *units its size; hipErrorNotSupported when the tree is not in DFS order (left child = i + 1)
-hipError_t build_qnodes(const float4* nodes, uint32_t n, float4** qOut, size_t* units, hipStream_t st);
-void launch_chase_init(void* rec, uint32_t n, hipStream_t st);
-void launch_chase(const void* rec, uint32_t n, int steps, int waves, uint32_t* sink, hipStream_t st);
-// the chase over packed 32-B / 48-B records (mcrt_ctx_gather_chase_compact): best of iters launches
-hipError_t chase_compact(uint32_t n, double leafFrac, int steps, int waves, int iters, hipStream_t st, float* bestMs);
+// mcrt_qnodes.hip: compact records of a flat DFS tree (after launch_leaf_parents) into q, 16-B units;
+// hipErrorNotSupported when the tree is not in DFS order (left child = i + 1), a box cannot be
+// bounded by the bytes, or qnode_offsets refuses.  q is empty after any failure.
+template <class T>
+class DevBuf;   // mcrt_devbuf.h
+hipError_t build_qnodes(const float4* nodes, uint32_t n, DevBuf<float4>& q, hipStream_t st);
+// The compact layout's arithmetic: n records of units[i] = 2 or 3 16-B units packed back to back,
+// off = their offsets (exclusive scan, device), *total = the units of all.  Finishes st.
+// hipErrorNotSupported for n == 0 and for a total >= 2^31: a record reference is off << 1 | leaf.
+hipError_t qnode_offsets(uint32_t* units, uint32_t* off, uint32_t n, size_t* total, hipStream_t st);
 void launch_bdpt_start(const SceneArgs& s, const FrameArgs& f, const BdptArgs& b, const mcrt_camera* cam,
                        const BdptQueue& camQ, const BdptQueue& lightQ, hipStream_t st);
 void launch_bdpt_vertex(const SceneArgs& s, const FrameArgs& f, const BdptArgs& b, int depth, const BdptQueue& qIn,

@@ -7,14 +7,15 @@
 //                        wave64 ballot/popc compaction into the shadow and extension queues
 //     k_shadow           any-hit over the shadow queue; radiance += L * V (ShadowPass)
 //     k_extend           closest hit over the extension queue (if b + 1 < D)
-//   k_accumulate         ReconstructionPass (clamp, weighted running mean)
+//   (k_accumulate, the ReconstructionPass, is the film's: mcrt_film.hip)
+// Also here: the RadeonRays-style ray queries, the AOV and denoiser-guide passes over the camera
+// hits, the scene's small kernels (k_surface_records, k_pose_snapshot) and k_tile_order; at the end
+// the launchers the host files call (mcrt_internal.h).
 // Traversal: the RadeonRays Bvh2 as one array of 64-B records (internal nodes hold both child
 // boxes, leaves their triangle), one flat loop per ray with a per-lane LDS short stack
 // (16 entries, [entry][lane] layout -> conflict free) spilling to a per-ray global column;
 // one wave per workgroup, the hardware dispatcher schedules the waves.
 #include <algorithm>
-
-#include <rocprim/device/device_scan.hpp>
 
 #include "mcrt_device.h"
 #include "mcrt_internal.h"
@@ -840,402 +841,6 @@ __global__ __launch_bounds__(256) void k_pose_snapshot(const mcrt_shape* __restr
     reinterpret_cast<uint32_t*>(out)[i] = w < WORDS - 1 ? src[(size_t)k * SHAPE_WORDS + w] : 0u;
 }
 
-// ---------------------------------------------------------------------------
-// ReconstructionPass (KRN/reconstruction.cl:6-60) with the filters of KRN/filters.cl:12-69,
-// evaluated on the device as the reference does (same expression shapes, so clang contracts the
-// same products into fma; `/` is the OpenCL-default 2.5-ulp division, cl_div; exp and sin are the
-// device library's, like OpenCL's).  The weight is uniform per frame (one pixelOffset per frame,
-// RTReconstructionPass.cpp:71-123); pinned against the reference's filters.cl run live
-// (oracle/refbuild/clprobe_filters.cl, tests/test_gpu_accumulate.py).  Band rows only.
-// ---------------------------------------------------------------------------
-MCRT_DEV float filterTriangle(f2 p, f2 radius) {   // filters.cl:17-20
-    return fmaxf(0.0f, radius.x - fabsf(p.x)) * fmaxf(0.0f, radius.y - fabsf(p.y));
-}
-MCRT_DEV float filterGaussian1D(float d, float alpha, float expv) {   // filters.cl:22-25
-    return fmaxf(0.0f, expf(-alpha * d * d) - expv);
-}
-MCRT_DEV float filterMitchell1D(float x, float B, float C) {   // filters.cl:32-39
-    x = fabsf(2.0f * x);
-    if (x > 1.0f)
-        return ((-B - 6*C) * x*x*x + (6*B + 30*C) * x*x + (-12*B - 48*C) * x + (8*B + 24*C)) * (1.f/6.f);
-    else
-        return ((12 - 9*B - 6*C) * x*x*x + (-18 + 12*B + 6*C) * x*x + (6 - 2*B)) * (1.f/6.f);
-}
-MCRT_DEV float filterSinc(float x) {   // filters.cl:47-54 (1e-5 is a float literal: no cl_khr_fp64 pragma)
-    x = fabsf(x);
-    if (x < 1e-5f) return 1.0f;
-    return cl_div(sinf(PI_F * x), (PI_F * x));
-}
-MCRT_DEV float filterWindowedSinc(float x, float radius, float tau) {   // filters.cl:56-64
-    x = fabsf(x);
-    if (x > radius) return 0.0f;
-    const float lanczos = filterSinc(cl_div(x, tau));
-    return filterSinc(x) * lanczos;
-}
-// the switch of reconstruction.cl:23-42
-MCRT_DEV float filterWeight(const mcrt_filter& fp) {
-    const f2 p = f2{fp.pixelOffset.x, fp.pixelOffset.y}, radius = f2{fp.radius.x, fp.radius.y};
-    switch (fp.filterType) {
-    case MCRT_TRIANGLE_FILTER: return filterTriangle(p, radius);
-    case MCRT_GAUSSIAN_FILTER:
-        return filterGaussian1D(p.x, fp.gaussianAlpha, fp.gaussianExpX) * filterGaussian1D(p.y, fp.gaussianAlpha, fp.gaussianExpY);
-    case MCRT_MITCHELL_FILTER:
-        return filterMitchell1D(cl_div(p.x, radius.x), fp.mitchellB, fp.mitchellC) *
-               filterMitchell1D(cl_div(p.y, radius.y), fp.mitchellB, fp.mitchellC);
-    case MCRT_LANCZOS_SINC_FILTER:
-        return filterWindowedSinc(p.x, radius.x, fp.lanczosSincTau) * filterWindowedSinc(p.y, radius.y, fp.lanczosSincTau);
-    default: return 1.0f;   // RT_BOX_FILTER
-    }
-}
-
-// A batch of f.batch frames (mcrt_render_frames) is accumulated in frame order, frame + k with
-// filter filters[k * fstride]: per pixel the same operations as f.batch single-frame launches.
-// LIST (adaptive sampling): wave j takes tile list[j] (padded with numTiles past the list's end) and
-// the tile's sample count stands for `frame`, so "first sample" is the count being 0; the pixels of
-// other tiles are not touched.
-template <bool LIST>
-__global__ __launch_bounds__(256) void k_accumulate(FrameArgs f, int frame, const mcrt_filter* __restrict__ filters, int fstride,
-                                                    const float4* __restrict__ radiance, float4* __restrict__ wsum,
-                                                    float* __restrict__ wts, float4* __restrict__ image,
-                                                    const uint32_t* __restrict__ list, const uint32_t* __restrict__ tileCount) {
-    const int lane = threadIdx.x & 63;
-    int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    if (LIST) tile = (int)list[tile];
-    int x, y;
-    if (tile >= f.numTiles || !tilePixel(f, tile, lane, x, y)) return;
-    if (LIST) frame = (int)tileCount[tile];
-    const int pix = y * (int)f.W + x;
-    f4 s;
-    float ws;
-    if (frame != 0) {
-        const float4 o = wsum[pix];
-        s = f4{o.x, o.y, o.z, o.w};
-        ws = wts[pix];
-    }
-    for (int k = 0; k < f.batch; ++k) {
-        const float4 r4 = radiance[(size_t)k * f.W * f.H + pix];
-        const f4 radiance4 = f4{cl_clamp(r4.x, 0.0f, 1000.0f), cl_clamp(r4.y, 0.0f, 1000.0f),
-                                cl_clamp(r4.z, 0.0f, 1000.0f), cl_clamp(r4.w, 0.0f, 1000.0f)};
-        const float w = filterWeight(filters[k * fstride]);
-        if (frame + k == 0) {
-            s = radiance4 * w;
-            ws = w;
-        } else {
-            s += radiance4 * w;   // contracted to fma, as reconstruction.cl:50
-            ws = ws + w;
-        }
-    }
-    wsum[pix] = make_float4(s.x, s.y, s.z, s.w);
-    wts[pix] = ws;
-    const f4 fin = cl_div(s, ws);
-    image[pix] = make_float4(fin.x, fin.y, fin.z, fin.w);
-}
-
-// image = sum / weight after a multi-GPU reduce of the accumulators
-__global__ __launch_bounds__(256) void k_resolve(int n, const float4* __restrict__ wsum, const float* __restrict__ wts,
-                                                 float4* __restrict__ image) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 s = wsum[i];
-    const float w = wts[i];
-    image[i] = make_float4(cl_div(s.x, w), cl_div(s.y, w), cl_div(s.z, w), cl_div(s.w, w));
-}
-
-// Tile split, end of job: a rank's own rows of the accumulators in its band order (local 8-row
-// block tb at rows 8 tb .. 8 tb + 7, tilePixel's numbering; mcrt.dist.band_rows_of), one packed row
-// = W x (sum w*L as 4 floats) then W x sum w, straight from the frame buffer: no full-frame copy
-// before the gather.  bpb = band_rows / 8.
-__device__ __forceinline__ void bandOwner(int y, int bpb, int numBands, int& r, int& row) {
-    const int gb = y >> 3;
-    r = (gb / bpb) % numBands;
-    row = ((gb / (bpb * numBands)) * bpb + gb % bpb) * 8 + (y & 7);
-}
-
-__global__ __launch_bounds__(256) void k_band_pack(int W, int H, int bpb, int numBands, int band,
-                                                   const float4* __restrict__ wsum, const float* __restrict__ wts,
-                                                   float* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W * H) return;
-    const int y = i / W, x = i - y * W;
-    int r, row;
-    bandOwner(y, bpb, numBands, r, row);
-    if (r != band) return;
-    float* o = out + (size_t)row * 5 * W;
-    const float4 v = wsum[i];
-    o[4 * x] = v.x;
-    o[4 * x + 1] = v.y;
-    o[4 * x + 2] = v.z;
-    o[4 * x + 3] = v.w;
-    o[4 * W + x] = wts[i];
-}
-
-// Rank dst after the gather: every other rank's rows (recv = numBands x maxRows packed rows) into
-// the accumulators in place, then the image (k_resolve's division) in the same pass.
-__global__ __launch_bounds__(256) void k_band_unpack(int W, int H, int bpb, int numBands, int band, int maxRows,
-                                                     const float* __restrict__ recv, float4* __restrict__ wsum,
-                                                     float* __restrict__ wts, float4* __restrict__ image) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= W * H) return;
-    const int y = i / W, x = i - y * W;
-    int r, row;
-    bandOwner(y, bpb, numBands, r, row);
-    float4 s;
-    float w;
-    if (r == band) {
-        s = wsum[i];
-        w = wts[i];
-    } else {
-        const float* p = recv + ((size_t)r * maxRows + row) * 5 * W;
-        s = make_float4(p[4 * x], p[4 * x + 1], p[4 * x + 2], p[4 * x + 3]);
-        w = p[4 * W + x];
-        wsum[i] = s;
-        wts[i] = w;
-    }
-    image[i] = make_float4(cl_div(s.x, w), cl_div(s.y, w), cl_div(s.z, w), cl_div(s.w, w));
-}
-
-// ---------------------------------------------------------------------------
-// Post-process (the reference's RTDenoisePass + RTToneMappingPass after reconstruction)
-// ---------------------------------------------------------------------------
-#define DENOISE_TILE 16
-#define DENOISE_RMAX 16
-// BilateralDenoise (KRN/Denoise.cl:6-47): a 16x16 tile plus its clamped apron staged in LDS
-// once (the reference re-reads the (2r+1)^2 window through the image unit per pixel); the
-// window is walked in the reference's order (x outer, y inner) so the sums round identically.
-__global__ __launch_bounds__(DENOISE_TILE * DENOISE_TILE) void k_denoise(int W, int H, int r, float ss, float sr,
-                                                                         const float4* __restrict__ in,
-                                                                         float4* __restrict__ out) {
-    __shared__ float4 tile[(DENOISE_TILE + 2 * DENOISE_RMAX) * (DENOISE_TILE + 2 * DENOISE_RMAX)];
-    const int TW = DENOISE_TILE + 2 * r;
-    const int x0 = blockIdx.x * DENOISE_TILE - r, y0 = blockIdx.y * DENOISE_TILE - r;
-    const int tid = threadIdx.y * DENOISE_TILE + threadIdx.x;
-    for (int i = tid; i < TW * TW; i += DENOISE_TILE * DENOISE_TILE) {
-        const int gx = min(max(x0 + i % TW, 0), W - 1), gy = min(max(y0 + i / TW, 0), H - 1);
-        tile[i] = in[(size_t)gy * W + gx];
-    }
-    __syncthreads();
-    const int gx = blockIdx.x * DENOISE_TILE + threadIdx.x, gy = blockIdx.y * DENOISE_TILE + threadIdx.y;
-    if (gx >= W || gy >= H) return;
-    const float sdSq = ss * ss, srSq = sr * sr;
-    const float4 oc = tile[(gy - y0) * TW + (gx - x0)];
-    const f4 o = f4{oc.x, oc.y, oc.z, oc.w};
-    f4 fc = f4{0.0f, 0.0f, 0.0f, 0.0f};
-    float weightSum = 0.0f;
-    for (int rx = -r; rx <= r; ++rx) {
-        const int x = min(max(rx + gx, 0), W - 1);
-        for (int ry = -r; ry <= r; ++ry) {
-            const int y = min(max(ry + gy, 0), H - 1);
-            const float4 kc = tile[(y - y0) * TW + (x - x0)];
-            const f4 k = f4{kc.x, kc.y, kc.z, kc.w};
-            const f4 cd = o - k;
-            const float d2 = fmaf(cd.w, cd.w, fmaf(cd.z, cd.z, fmaf(cd.y, cd.y, cd.x * cd.x)));   // dot(float4)
-            const int sp = (gx - x) * (gx - x) + (gy - y) * (gy - y);
-            const float w = expf(cl_div((float)(-sp), (2.0f * sdSq)) - cl_div(d2, (2.0f * srSq)));
-            weightSum += w;
-            fc += w * k;
-        }
-    }
-    fc = cl_div(fc, weightSum);
-    out[(size_t)gy * W + gx] = make_float4(fc.x, fc.y, fc.z, fc.w);
-}
-
-// ReinhardToneMapping (KRN/ToneMapping.cl:42-63), luminance of KRN/colors.cl:19-22
-__global__ __launch_bounds__(256) void k_tonemap(int n, float Lwhite, const float4* __restrict__ in,
-                                                 float4* __restrict__ out) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float4 p = in[i];
-    const float L = 0.212671f * p.x + 0.715160f * p.y + 0.072169f * p.z;
-    const float tL = cl_div(L * (1.0f + cl_div(L, (Lwhite * Lwhite))), (1.0f + L));
-    const float s = cl_div(tL, L);
-    out[i] = make_float4(p.x * s, p.y * s, p.z * s, p.w);
-}
-
-// Dependent-gather ceiling probe (mcrt_ctx_gather_chase): every lane follows a chain of 64-B
-// records whose links are read from the record just fetched, fetched as four 16-B pieces -- the
-// traversal's access pattern with none of its arithmetic.  The array size decides where the
-// records come from (L2, Infinity Cache, HBM), so the traversal's node-visit rate can be set
-// against the ceiling of its own access pattern (tools/probe/chase_probe.hip has more variants).
-__global__ void k_chase_init(int4* rec, uint32_t n, uint32_t seed) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    uint32_t h = (uint32_t)i * 2654435761u ^ seed;
-    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
-    const uint32_t nxt = h % n;
-    for (int q = 0; q < 4; ++q) rec[4 * i + q] = make_int4((int)nxt, (int)(nxt ^ 1u), (int)(nxt ^ 2u), (int)nxt);
-}
-__global__ __launch_bounds__(64) void k_chase(const int4* __restrict__ rec, uint32_t n, int steps, uint32_t* sink) {
-    const uint32_t chain = blockIdx.x * 64 + threadIdx.x;
-    uint32_t h = chain * 0x9E3779B9u + 12345u;
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13;
-    uint32_t idx = h % n, acc = 0;
-    for (int s = 0; s < steps; ++s) {
-        const int4 a = rec[4 * (size_t)idx], b = rec[4 * (size_t)idx + 1];
-        const int4 c = rec[4 * (size_t)idx + 2], d = rec[4 * (size_t)idx + 3];
-        asm volatile("" ::"v"(a.y), "v"(b.y), "v"(c.y));
-        acc += (uint32_t)(a.z ^ b.z ^ c.z);
-        idx = (uint32_t)d.w;
-    }
-    if (acc == 0xdeadbeefu) sink[0] = idx;   // never true: keeps the loads live
-}
-
-// The chase over the compact records' layout: record i is 2 (internal, 32 B) or 3 (leaf, 48 B)
-// 16-B units, packed back to back at off[i] (exclusive scan of chase_units); its link is the next
-// record's reference (unit offset << 1 | leaf bit), so a leaf's third unit is fetched in the same
-// round trip as in mcrt_traverse.h qwalk.
-MCRT_DEV uint32_t chaseHash(uint32_t i, uint32_t seed) {
-    uint32_t h = i * 2654435761u ^ seed;
-    h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
-    return h;
-}
-__global__ void k_chase_units(uint32_t* units, uint32_t n, uint32_t leaf16) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) units[i] = 2u + ((chaseHash((uint32_t)i, 99u) & 0xffffu) < leaf16 ? 1u : 0u);
-}
-__global__ void k_chase_init_compact(int4* rec, const uint32_t* off, const uint32_t* units, uint32_t n) {
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const uint32_t nxt = chaseHash((uint32_t)i, 777u) % n;
-    const int ref = (int)((off[nxt] << 1) | (units[nxt] == 3u ? 1u : 0u));
-    for (uint32_t q = 0; q < units[i]; ++q) rec[off[i] + q] = make_int4((int)nxt, (int)(nxt ^ 1u), (int)(nxt ^ 2u), ref);
-}
-__global__ __launch_bounds__(64) void k_chase_compact(const int4* __restrict__ rec, const uint32_t* __restrict__ off,
-                                                      const uint32_t* __restrict__ units, uint32_t n, int steps,
-                                                      uint32_t* sink) {
-    const uint32_t chain = blockIdx.x * 64 + threadIdx.x;
-    uint32_t h = chain * 0x9E3779B9u + 12345u;
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13;
-    const uint32_t i0 = h % n;
-    uint32_t ref = (off[i0] << 1) | (units[i0] == 3u ? 1u : 0u), acc = 0;
-    for (int s = 0; s < steps; ++s) {
-        const int4* p = rec + (ref >> 1);
-        const int4 a = p[0], b = p[1];
-        int4 c;
-        asm("" : "=v"(c.x), "=v"(c.y), "=v"(c.z), "=v"(c.w));
-        if (ref & 1u) c = p[2];
-        asm volatile("" ::"v"(a.y), "v"(b.y), "v"(c.y));
-        acc += (uint32_t)(a.z ^ b.z ^ c.z);
-        ref = (uint32_t)a.w;
-    }
-    if (acc == 0xdeadbeefu) sink[0] = ref;   // never true: keeps the loads live
-}
-
-// Parent links of the flat tree's leaves (the occluder hints' box test, mcrt_traverse.h
-// hintOccludes): every internal record writes its index into word 13 of each child that is a
-// triangle leaf (mcrt_bvh.cpp leaves carry -1 there; the traversal never reads it for a leaf).
-__global__ __launch_bounds__(256) void k_leaf_parents(float4* __restrict__ nodes, uint32_t n) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int4 w = *reinterpret_cast<const int4*>(&nodes[4 * (size_t)i + 3]);
-    if (w.x < 0) return;
-    const int ch[2] = {w.x, w.y};
-    for (int k = 0; k < 2; ++k) {
-        if ((uint32_t)ch[k] >= n) continue;
-        int* cw = reinterpret_cast<int*>(&nodes[4 * (size_t)ch[k] + 3]);
-        if (cw[0] == -1) cw[1] = (int)i;
-    }
-}
-
-// Compact records (mcrt_traverse.h traverseQOct has the format and the exactness argument).
-// Sizes in 16-B units per 64-B record (internal 2, leaf 3); notDfs: a left child that is not the
-// next record (the LBVH's numbering) -- the compact walk takes the left child as the next record.
-__global__ __launch_bounds__(256) void k_qnodes_sizes(const float4* __restrict__ nodes, uint32_t n,
-                                                      uint32_t* __restrict__ units, int* __restrict__ notDfs) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const int4 w = *reinterpret_cast<const int4*>(&nodes[4 * (size_t)i + 3]);
-    units[i] = w.x >= 0 ? 2u : 3u;
-    if (w.x >= 0 && w.x != (int)i + 1) atomicOr(notDfs, 1);
-}
-
-// One axis of an internal record: its origin (the smaller lo) and the exponent byte e of its step,
-// 2^(e - 127) >= extent / 250.  False for non-finite boxes.
-MCRT_DEV bool quantExp(float lo0, float hi0, float lo1, float hi1, float& o, uint32_t& e) {
-    o = fminf(lo0, lo1);
-    const float ext = fmaxf(hi0, hi1) - o;
-    if (!(ext >= 0.0f) || ext == __builtin_inff()) return false;
-    int k = -126;
-    if (ext > 0.0f) frexpf(ext * (1.0f / 250.0f), &k);   // ext / 250 <= 2^k
-    e = (uint32_t)min(max(k + 127, 1), 254);
-    return true;
-}
-// The two children's (lo, hi) on that axis as bytes q with fmaf(q, s, o) <= lo and >= hi exactly as
-// the traversal decodes them; s = the walk's step (qScales: 2^(e - 127) times a mantissa the meta
-// word's lower fields supply: 1 for x, about 1.24 for y and z), so 255 s covers the extent.
-// False if no byte reaches.
-MCRT_DEV bool quantBytes(float lo0, float hi0, float lo1, float hi1, float o, float sc, uint32_t& bytes) {
-    const float b[4] = {lo0, hi0, lo1, hi1};
-    bytes = 0;
-    for (int j = 0; j < 4; ++j) {
-        const bool up = (j & 1) != 0;   // hi bounds round up, lo bounds down
-        int q = (int)(up ? ceilf((b[j] - o) / sc) : floorf((b[j] - o) / sc));
-        q = min(max(q, 0), 255);
-        if (up) {
-            while (q < 255 && fmaf((float)q, sc, o) < b[j]) ++q;
-            if (fmaf((float)q, sc, o) < b[j]) return false;
-        } else {
-            while (q > 0 && fmaf((float)q, sc, o) > b[j]) --q;
-            if (fmaf((float)q, sc, o) > b[j]) return false;
-        }
-        bytes |= (uint32_t)q << (8 * j);
-    }
-    return true;
-}
-
-__global__ __launch_bounds__(256) void k_qnodes_convert(const float4* __restrict__ nodes, uint32_t n,
-                                                        const uint32_t* __restrict__ off, float4* __restrict__ q,
-                                                        int* __restrict__ fail) {
-    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float4 n0 = nodes[4 * (size_t)i], n1 = nodes[4 * (size_t)i + 1], n2 = nodes[4 * (size_t)i + 2];
-    const int4 w = *reinterpret_cast<const int4*>(&nodes[4 * (size_t)i + 3]);
-    float4* dst = q + off[i];
-    if (w.x >= 0) {   // child 0 box (n0.x, n0.z, n2.x)-(n0.y, n0.w, n2.y), child 1 (n1.x, n1.z, n2.z)-(n1.y, n1.w, n2.w)
-        float ox, oy, oz;
-        uint32_t bx = 0, by = 0, bz = 0, ex = 0, ey = 0, ez = 0;
-        bool ok = quantExp(n0.x, n0.y, n1.x, n1.y, ox, ex) && quantExp(n0.z, n0.w, n1.z, n1.w, oy, ey) &&
-                  quantExp(n2.x, n2.y, n2.z, n2.w, oz, ez) && (uint32_t)w.y < n;
-        const uint32_t leaf0 = ok && reinterpret_cast<const int4*>(&nodes[4 * (size_t)w.x + 3])->x < 0 ? 1u : 0u;
-        const uint32_t leaf1 = ok && reinterpret_cast<const int4*>(&nodes[4 * (size_t)w.y + 3])->x < 0 ? 1u : 0u;
-        // the y and z steps carry a mantissa from the fields below their exponent (qScales: 1 + e_x / 512
-        // for y, 1 + e_y / 512 + e_x / 2^18 for z, about 1.24): one exponent less then often still covers
-        // the extent, which gives those axes the x axis's step sizes (1.44 x the ideal step on average
-        // instead of 1.79); quantBytes decides, y first (z's mantissa depends on e_y)
-        uint32_t meta = ex | (ey << 9) | (ez << 18) | (leaf0 << 27);
-        if (ok && ey > 1 && quantBytes(n0.z, n0.w, n1.z, n1.w, oy, qScales(meta - (1u << 9)).y, by)) meta -= 1u << 9;
-        if (ok && ez > 1 && quantBytes(n2.x, n2.y, n2.z, n2.w, oz, qScales(meta - (1u << 18)).z, bz)) meta -= 1u << 18;
-        const QScales sc = qScales(meta);
-        ok = ok && quantBytes(n0.x, n0.y, n1.x, n1.y, ox, sc.x, bx) && quantBytes(n0.z, n0.w, n1.z, n1.w, oy, sc.y, by) &&
-             quantBytes(n2.x, n2.y, n2.z, n2.w, oz, sc.z, bz);
-        if (!ok) {
-            atomicOr(fail, 1);
-            return;
-        }
-        dst[0] = make_float4(ox, oy, oz, __uint_as_float((off[w.y] << 1) | leaf1));
-        dst[1] = make_float4(__uint_as_float(bx), __uint_as_float(by), __uint_as_float(bz), __uint_as_float(meta));
-        return;
-    }
-// leaf: its exact box (as the parent's record stores it) must be min / max of v0, v0 + e1, v0 + e2
-    // for the compact walk to test it from the triangle; else bit 31 sends the walk to the parent
-    bool slow = true;
-    const int par = w.y;   // k_leaf_parents
-    if (par >= 0 && (uint32_t)par < n) {
-        const float4 p0 = nodes[4 * (size_t)par], p1 = nodes[4 * (size_t)par + 1], p2 = nodes[4 * (size_t)par + 2];
-        const bool right = reinterpret_cast<const int4*>(&nodes[4 * (size_t)par + 3])->y == (int)i;
-        const f3 lo = right ? f3{p1.x, p1.z, p2.z} : f3{p0.x, p0.z, p2.x};
-        const f3 hi = right ? f3{p1.y, p1.w, p2.w} : f3{p0.y, p0.w, p2.y};
-        const f3 v0 = ld3(n0), v1 = v0 + ld3(n1), v2 = v0 + ld3(n2);
-        const f3 l = f3{fminf(fminf(v0.x, v1.x), v2.x), fminf(fminf(v0.y, v1.y), v2.y), fminf(fminf(v0.z, v1.z), v2.z)};
-        const f3 h = f3{fmaxf(fmaxf(v0.x, v1.x), v2.x), fmaxf(fmaxf(v0.y, v1.y), v2.y), fmaxf(fmaxf(v0.z, v1.z), v2.z)};
-        slow = __float_as_uint(l.x) != __float_as_uint(lo.x) || __float_as_uint(l.y) != __float_as_uint(lo.y) ||
-               __float_as_uint(l.z) != __float_as_uint(lo.z) || __float_as_uint(h.x) != __float_as_uint(hi.x) ||
-               __float_as_uint(h.y) != __float_as_uint(hi.y) || __float_as_uint(h.z) != __float_as_uint(hi.z);
-    }
-    dst[0] = n0;
-    dst[1] = n1;
-    dst[2] = make_float4(n2.x, n2.y, n2.z, __uint_as_float(i | (slow ? 0x80000000u : 0u)));
-}
-
 // Longest-first order of the camera / first-shading tiles from the previous call's camera-wave
 // times (FrameArgs::tileCost): tiles bucketed by log2 cost in 1/8 steps, buckets in descending
 // order (one workgroup; a tile's place inside its bucket is arbitrary -- any order gives the same
@@ -1259,21 +864,6 @@ __global__ __launch_bounds__(1024) void k_tile_order(const uint32_t* __restrict_
     }
     __syncthreads();
     for (int t = threadIdx.x; t < n; t += 1024) order[atomicAdd(&hist[bucket(cost[t])], 1u)] = (uint32_t)t;
-}
-
-// Attainable-bandwidth probe (mcrt_ctx_stream_copy): a persistent grid (8 workgroups per CU)
-// strides over the array; each lane keeps 4 independent 16-B nontemporal loads in flight.
-__global__ __launch_bounds__(256) void k_stream_copy(const f4* __restrict__ src, f4* __restrict__ dst, size_t n) {
-    const size_t step = (size_t)gridDim.x * 1024;
-    for (size_t base = (size_t)blockIdx.x * 1024 + threadIdx.x; base < n; base += step) {
-        f4 v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (base + 256 * k < n) v[k] = __builtin_nontemporal_load(src + base + 256 * k);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (base + 256 * k < n) __builtin_nontemporal_store(v[k], dst + base + 256 * k);
-    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1394,159 +984,8 @@ void launch_pose_snapshot(const mcrt_shape* shapes, PrevPose* out, int n, hipStr
     const int words = n * (int)(sizeof(PrevPose) / 4);
     hipLaunchKernelGGL(k_pose_snapshot, dim3((words + 255) / 256), dim3(256), 0, st, shapes, out, n);
 }
-void launch_accumulate(const FrameArgs& f, int frame, const mcrt_filter* filters, int filterStride, const float4* radiance,
-                       float4* wsum, float* wts, float4* image, hipStream_t st, const uint32_t* list, int listLen,
-                       const uint32_t* tileCount) {
-    if (list) {   // listLen > 0: whole workgroups of 4 waves, the surplus ones find numTiles in the table
-        hipLaunchKernelGGL(k_accumulate<true>, dim3((listLen * 64 + 255) / 256), dim3(256), 0, st, f, frame, filters,
-                           filterStride, radiance, wsum, wts, image, list, tileCount);
-        return;
-    }
-    const int blocks = (f.numTiles * 64 + 255) / 256;
-    hipLaunchKernelGGL(k_accumulate<false>, dim3(blocks), dim3(256), 0, st, f, frame, filters, filterStride, radiance, wsum,
-                       wts, image, list, tileCount);
-}
-
-void launch_denoise(int W, int H, int r, float ss, float sr, const float4* in, float4* out, hipStream_t st) {
-    hipLaunchKernelGGL(k_denoise, dim3((W + DENOISE_TILE - 1) / DENOISE_TILE, (H + DENOISE_TILE - 1) / DENOISE_TILE),
-                       dim3(DENOISE_TILE, DENOISE_TILE), 0, st, W, H, r, ss, sr, in, out);
-}
-void launch_tonemap(int n, float Lwhite, const float4* in, float4* out, hipStream_t st) {
-    hipLaunchKernelGGL(k_tonemap, dim3((n + 255) / 256), dim3(256), 0, st, n, Lwhite, in, out);
-}
-void launch_chase_init(void* rec, uint32_t n, hipStream_t st) {
-    hipLaunchKernelGGL(k_chase_init, dim3((n + 255) / 256), dim3(256), 0, st, reinterpret_cast<int4*>(rec), n, 777u);
-}
-void launch_chase(const void* rec, uint32_t n, int steps, int waves, uint32_t* sink, hipStream_t st) {
-    hipLaunchKernelGGL(k_chase, dim3(waves), dim3(64), 0, st, reinterpret_cast<const int4*>(rec), n, steps, sink);
-}
-
-hipError_t chase_compact(uint32_t n, double leafFrac, int steps, int waves, int iters, hipStream_t st, float* bestMs) {
-    uint32_t *units = nullptr, *off = nullptr, *sink = nullptr, last[2] = {0, 0};
-    int4* rec = nullptr;
-    void* tmp = nullptr;
-    size_t tmpBytes = 0;
-    const uint32_t leaf16 = (uint32_t)std::min(65536.0, std::max(0.0, leafFrac * 65536.0));
-    hipError_t e = hipMalloc(&units, 4 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&off, 4 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&sink, 4);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_chase_units, dim3((n + 255) / 256), dim3(256), 0, st, units, n, leaf16);
-        e = rocprim::exclusive_scan(nullptr, tmpBytes, units, off, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
-    }
-    if (e == hipSuccess) e = hipMalloc(&tmp, tmpBytes);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, tmpBytes, units, off, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&last[0], off + n - 1, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&last[1], units + n - 1, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess) e = hipMalloc(&rec, 16 * ((size_t)last[0] + last[1]));
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_chase_init_compact, dim3((n + 255) / 256), dim3(256), 0, st, rec, off, units, n);
-        hipEvent_t e0, e1;
-        hipEventCreate(&e0);
-        hipEventCreate(&e1);
-        float best = 1e30f;
-        for (int i = 0; i < iters + 1; ++i) {   // launch 0 warms caches and translations
-            hipEventRecord(e0, st);
-            hipLaunchKernelGGL(k_chase_compact, dim3(waves), dim3(64), 0, st, rec, off, units, n,
-                               i == 0 ? std::max(1, steps / 4) : steps, sink);
-            hipEventRecord(e1, st);
-            hipEventSynchronize(e1);
-            float ms = 0.0f;
-            hipEventElapsedTime(&ms, e0, e1);
-            if (i > 0 && ms < best) best = ms;
-        }
-        hipEventDestroy(e0);
-        hipEventDestroy(e1);
-        *bestMs = best;
-        e = hipGetLastError();
-    }
-    (void)hipFree(rec);
-    (void)hipFree(tmp);
-    (void)hipFree(sink);
-    (void)hipFree(off);
-    (void)hipFree(units);
-    return e;
-}
-
-void launch_leaf_parents(float4* nodes, uint32_t n, hipStream_t st) {
-    if (n == 0) return;
-    hipLaunchKernelGGL(k_leaf_parents, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n);
-}
-
-hipError_t build_qnodes(const float4* nodes, uint32_t n, float4** qOut, size_t* unitsOut, hipStream_t st) {
-    *qOut = nullptr;
-    *unitsOut = 0;
-    if (n == 0 || n >= (1u << 31)) return hipErrorNotSupported;
-    uint32_t *units = nullptr, *off = nullptr;
-    int* flags = nullptr;
-    void* tmp = nullptr;
-    size_t tmpBytes = 0;
-    float4* q = nullptr;
-    int h[2] = {0, 0};
-    uint32_t lastOff = 0, lastUnits = 0;
-    hipError_t e = hipMalloc(&units, 4 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&off, 4 * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&flags, 2 * sizeof(int));
-    if (e == hipSuccess) e = hipMemsetAsync(flags, 0, 2 * sizeof(int), st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_qnodes_sizes, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n, units, flags);
-        e = rocprim::exclusive_scan(nullptr, tmpBytes, units, off, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
-    }
-    if (e == hipSuccess) e = hipMalloc(&tmp, tmpBytes);
-    if (e == hipSuccess) e = rocprim::exclusive_scan(tmp, tmpBytes, units, off, 0u, (size_t)n, rocprim::plus<uint32_t>(), st);
-    if (e == hipSuccess) e = hipMemcpyAsync(h, flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&lastOff, off + n - 1, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(&lastUnits, units + n - 1, 4, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    const size_t total = (size_t)lastOff + lastUnits;
-    if (e == hipSuccess && h[0] != 0) e = hipErrorNotSupported;   // not depth-first
-    if (e == hipSuccess) e = hipMalloc(&q, 16 * total);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_qnodes_convert, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n, off, q, flags + 1);
-        e = hipMemcpyAsync(h + 1, flags + 1, sizeof(int), hipMemcpyDeviceToHost, st);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && h[1] != 0) e = hipErrorNotSupported;   // a box the bytes cannot bound
-    (void)hipFree(tmp);
-    (void)hipFree(flags);
-    (void)hipFree(off);
-    (void)hipFree(units);
-    if (e != hipSuccess) {
-        if (q) (void)hipFree(q);
-        return e;
-    }
-    *qOut = q;
-    *unitsOut = total;
-    return hipSuccess;
-}
-
 void launch_tile_order(const uint32_t* cost, int n, uint32_t* order, hipStream_t st) {
     hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, st, cost, n, order);
-}
-
-void launch_stream_copy(const float4* src, float4* dst, size_t n4, int numCUs, hipStream_t st) {
-    const size_t need = (n4 + 1023) / 1024;
-    const size_t blocks = std::min(need, (size_t)std::max(numCUs, 1) * 8);
-    hipLaunchKernelGGL(k_stream_copy, dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const f4*>(src),
-                       reinterpret_cast<f4*>(dst), n4);
-}
-
-
-void launch_band_pack(const FrameArgs& f, const float4* wsum, const float* wts, float* out, hipStream_t st) {
-    const int n = (int)(f.W * f.H);
-    hipLaunchKernelGGL(k_band_pack, dim3((n + 255) / 256), dim3(256), 0, st, (int)f.W, (int)f.H, f.bandRows >> 3,
-                       f.numBands, f.bandIndex, wsum, wts, out);
-}
-void launch_band_unpack(const FrameArgs& f, int maxRows, const float* recv, float4* wsum, float* wts, float4* image,
-                        hipStream_t st) {
-    const int n = (int)(f.W * f.H);
-    hipLaunchKernelGGL(k_band_unpack, dim3((n + 255) / 256), dim3(256), 0, st, (int)f.W, (int)f.H, f.bandRows >> 3,
-                       f.numBands, f.bandIndex, maxRows, recv, wsum, wts, image);
-}
-void launch_resolve(uint32_t W, uint32_t H, const float4* wsum, const float* wts, float4* image, hipStream_t st) {
-    const int n = (int)(W * H);
-    hipLaunchKernelGGL(k_resolve, dim3((n + 255) / 256), dim3(256), 0, st, n, wsum, wts, image);
 }
 
 }  // namespace mcrt

@@ -5,7 +5,7 @@
 // block, events and spill columns; the rest of the runtime borrows the current slot's camera hits
 // through borrow_camera_hits / release_slot and reads its radiance, lastBatch and stream
 // (mcrt_bdpt_host.cpp also the fields bdpt_render is handed).  The kernels and their launchers are
-// mcrt_kernels.hip's.
+// mcrt_kernels.hip's; k_accumulate and its launcher are mcrt_film.hip's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

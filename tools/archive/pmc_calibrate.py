@@ -3,7 +3,7 @@
 MI355X_MICROARCH.md calibrates FETCH_SIZE only for coalesced 16-B/lane streaming reads (it reports
 half their bytes) and calls other widths uncalibrated.  The traversal gathers one 64-B record per
 lane per step as four dependent-free 16-B loads at a random address -- exactly the access pattern
-of the dependent-gather probe (mcrt_ctx_gather_chase, mcrt_kernels.hip k_chase): 32 waves per CU,
+of the dependent-gather probe (mcrt_ctx_gather_chase, mcrt_probe.hip k_chase): 32 waves per CU,
 every lane following its own chain of uniformly random records.  With the record array far larger
 than every cache (the HBM case) nearly every step misses L2, so the memory-side demand is known:
 one 64-B record per step.  This program runs the probe at L2 (2 MiB), Infinity-Cache (122 MiB)
