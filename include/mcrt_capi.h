@@ -321,6 +321,26 @@ MCRT_API mcrt_status mcrt_scene_destroy(mcrt_scene scene);
 MCRT_API mcrt_status mcrt_scene_update_lights(mcrt_scene scene, const mcrt_light* lights, uint32_t n);
 MCRT_API mcrt_status mcrt_scene_update_materials(mcrt_scene scene, const mcrt_material* m, uint32_t n);
 MCRT_API mcrt_status mcrt_scene_update_shapes(mcrt_scene scene, const mcrt_shape* s, uint32_t n);
+/* Deforming meshes (skinning, cloth, morph targets, a simulation's output): replaces the positions
+ * -- and the normals, unless `normals` is NULL: they are kept -- of vertices [first, first + count)
+ * of the scene's vertex array.  Indices, uvs and the shapes stay.  MCRT_ERROR_INVALID_ARG for a NULL
+ * scene, a NULL position pointer or a range that does not lie inside the vertex array; a rejected
+ * call changes nothing.  The call runs after every launch already enqueued (it finishes the context
+ * stream, then the device, as mcrt_accel_update_transforms does), so frames in flight finish on the
+ * old vertices; it returns synchronised.  The surface records are regenerated in place: shading
+ * sees the new positions and normals from the next launch on.
+ * The acceleration structure is STALE afterwards, as after mcrt_scene_update_shapes, until
+ * mcrt_accel_refit (same topology, fast) or mcrt_accel_build (a new tree) has run.
+ * `area` of mcrt_shape and mcrt_light stays what the caller gave at creation: a deformed emitter
+ * wants mcrt_scene_update_shapes / mcrt_scene_update_lights with its new area too.
+ * _device: the same from device memory (a skinning kernel's output; float4 per vertex), copied on
+ * the context stream.  The host copy of the positions that the host builders read is then
+ * downloaded by the next call that needs it (mcrt_accel_build with a host builder, which the flat
+ * route of mcrt_accel_update_transforms ends in). */
+MCRT_API mcrt_status mcrt_scene_update_vertices(mcrt_scene scene, uint32_t first, uint32_t count,
+                                                const mcrt_float4* positions, const mcrt_float4* normals);
+MCRT_API mcrt_status mcrt_scene_update_vertices_device(mcrt_scene scene, uint32_t first, uint32_t count,
+                                                       const void* d_positions, const void* d_normals);
 /* BVH build over all shapes in world space (IntersectionApi::Commit ->
  * IntersectorLDS::Process -> Bvh2::Build, RR/src/accelerator/bvh2.h:206-315).
  * Hit shapeid = index into the shapes array (RTScene assigns SetId(nextShapeId++)
@@ -348,8 +368,24 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene scene, const mcrt_accel_opts* o
  * topology change. */
 MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene scene, const mcrt_shape* shapes, uint32_t n,
                                                   const mcrt_mat4* world_to_local /* may be NULL */);
-/* The last mcrt_accel_update_transforms: *path 0 none yet, 1 top level built on the device, 2 top
- * level built on the host, 3 full rebuild (flat); *ms its wall time including its synchronisation. */
+/* Refit: brings the structure of the last mcrt_accel_build up to date with the scene's current
+ * vertex positions (mcrt_scene_update_vertices) AND current shape transforms
+ * (mcrt_scene_update_shapes), keeping the tree's topology.
+ *  - flat (every builder: device SAH, host SAH, the perf tree, the LBVH): on the device
+ *    (mcrt_refit.hip).  Every leaf becomes what the builder would write for its triangle, bit for
+ *    bit; every box above becomes the exact union of its children; the compact records are
+ *    converted again in place.  Depth, record count and device bytes do not change, and after the
+ *    structure's first refit nothing is allocated.  Reported as path 4.
+ *  - two-level: rebuilt with the options of the last build; correct, not fast.  Reported as path 3.
+ * The tree's quality decays as the mesh leaves the pose it was built for: the caller decides when
+ * to call mcrt_accel_build again.  mcrt_accel_update_transforms on a flat scene keeps its full
+ * rebuild (path 3); a host that wants the fast path calls mcrt_scene_update_shapes and then this.
+ * Synchronises as mcrt_accel_update_transforms does.  MCRT_ERROR_NOT_READY before the first
+ * mcrt_accel_build. */
+MCRT_API mcrt_status mcrt_accel_refit(mcrt_scene scene);
+/* The last mcrt_accel_update_transforms or mcrt_accel_refit: *path 0 none yet, 1 top level built on
+ * the device, 2 top level built on the host, 3 full rebuild (flat update_transforms, two-level
+ * refit), 4 flat refit on the device; *ms its wall time including its synchronisation. */
 MCRT_API mcrt_status mcrt_accel_update_info(mcrt_scene scene, int32_t* path, double* ms);
 /* Build statistics: node count, bytes on device, host build milliseconds. */
 MCRT_API mcrt_status mcrt_accel_info(mcrt_scene scene, uint64_t* num_nodes, uint64_t* device_bytes,

@@ -1,11 +1,12 @@
 // mcrt_accel.cpp -- the scene's acceleration structure on the device: mcrt_accel_build over the
 // three builders (device SAH, device LBVH, the host layer's build_host_tree + upload) with one
-// commit into AccelState (mcrt_host.h), the transform-only update, the read-back entry points and
+// commit into AccelState (mcrt_host.h), the transform-only update, the refit, the read-back entry points and
 // the traversal views the render and query paths take.  The options, input checks and the host
 // build itself are mcrt_accel_host.cpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -140,6 +141,10 @@ static void drop(AccelState& a) {
     mcrt::top_build_destroy(a.topDev);   // sized for the previous top level
     a.topDev = nullptr;
     a.top2l = mcrt::Bvh2lTop();
+    a.refitParent.reset();   // the previous topology's
+    a.refitArrive.reset();
+    a.refitQOff.reset();
+    a.refitFlag.reset();
     a.tree = mcrt::TreeInfo();
     a.qRoot = 0;
     a.packets = false;
@@ -261,7 +266,9 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
             std::fprintf(stderr, "mcrt: device SAH build out of memory, building the same tree on the host\n");
     }
     mcrt::HostTree t;
-    if (mcrt::build_host_tree(plan, s->shapes.data(), s->shapes.size(), s->indices.data(), s->positions.data(), t) != MCRT_OK)
+    const mcrt_float4* positions = mcrt::host_positions(s);   // downloaded after a device-side vertex update
+    if (!positions) return fail(ctx, MCRT_ERROR_DEVICE, "download of the updated vertex positions failed");
+    if (mcrt::build_host_tree(plan, s->shapes.data(), s->shapes.size(), s->indices.data(), positions, t) != MCRT_OK)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, plan.twoLevel ? "two-level BVH build failed" : "BVH build failed");
     hipSetDevice(ctx->device);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -353,6 +360,75 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
     apply_spill_cap(a);
     done(path);
     if (forceDev && path != 1) return fail(ctx, MCRT_ERROR_DEVICE, "MCRT_TOP_BUILD=device: " + devWhy);
+    return MCRT_OK;
+}
+
+// Refit of a flat structure (mcrt_refit.hip).  What the topology fixes stays as the
+// build left it: depth, packets, the spill cap, qRoot, the compact records' offsets and size.  The
+// occluder-hint table stays too: a hint is an exact leaf test plus the parent's stored box
+// (mcrt_traverse.h hintOccludes: "any table content is safe"), and both were just rewritten.
+MCRT_API mcrt_status mcrt_accel_refit(mcrt_scene s) {
+    if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
+    mcrt_ctx ctx = s->ctx;
+    AccelState& a = s->accel;
+    if (!a.dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
+    const auto t0 = Clock::now();
+    hipSetDevice(ctx->device);
+    // as mcrt_accel_update_transforms: after every launch that reads the records
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    if (a.tree.twoLevel) {   // rebuilt: correct, not fast (refitting the per-mesh trees is DESIGN 2j's follow-up)
+        mcrt_accel_opts o = a.lastOpts;
+        const mcrt_status st = mcrt_accel_build(s, a.haveOpts ? &o : nullptr);
+        if (st != MCRT_OK) return st;
+        a.updatePath = 3;
+        a.updateMs = ms_since(t0);
+        return MCRT_OK;
+    }
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)a.tree.numNodes;
+    [[maybe_unused]] const int depth0 = a.tree.depth, cap0 = a.spillCap;
+    [[maybe_unused]] const bool packets0 = a.packets;
+    if (!a.refitParent) {   // the structure's first refit: everything a refit needs, once
+        DevBuf<int> parent, arrive, flag;
+        DevBuf<uint32_t> qoff;
+        HIPCHK(ctx, parent.alloc(n));
+        HIPCHK(ctx, arrive.alloc(n));
+        HIPCHK(ctx, flag.alloc(4));
+        HIPCHK(ctx, mcrt::launch_refit_parents(a.dNodes.get(), n, parent.get(), st));
+        if (a.dQNodes) {
+            size_t total = 0;
+            HIPCHK(ctx, mcrt::refit_qnode_offsets(a.dNodes.get(), n, qoff, &total, st));
+            if (total != a.dQNodes.size()) return fail(ctx, MCRT_ERROR_DEVICE, "compact records: size changed without a build");
+        }
+        a.refitParent = std::move(parent);
+        a.refitArrive = std::move(arrive);
+        a.refitFlag = std::move(flag);
+        a.refitQOff = std::move(qoff);
+    }
+    {
+        Timed t(ctx, K_REFIT, nullptr, (int64_t)n);
+        HIPCHK(ctx, mcrt::launch_refit(a.dNodes.get(), n, s->dShapes.get(), (uint32_t)s->shapes.size(), s->dIndices.get(),
+                                       s->dPositions.get(), a.refitParent.get(), a.refitArrive.get(), st));
+    }
+    int unbounded = 0;
+    if (a.dQNodes) {
+        Timed t(ctx, K_REFIT_QNODES, nullptr, (int64_t)n);
+        HIPCHK(ctx, mcrt::refit_qnodes(a.dNodes.get(), n, a.refitQOff.get(), a.dQNodes.get(), a.refitFlag.get(), st));
+    }
+    float root[16];
+    if (a.dQNodes) HIPCHK(ctx, hipMemcpyAsync(&unbounded, a.refitFlag.get(), sizeof(int), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipMemcpyAsync(root, a.dNodes.get(), sizeof(root), hipMemcpyDeviceToHost, st));
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    if (unbounded) {   // a box the bytes cannot bound: the 64-B walk answers the same, as after finish()
+        a.dQNodes.reset();
+        a.refitQOff.reset();
+    }
+    mcrt::root_record_box(root, a.tree.box);
+    // the topology's, untouched by construction
+    assert(a.tree.depth == depth0 && a.spillCap == cap0 && a.packets == packets0 && a.qRoot == (n == 1 ? 1u : 0u));
+    a.updatePath = 4;
+    a.updateMs = ms_since(t0);
     return MCRT_OK;
 }
 

@@ -47,7 +47,7 @@ const char* kKernelNames[K_COUNT] = {"k_primary",    "k_shade0",      "k_shadeN"
                                      "k_atrous_s1",   "k_atrous_s2",   "k_atrous_s4",  "k_atrous_s8",
                                      "k_atrous_s16",  "k_atrous_s32",  "k_atrous_s64", "k_atrous_s128",
                                      "k_temporal",    "k_temporal_var", "k_guides_motion", "k_temporal_motion",
-                                     "k_tile_error",  "k_tile_list"};
+                                     "k_tile_error",  "k_tile_list",   "k_refit",      "k_refit_qnodes"};
 
 }  // namespace
 
@@ -236,6 +236,17 @@ mcrt_status mcrt::check_updated_shapes(mcrt_scene s, const mcrt_shape* sh, uint3
     return MCRT_OK;
 }
 
+const mcrt_float4* mcrt::host_positions(mcrt_scene s) {
+    if (s->positionsStale) {   // the update that left it stale ended synchronised
+        hipSetDevice(s->ctx->device);
+        if (hipMemcpy(s->positions.data(), s->dPositions.get(), sizeof(float4) * s->positions.size(),
+                      hipMemcpyDeviceToHost) != hipSuccess)
+            return nullptr;
+        s->positionsStale = false;
+    }
+    return s->positions.data();
+}
+
 // ---------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------
@@ -377,6 +388,8 @@ static hipError_t build_surface_records(mcrt_scene s) {
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
+    s->surfMeshes = e == hipSuccess ? (uint32_t)nm : 0;
+    s->surfRecords = e == hipSuccess ? total : 0;
     return e;
 }
 
@@ -492,6 +505,56 @@ MCRT_API mcrt_status mcrt_scene_update_shapes(mcrt_scene s, const mcrt_shape* sh
     s->shapes.assign(sh, sh + n);   // after the last check: a rejected call leaves the scene as it was
     HIPCHK(s->ctx, build_surface_records(s));   // startVertex may have moved
     return MCRT_OK;
+}
+
+// The two vertex updates: `device` tells where positions / normals live.  Everything is checked
+// before anything is touched; the copies and the surface records' relaunch run on the context
+// stream after every launch already enqueued, and the call ends synchronised.
+static mcrt_status update_vertices(mcrt_scene s, uint32_t first, uint32_t count, const void* positions,
+                                   const void* normals, bool device) {
+    if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
+    mcrt_ctx ctx = s->ctx;
+    if (!positions) return fail(ctx, MCRT_ERROR_INVALID_ARG, "positions is NULL");
+    const size_t nv = s->positions.size();
+    if ((size_t)first > nv || (size_t)count > nv - first)
+        return fail(ctx, MCRT_ERROR_INVALID_ARG, "vertex range [" + std::to_string(first) + ", " +
+                                                     std::to_string((uint64_t)first + count) + ") is outside the scene's " +
+                                                     std::to_string(nv) + " vertices");
+    if (count == 0) return MCRT_OK;
+    hipSetDevice(ctx->device);
+    // as mcrt_accel_update_transforms: frames in flight finish on the old vertices
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    hipStream_t st = ctx->stream;
+    const hipMemcpyKind kind = device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const size_t bytes = sizeof(float4) * (size_t)count;
+    HIPCHK(ctx, hipMemcpyAsync(s->dPositions.get() + first, positions, bytes, kind, st));
+    if (normals) HIPCHK(ctx, hipMemcpyAsync(s->dNormals.get() + first, normals, bytes, kind, st));
+    if (device) {
+        s->positionsStale = true;
+    } else if (!s->positionsStale) {   // a stale copy is downloaded whole later, this range with it
+        std::memcpy(s->positions.data() + first, positions, bytes);
+    }
+    if (s->surfMeshes > 0) {   // in place: the meshes, their bases and the records' count are the topology's
+        const uint32_t* m = s->dSurfMeshes.get();
+        const int nm = (int)s->surfMeshes;
+        mcrt::launch_surface_records(m, m + nm, m + 2 * nm, nm, s->surfRecords, s->dIndices.get(), s->dPositions.get(),
+                                     s->dUvs.get(), s->dNormals.get(), s->dSurf.get(), st);
+        HIPCHK(ctx, hipGetLastError());
+    }
+    HIPCHK(ctx, hipStreamSynchronize(st));
+    HIPCHK(ctx, hipDeviceSynchronize());
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_scene_update_vertices(mcrt_scene s, uint32_t first, uint32_t count, const mcrt_float4* positions,
+                                                const mcrt_float4* normals) {
+    return update_vertices(s, first, count, positions, normals, false);
+}
+
+MCRT_API mcrt_status mcrt_scene_update_vertices_device(mcrt_scene s, uint32_t first, uint32_t count,
+                                                       const void* d_positions, const void* d_normals) {
+    return update_vertices(s, first, count, d_positions, d_normals, true);
 }
 
 MCRT_API mcrt_status mcrt_scene_motion_snapshot(mcrt_scene s) {

@@ -32,6 +32,7 @@ enum KernelId {
     K_ATROUS,   // one entry per level: K_ATROUS + i is the launch of step 2^i
     K_TEMPORAL = K_ATROUS + MCRT_ATROUS_MAX_LEVELS, K_TEMPORAL_VAR, K_GUIDES_MOTION, K_TEMPORAL_MOTION,
     K_TILE_ERROR, K_TILE_LIST,
+    K_REFIT, K_REFIT_QNODES,   // mcrt_accel_refit: the refit launch, the compact conversion
     K_COUNT
 };
 
@@ -86,6 +87,12 @@ struct AccelState {
     mcrt::TopBuildDev* topDev = nullptr;
     int updatePath = 0;
     double updateMs = 0.0;
+    // refit of a flat structure (mcrt_accel_refit): made by the structure's first refit, freed by
+    // drop(); refits after the first allocate nothing
+    DevBuf<int> refitParent;       // per record: its parent, -1 for the root
+    DevBuf<int> refitArrive;       // per record: arrivals of the running refit
+    DevBuf<uint32_t> refitQOff;    // per record: offset of its compact record (with dQNodes only)
+    DevBuf<int> refitFlag;         // the converter's "a box the bytes cannot bound"
     ~AccelState() { mcrt::top_build_destroy(topDev); }   // the buffers free themselves
 };
 
@@ -108,7 +115,11 @@ struct mcrt_scene_s {
     DevBuf<mcrt_material> dMaterials;
     DevBuf<float4> dSurf;           // surface records (SceneArgs::surf), 128 B per distinct mesh triangle
     DevBuf<uint32_t> dSurfBase;     // per shape: its first surface record
-    DevBuf<uint32_t> dSurfMeshes;   // build scratch: startIdx | startVertex | base per distinct mesh
+    DevBuf<uint32_t> dSurfMeshes;   // startIdx | startVertex | base per distinct mesh (kept: vertex updates relaunch over it)
+    uint32_t surfMeshes = 0, surfRecords = 0;   // distinct meshes with triangles, and the records of all
+    // mcrt_scene_update_vertices_device wrote dPositions alone: `positions` is downloaded by the
+    // next route that reads it (mcrt::host_positions)
+    bool positionsStale = false;
     uint32_t numLights = 0, numMaterials = 0, numTextures = 0;
     bool hasSobol = false;
     AccelState accel;   // the acceleration structure and what is sized by it (mcrt_accel.cpp)
@@ -322,6 +333,9 @@ mcrt_status check_device_flags(mcrt_ctx ctx);
 // the scene's current table counts (check_scene_tables), and a moved startVertex against the host
 // copies of the indices and the vertex count.  Changes nothing; MCRT_ERROR_INVALID_ARG names the shape.
 mcrt_status check_updated_shapes(mcrt_scene s, const mcrt_shape* shapes, uint32_t n);
+// The host copy of the positions, for a host builder: downloaded first when a device-side vertex
+// update left it stale (the caller has finished the context stream).  NULL after a failed download.
+const mcrt_float4* host_positions(mcrt_scene s);
 // An integer environment variable clamped to lo .. hi, or `def` when it is not set.
 int env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX);
 // Host reads and context-stream work that touch the slots: all slot streams first.

@@ -233,6 +233,18 @@ hipError_t build_qnodes(const float4* nodes, uint32_t n, DevBuf<float4>& q, hipS
 // off = their offsets (exclusive scan, device), *total = the units of all.  Finishes st.
 // hipErrorNotSupported for n == 0 and for a total >= 2^31: a record reference is off << 1 | leaf.
 hipError_t qnode_offsets(uint32_t* units, uint32_t* off, uint32_t n, size_t* total, hipStream_t st);
+// The refit's use of the converter (mcrt_accel_refit): the offsets of the structure's compact records
+// once (k_qnodes_sizes + qnode_offsets; *total = their units, which a refit cannot change), then the
+// conversion into the existing q after every refit (enqueued; *flag, device memory, is non-zero
+// afterwards for a box the bytes cannot bound: q is then unusable).  The first finishes st.
+hipError_t refit_qnode_offsets(const float4* nodes, uint32_t n, DevBuf<uint32_t>& off, size_t* total, hipStream_t st);
+hipError_t refit_qnodes(const float4* nodes, uint32_t n, const uint32_t* off, float4* q, int* flag, hipStream_t st);
+// mcrt_refit.hip: parent[i] of every record from the child words (-1 for the root), and the refit
+// itself: leaves from the current vertices and shapes, boxes bottom-up; arrive: n counters, zeroed
+// by the launch function
+hipError_t launch_refit_parents(const float4* nodes, uint32_t n, int* parent, hipStream_t st);
+hipError_t launch_refit(float4* nodes, uint32_t n, const mcrt_shape* dShapes, uint32_t numShapes, const uint32_t* dIndices,
+                        const float4* dPositions, const int* parent, int* arrive, hipStream_t st);
 void launch_bdpt_start(const SceneArgs& s, const FrameArgs& f, const BdptArgs& b, const mcrt_camera* cam,
                        const BdptQueue& camQ, const BdptQueue& lightQ, hipStream_t st);
 void launch_bdpt_vertex(const SceneArgs& s, const FrameArgs& f, const BdptArgs& b, int depth, const BdptQueue& qIn,

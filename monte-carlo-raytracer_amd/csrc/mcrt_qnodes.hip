@@ -187,4 +187,29 @@ hipError_t build_qnodes(const float4* nodes, uint32_t n, DevBuf<float4>& q, hipS
     return e;
 }
 
+hipError_t refit_qnode_offsets(const float4* nodes, uint32_t n, DevBuf<uint32_t>& off, size_t* total, hipStream_t st) {
+    off.reset();
+    *total = 0;
+    if (n == 0) return hipErrorNotSupported;
+    DevBuf<uint32_t> units;
+    DevBuf<int> flag;   // not depth-first: such a tree has no compact records, and the caller knows
+    hipError_t e = (hipError_t)units.alloc(n);
+    if (e == hipSuccess) e = (hipError_t)off.alloc(n);
+    if (e == hipSuccess) e = (hipError_t)flag.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(flag.get(), 0, sizeof(int), st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(k_qnodes_sizes, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n, units.get(), flag.get());
+        e = qnode_offsets(units.get(), off.get(), n, total, st);   // finishes st
+    }
+    if (e != hipSuccess) off.reset();
+    return e;
+}
+
+hipError_t refit_qnodes(const float4* nodes, uint32_t n, const uint32_t* off, float4* q, int* flag, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_qnodes_convert, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n, off, q, flag);
+    return hipGetLastError();
+}
+
 }  // namespace mcrt

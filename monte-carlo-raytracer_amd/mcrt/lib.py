@@ -43,6 +43,9 @@ SIGNATURES = {
     "mcrt_scene_update_lights": (_c.c_int, [_vp, _vp, _c.c_uint32]),
     "mcrt_scene_update_materials": (_c.c_int, [_vp, _vp, _c.c_uint32]),
     "mcrt_scene_update_shapes": (_c.c_int, [_vp, _vp, _c.c_uint32]),
+    "mcrt_scene_update_vertices": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp]),
+    "mcrt_scene_update_vertices_device": (_c.c_int, [_vp, _c.c_uint32, _c.c_uint32, _vp, _vp]),
+    "mcrt_accel_refit": (_c.c_int, [_vp]),
     "mcrt_accel_build": (_c.c_int, [_vp, _vp]),
     "mcrt_accel_update_transforms": (_c.c_int, [_vp, _vp, _c.c_uint32, _vp]),
     "mcrt_accel_update_info": (_c.c_int, [_vp, _c.POINTER(_c.c_int32), _c.POINTER(_c.c_double)]),
@@ -367,14 +370,39 @@ class DeviceScene:
         w2l = None if world_to_local is None else np.ascontiguousarray(world_to_local, np.float32)
         _check(lib().mcrt_accel_update_transforms(self.h, _p(self._shapes), len(self._shapes), _p(w2l)), self.ctx.h)
 
+    def update_vertices(self, positions, normals=None, first=0, count=None):
+        """mcrt_scene_update_vertices: positions (and normals, unless None: kept) of vertices
+        [first, first + count) from float32 (count, 4) numpy arrays, or -- mcrt_scene_update_vertices_device
+        -- from device pointers (ints; `count` is then required).  The structure is stale until
+        refit() or build()."""
+        if isinstance(positions, (int, np.integer)):
+            if count is None:
+                raise ValueError("count is required with device pointers")
+            nrm = None if normals is None else int(normals)
+            _check(lib().mcrt_scene_update_vertices_device(self.h, first, count, int(positions), nrm), self.ctx.h)
+            return
+        pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 4)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 4)
+        if nrm is not None and len(nrm) != len(pos):
+            raise ValueError("normals and positions differ in length")
+        count = len(pos) if count is None else count
+        if count > len(pos):
+            raise ValueError("count exceeds the arrays")
+        _check(lib().mcrt_scene_update_vertices(self.h, first, count, _p(pos), _p(nrm)), self.ctx.h)
+
+    def refit(self):
+        """mcrt_accel_refit: the structure follows the current vertices and shape transforms with
+        its topology kept (flat: on the device, update_info() path 4; two-level: rebuilt, path 3)."""
+        _check(lib().mcrt_accel_refit(self.h), self.ctx.h)
+
     def motion_snapshot(self):
         """mcrt_scene_motion_snapshot: the shapes' current poses become their previous poses (call it
         before this frame's update_transforms / update_shapes)."""
         _check(lib().mcrt_scene_motion_snapshot(self.h), self.ctx.h)
 
     def update_info(self):
-        """The last update_transforms: path 0 none yet, 1 top level built on the device, 2 on the
-        host, 3 full rebuild; ms its wall time (mcrt_accel_update_info)."""
+        """The last update_transforms or refit: path 0 none yet, 1 top level built on the device, 2 on
+        the host, 3 full rebuild, 4 flat refit on the device; ms its wall time (mcrt_accel_update_info)."""
         path, ms = _c.c_int32(), _c.c_double()
         _check(lib().mcrt_accel_update_info(self.h, _c.byref(path), _c.byref(ms)), self.ctx.h)
         return {"path": path.value, "ms": ms.value}
