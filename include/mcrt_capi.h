@@ -400,6 +400,17 @@ MCRT_API mcrt_status mcrt_accel_layout(mcrt_scene scene, int32_t* two_level, uin
  * where the host build leaves -1. */
 MCRT_API mcrt_status mcrt_accel_read_records(mcrt_scene scene, float* out, uint64_t max_records,
                                              uint64_t* num_records);
+/* Copy of the flat structure's compact records (the per-ray walks' copy of the tree)
+ * in 16-B units into out (up to max_units; out may be NULL to query).  *num_units is 0 where the
+ * structure has none; *root_ref (may be NULL) is the root's reference, unit offset << 1 | leaf bit. */
+MCRT_API mcrt_status mcrt_accel_read_compact(mcrt_scene scene, void* out, uint64_t max_units, uint64_t* num_units,
+                                             uint32_t* root_ref);
+/* The order of the compact records, on the host (no device needed): kids = n x (left, right) record
+ * indices, (-1, -1) for a leaf, every child index above its parent's; order 1 sibling pairs, 2
+ * treelets; off[i] = the 16-B unit at which record i starts (internal records take 2 units,
+ * leaves 3; a 128-B line is 8), *num_units the copy's size. */
+MCRT_API mcrt_status mcrt_accel_compact_order(const int32_t* kids, uint32_t n, int32_t order, uint32_t* off,
+                                              uint64_t* num_units);
 /* ------------------------------------------------------------------------ */
 /* Scene ingestion for C/C++ hosts (mcrt_objload.cpp): OBJ + MTL + PNG into the
  * SCENE_PARAMS arrays, replacing the reference's assimp import + RTScene mesh,

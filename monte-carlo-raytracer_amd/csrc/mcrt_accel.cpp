@@ -174,9 +174,13 @@ static mcrt_status finish(mcrt_scene s, bool boxFromRoot) {
     // MCRT_QUANT_NODES=0 keeps the 64-B records everywhere (A/B, tests).  A tree the converter
     // cannot take (LBVH numbering) or a device without room for it (~0.8 GB at 10 M triangles)
     // keeps the 64-B walk: the same answers.
+    // MCRT_QNODE_ORDER picks their order (A/B, tests: 1 sibling pairs, 2 treelets, the default; either
+    // gives the same walks).
     if (!t.twoLevel && env_int("MCRT_QUANT_NODES", 1) != 0) {
         DevBuf<float4> q;
-        const hipError_t e = mcrt::build_qnodes(a.dNodes.get(), (uint32_t)t.numNodes, q, ctx->stream);
+        const int order = env_int("MCRT_QNODE_ORDER", mcrt::QORDER_TREELETS);
+        a.qOrder = order == mcrt::QORDER_SIBLINGS ? order : mcrt::QORDER_TREELETS;
+        const hipError_t e = mcrt::build_qnodes(a.dNodes.get(), (uint32_t)t.numNodes, a.qOrder, q, ctx->stream);
         if (e == hipSuccess) {
             a.dQNodes = std::move(q);
         } else if (e != hipErrorNotSupported && e != hipErrorOutOfMemory) {
@@ -398,7 +402,7 @@ MCRT_API mcrt_status mcrt_accel_refit(mcrt_scene s) {
         HIPCHK(ctx, mcrt::launch_refit_parents(a.dNodes.get(), n, parent.get(), st));
         if (a.dQNodes) {
             size_t total = 0;
-            HIPCHK(ctx, mcrt::refit_qnode_offsets(a.dNodes.get(), n, qoff, &total, st));
+            HIPCHK(ctx, mcrt::refit_qnode_offsets(a.dNodes.get(), n, a.qOrder, qoff, &total, st));
             if (total != a.dQNodes.size()) return fail(ctx, MCRT_ERROR_DEVICE, "compact records: size changed without a build");
         }
         a.refitParent = std::move(parent);
@@ -472,6 +476,35 @@ MCRT_API mcrt_status mcrt_accel_read_records(mcrt_scene s, float* out, uint64_t 
     hipSetDevice(ctx->device);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
     HIPCHK(ctx, hipMemcpy(out, a.dNodes.get(), 64 * std::min<uint64_t>(max_records, a.tree.numNodes), hipMemcpyDeviceToHost));
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_accel_read_compact(mcrt_scene s, void* out, uint64_t max_units, uint64_t* num_units,
+                                             uint32_t* root_ref) {
+    if (!s || !num_units) return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument");
+    const AccelState& a = s->accel;
+    if (!a.dNodes) return fail(s->ctx, MCRT_ERROR_INVALID_ARG, "scene has no acceleration structure");
+    *num_units = a.dQNodes.size();
+    if (root_ref) *root_ref = a.qRoot;
+    if (!out || !a.dQNodes) return MCRT_OK;
+    mcrt_ctx ctx = s->ctx;
+    hipSetDevice(ctx->device);
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    HIPCHK(ctx, hipMemcpy(out, a.dQNodes.get(), 16 * std::min<uint64_t>(max_units, a.dQNodes.size()), hipMemcpyDeviceToHost));
+    return MCRT_OK;
+}
+
+MCRT_API mcrt_status mcrt_accel_compact_order(const int32_t* kids, uint32_t n, int32_t order, uint32_t* off,
+                                              uint64_t* num_units) {
+    if (!kids || !off || !num_units || n == 0 || order < 1 || order > 2)
+        return fail(nullptr, MCRT_ERROR_INVALID_ARG, "NULL argument, no records or an unknown order");
+    for (uint32_t i = 0; i < n; ++i) {   // parents before their children, every record some node's child once
+        const int32_t l = kids[2 * (size_t)i], r = kids[2 * (size_t)i + 1];
+        if (l < 0) continue;
+        if ((uint32_t)l <= i || (uint32_t)l >= n || (uint32_t)r <= i || (uint32_t)r >= n || l == r)
+            return fail(nullptr, MCRT_ERROR_INVALID_ARG, "child indices must lie above their parent's");
+    }
+    *num_units = mcrt::qnode_order_offsets(kids, n, order, off);
     return MCRT_OK;
 }
 

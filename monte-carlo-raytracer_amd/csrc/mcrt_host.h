@@ -66,6 +66,7 @@ struct AccelState {
     mcrt::TreeInfo tree;       // counts, depth, layout, builder, world box
     // compact records of the flat tree (TraceCtx::qnodes; mcrt::build_qnodes), empty when not built
     DevBuf<float4> dQNodes;
+    int qOrder = 0;   // their order (QORDER_*), for the refit's offsets
     uint32_t qRoot = 0;
     bool packets = false;      // coherent launches as wave packets
     double buildMs = 0.0;

@@ -223,21 +223,27 @@ void launch_tonemap(int n, float Lwhite, const float4* in, float4* out, hipStrea
 void launch_leaf_parents(float4* nodes, uint32_t n, hipStream_t st);
 // order[0..n) = tiles by descending cost[tile] (bucketed; one workgroup)
 void launch_tile_order(const uint32_t* cost, int n, uint32_t* order, hipStream_t st);
-// mcrt_qnodes.hip: compact records of a flat DFS tree (after launch_leaf_parents) into q, 16-B units;
-// hipErrorNotSupported when the tree is not in DFS order (left child = i + 1), a box cannot be
-// bounded by the bytes, or qnode_offsets refuses.  q is empty after any failure.
+// mcrt_qnodes.hip: compact records of a flat DFS tree (after launch_leaf_parents) into q, 16-B units,
+// in the given order (QORDER_*); hipErrorNotSupported when the tree is not in DFS order
+// (left child = i + 1), a box cannot be bounded by the bytes, or the copy would take 2^31 units or more.
+// q is empty after any failure.
 template <class T>
 class DevBuf;   // mcrt_devbuf.h
-hipError_t build_qnodes(const float4* nodes, uint32_t n, DevBuf<float4>& q, hipStream_t st);
-// The compact layout's arithmetic: n records of units[i] = 2 or 3 16-B units packed back to back,
+enum { QORDER_SIBLINGS = 1, QORDER_TREELETS = 2 };
+hipError_t build_qnodes(const float4* nodes, uint32_t n, int order, DevBuf<float4>& q, hipStream_t st);
+// The order itself, on the host: kids = n x (left, right) record indices, (-1, -1) for a leaf, parents
+// before their children; off[i] = the 16-B unit at which record i starts.  Returns the copy's units.
+size_t qnode_order_offsets(const int* kids, uint32_t n, int order, uint32_t* off);
+// The probes' layout arithmetic: n records of units[i] = 2 or 3 16-B units packed back to back,
 // off = their offsets (exclusive scan, device), *total = the units of all.  Finishes st.
 // hipErrorNotSupported for n == 0 and for a total >= 2^31: a record reference is off << 1 | leaf.
 hipError_t qnode_offsets(uint32_t* units, uint32_t* off, uint32_t n, size_t* total, hipStream_t st);
 // The refit's use of the converter (mcrt_accel_refit): the offsets of the structure's compact records
-// once (k_qnodes_sizes + qnode_offsets; *total = their units, which a refit cannot change), then the
+// once (the build's order again; *total = their units, which a refit cannot change), then the
 // conversion into the existing q after every refit (enqueued; *flag, device memory, is non-zero
 // afterwards for a box the bytes cannot bound: q is then unusable).  The first finishes st.
-hipError_t refit_qnode_offsets(const float4* nodes, uint32_t n, DevBuf<uint32_t>& off, size_t* total, hipStream_t st);
+hipError_t refit_qnode_offsets(const float4* nodes, uint32_t n, int order, DevBuf<uint32_t>& off, size_t* total,
+                               hipStream_t st);
 hipError_t refit_qnodes(const float4* nodes, uint32_t n, const uint32_t* off, float4* q, int* flag, hipStream_t st);
 // mcrt_refit.hip: parent[i] of every record from the child words (-1 for the root), and the refit
 // itself: leaves from the current vertices and shapes, boxes bottom-up; arrive: n counters, zeroed

@@ -1,10 +1,13 @@
 // mcrt_qnodes.hip -- the acceleration structure's converter: the leaves' parent links and the compact
 // records of a flat tree (mcrt_traverse.h traverseQOct has the format and the exactness argument).
-// mcrt_accel.cpp's finish() is the only caller of launch_leaf_parents and build_qnodes; the layout's
-// offset arithmetic (qnode_offsets) is shared with the probe that imitates it (mcrt_probe.hip).
+// mcrt_accel.cpp's finish() is the only caller of launch_leaf_parents and build_qnodes.  The records'
+// order by cache line is qnode_order_offsets' (host); the back-to-back offset arithmetic
+// (qnode_offsets) serves the probe that imitates the walk's fetches (mcrt_probe.hip).
 //
 // Built with mcrt_kernels.o's flags, where the kernels came from: quantBytes divides on the device.
 #include <rocprim/device/device_scan.hpp>
+
+#include <vector>
 
 #include "mcrt_devbuf.h"
 #include "mcrt_device.h"
@@ -30,15 +33,16 @@ __global__ __launch_bounds__(256) void k_leaf_parents(float4* __restrict__ nodes
 }
 
 // Compact records (mcrt_traverse.h traverseQOct has the format and the exactness argument).
-// Sizes in 16-B units per 64-B record (internal 2, leaf 3); notDfs: a left child that is not the
-// next record (the LBVH's numbering) -- the compact walk takes the left child as the next record.
-__global__ __launch_bounds__(256) void k_qnodes_sizes(const float4* __restrict__ nodes, uint32_t n,
-                                                      uint32_t* __restrict__ units, int* __restrict__ notDfs) {
+// The child words of every record for the host's ordering pass (qnode_order_offsets): (left, right),
+// (-1, -1) for a leaf; notDfs: a left child that is not the next record (the LBVH's numbering) --
+// the ordering pass takes parents before their children, which the depth-first numbering gives.
+__global__ __launch_bounds__(256) void k_qnodes_kids(const float4* __restrict__ nodes, uint32_t n,
+                                                     int2* __restrict__ kids, int* __restrict__ notDfs) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int4 w = *reinterpret_cast<const int4*>(&nodes[4 * (size_t)i + 3]);
-    units[i] = w.x >= 0 ? 2u : 3u;
-    if (w.x >= 0 && w.x != (int)i + 1) atomicOr(notDfs, 1);
+    kids[i] = w.x >= 0 ? make_int2(w.x, w.y) : make_int2(-1, -1);
+    if (w.x >= 0 && (w.x != (int)i + 1 || (uint32_t)w.y >= n || w.y <= w.x)) atomicOr(notDfs, 1);
 }
 
 // One axis of an internal record: its origin (the smaller lo) and the exponent byte e of its step,
@@ -94,7 +98,10 @@ __global__ __launch_bounds__(256) void k_qnodes_convert(const float4* __restrict
         // for y, 1 + e_y / 512 + e_x / 2^18 for z, about 1.24): one exponent less then often still covers
         // the extent, which gives those axes the x axis's step sizes (1.44 x the ideal step on average
         // instead of 1.79); quantBytes decides, y first (z's mantissa depends on e_y)
-        uint32_t meta = ex | (ey << 9) | (ez << 18) | (leaf0 << 27);
+        // bits 27..31: what the right child's reference is above the left child's, 2 x the 16-B units
+        // between the two records + the leaf bits' difference (3..17: siblings are at most a line apart)
+        const uint32_t step = ok ? 2u * (off[w.y] - off[w.x]) + leaf1 - leaf0 : 0u;
+        uint32_t meta = ex | (ey << 9) | (ez << 18) | (step << 27);
         if (ok && ey > 1 && quantBytes(n0.z, n0.w, n1.z, n1.w, oy, qScales(meta - (1u << 9)).y, by)) meta -= 1u << 9;
         if (ok && ez > 1 && quantBytes(n2.x, n2.y, n2.z, n2.w, oz, qScales(meta - (1u << 18)).z, bz)) meta -= 1u << 18;
         const QScales sc = qScales(meta);
@@ -104,7 +111,7 @@ __global__ __launch_bounds__(256) void k_qnodes_convert(const float4* __restrict
             atomicOr(fail, 1);
             return;
         }
-        dst[0] = make_float4(ox, oy, oz, __uint_as_float((off[w.y] << 1) | leaf1));
+        dst[0] = make_float4(ox, oy, oz, __uint_as_float((off[w.x] << 1) | leaf0));
         dst[1] = make_float4(__uint_as_float(bx), __uint_as_float(by), __uint_as_float(bz), __uint_as_float(meta));
         return;
     }
@@ -159,50 +166,109 @@ hipError_t qnode_offsets(uint32_t* units, uint32_t* off, uint32_t n, size_t* tot
     return *total >= ((size_t)1 << 31) ? hipErrorNotSupported : hipSuccess;
 }
 
-hipError_t build_qnodes(const float4* nodes, uint32_t n, DevBuf<float4>& q, hipStream_t st) {
-    q.reset();
-    if (n == 0) return hipErrorNotSupported;
-    DevBuf<uint32_t> units, off;
-    DevBuf<int> flags;   // [0] not depth-first, [1] a box the bytes cannot bound
-    int h[2] = {0, 0};
-    size_t total = 0;
-    hipError_t e = (hipError_t)units.alloc(n);
-    if (e == hipSuccess) e = (hipError_t)off.alloc(n);
-    if (e == hipSuccess) e = (hipError_t)flags.alloc(2);
-    if (e == hipSuccess) e = hipMemsetAsync(flags.get(), 0, 2 * sizeof(int), st);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_qnodes_sizes, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n, units.get(), flags.get());
-    e = hipMemcpyAsync(h, flags.get(), sizeof(int), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = qnode_offsets(units.get(), off.get(), n, &total, st);   // finishes st: h[0] is there
-    if (e == hipSuccess && h[0] != 0) e = hipErrorNotSupported;
-    if (e == hipSuccess) e = (hipError_t)q.alloc(total);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_qnodes_convert, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n, off.get(), q.get(),
-                           flags.get() + 1);
-        e = hipMemcpyAsync(h + 1, flags.get() + 1, sizeof(int), hipMemcpyDeviceToHost, st);
+// The order of the compact copy: off[i] = the 16-B unit at which record i starts, for
+// a tree whose parents come before their children.  A 128-B line is 8 units; internal records take
+// 2, leaves 3.
+//   QORDER_SIBLINGS  the two children of a node side by side in one line, pairs in depth-first order;
+//   QORDER_TREELETS  a node and both its children in one line (a treelet); each of the two children's
+//                    own children starts a treelet, the two treelets of a sibling pair side by side
+//                    (in one line where both fit), pairs in depth-first order.
+// Siblings are never more than a line apart, so the walk reaches the right child from the left
+// child's reference and the 5-bit step of the parent's meta word (which the 64-B tree's own order,
+// the right child a whole subtree away, would not fit).
+size_t qnode_order_offsets(const int* kids, uint32_t n, int order, uint32_t* off) {
+    auto leaf = [&](uint32_t i) { return kids[2 * (size_t)i] < 0; };
+    auto units = [&](uint32_t i) { return leaf(i) ? 3u : 2u; };
+    auto fit = [](size_t cur, uint32_t u) { return (cur & 7u) + u > 8u ? (cur + 7u) & ~(size_t)7u : cur; };
+    size_t cur = 0;
+    auto place = [&](uint32_t i) { off[i] = (uint32_t)cur; cur += units(i); };
+    place(0);
+    if (order == QORDER_SIBLINGS) {
+        for (uint32_t i = 0; i < n; ++i) {
+            if (leaf(i)) continue;
+            const uint32_t l = (uint32_t)kids[2 * (size_t)i], r = (uint32_t)kids[2 * (size_t)i + 1];
+            cur = fit(cur, units(l) + units(r));
+            place(l);
+            place(r);
+        }
+        return cur;
     }
+    std::vector<uint8_t> inner(n, 0);   // 1: a treelet's child member, whose children start treelets
+    auto treelet = [&](uint32_t g) {    // g and its children, in one line
+        if (leaf(g)) { cur = fit(cur, 3u); place(g); return; }
+        const uint32_t l = (uint32_t)kids[2 * (size_t)g], r = (uint32_t)kids[2 * (size_t)g + 1];
+        cur = fit(cur, 2u + units(l) + units(r));
+        place(g);
+        place(l);
+        place(r);
+        inner[l] = inner[r] = 1;
+    };
+    cur = 0;
+    treelet(0);
+    for (uint32_t i = 1; i < n; ++i) {
+        if (!inner[i] || leaf(i)) continue;
+        treelet((uint32_t)kids[2 * (size_t)i]);
+        treelet((uint32_t)kids[2 * (size_t)i + 1]);
+    }
+    return cur;
+}
+
+// The offsets of a structure's compact records on the device, and *total = their units.  Finishes st.
+// hipErrorNotSupported for a tree that is not depth-first and for a total >= 2^31 (a record
+// reference is off << 1 | leaf).
+static hipError_t order_offsets(const float4* nodes, uint32_t n, int order, DevBuf<uint32_t>& off, size_t* total,
+                                hipStream_t st) {
+    off.reset();
+    *total = 0;
+    if (n == 0 || n >= (1u << 30)) return hipErrorNotSupported;
+    DevBuf<int2> kids;
+    DevBuf<int> flag;
+    int notDfs = 0;
+    hipError_t e = (hipError_t)kids.alloc(n);
+    if (e == hipSuccess) e = (hipError_t)flag.alloc(1);
+    if (e == hipSuccess) e = hipMemsetAsync(flag.get(), 0, sizeof(int), st);
+    if (e != hipSuccess) return e;
+    std::vector<int> hk(2 * (size_t)n);
+    hipLaunchKernelGGL(k_qnodes_kids, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n, kids.get(), flag.get());
+    e = hipMemcpyAsync(hk.data(), kids.get(), 2 * sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&notDfs, flag.get(), sizeof(int), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e == hipSuccess && h[1] != 0) e = hipErrorNotSupported;
+    if (e != hipSuccess) return e;
+    if (notDfs) return hipErrorNotSupported;
+    kids.reset();
+    std::vector<uint32_t> ho(n);
+    const size_t units = qnode_order_offsets(hk.data(), n, order, ho.data());
+    if (units >= ((size_t)1 << 31)) return hipErrorNotSupported;
+    e = (hipError_t)off.alloc(n);
+    if (e == hipSuccess) e = hipMemcpyAsync(off.get(), ho.data(), sizeof(uint32_t) * (size_t)n, hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // ho is free to go
+    if (e != hipSuccess) off.reset();
+    else *total = units;
+    return e;
+}
+
+hipError_t build_qnodes(const float4* nodes, uint32_t n, int order, DevBuf<float4>& q, hipStream_t st) {
+    q.reset();
+    DevBuf<uint32_t> off;
+    DevBuf<int> flag;   // a box the bytes cannot bound
+    int h = 0;
+    size_t total = 0;
+    hipError_t e = order_offsets(nodes, n, order, off, &total, st);
+    if (e == hipSuccess) e = (hipError_t)flag.alloc(1);
+    if (e == hipSuccess) e = (hipError_t)q.alloc(total);
+    // the padding between treelets is never read; zeroed so that the copy is a function of the tree
+    if (e == hipSuccess) e = hipMemsetAsync(q.get(), 0, 16 * total, st);
+    if (e == hipSuccess) e = refit_qnodes(nodes, n, off.get(), q.get(), flag.get(), st);
+    if (e == hipSuccess) e = hipMemcpyAsync(&h, flag.get(), sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && h != 0) e = hipErrorNotSupported;
     if (e != hipSuccess) q.reset();
     return e;
 }
 
-hipError_t refit_qnode_offsets(const float4* nodes, uint32_t n, DevBuf<uint32_t>& off, size_t* total, hipStream_t st) {
-    off.reset();
-    *total = 0;
-    if (n == 0) return hipErrorNotSupported;
-    DevBuf<uint32_t> units;
-    DevBuf<int> flag;   // not depth-first: such a tree has no compact records, and the caller knows
-    hipError_t e = (hipError_t)units.alloc(n);
-    if (e == hipSuccess) e = (hipError_t)off.alloc(n);
-    if (e == hipSuccess) e = (hipError_t)flag.alloc(1);
-    if (e == hipSuccess) e = hipMemsetAsync(flag.get(), 0, sizeof(int), st);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(k_qnodes_sizes, dim3((n + 255) / 256), dim3(256), 0, st, nodes, n, units.get(), flag.get());
-        e = qnode_offsets(units.get(), off.get(), n, total, st);   // finishes st
-    }
-    if (e != hipSuccess) off.reset();
-    return e;
+hipError_t refit_qnode_offsets(const float4* nodes, uint32_t n, int order, DevBuf<uint32_t>& off, size_t* total,
+                               hipStream_t st) {
+    return order_offsets(nodes, n, order, off, total, st);
 }
 
 hipError_t refit_qnodes(const float4* nodes, uint32_t n, const uint32_t* off, float4* q, int* flag, hipStream_t st) {

@@ -402,13 +402,16 @@ MCRT_DEV int traverse(const TraceCtx& c, const TraceRay& r, uint32_t* stk, uint3
 // ---------------------------------------------------------------------------
 // Compact records (TraceCtx::qnodes, built by k_qnodes_convert from the 64-B records of a
 // depth-first tree): the per-ray walks fetch 32 B per internal node and 48 B per leaf instead of
-// 64 B -- two or three 16-B loads instead of four.  The traversal launches are bound by the vector-
+// 64 B -- two or three 16-B loads instead of four.  Their order in memory is the converter's
+// (mcrt_qnodes.hip qnode_order_offsets: a node and both its children in one 128-B line); the walk
+// only follows references.  The traversal launches are bound by the vector-
 // memory pipeline (TA busy 0.94, one cache access per 16-B lane load), not by arithmetic.
-//   internal (32 B): (origin.xyz, right child ref) | (x bytes, y bytes, z bytes, meta): for axis a
+//   internal (32 B): (origin.xyz, left child ref) | (x bytes, y bytes, z bytes, meta): for axis a
 //     the bytes are (child 0 lo, child 0 hi, child 1 lo, child 1 hi) and a bound decodes as
 //     fmaf(q, s_a, origin_a), s_a = qScales(meta) (2^(e_a - 127) times a mantissa, qScales); meta =
-//     e_x | e_y << 9 | e_z << 18 | leaf(child 0) << 27.  The left child is the next record
-//     (depth-first order, ref + 4); the right child's ref (16-B offset << 1 | leaf bit) is stored.
+//     e_x | e_y << 9 | e_z << 18 | step << 27.  The left child's ref (16-B offset << 1 | leaf bit)
+//     is stored; the right child's is that plus step (2 x the units between the two records + the
+//     difference of their leaf bits: 5 bits, the siblings lie within one line of each other).
 //   leaf (48 B): (v0 | shape id), (v1 - v0 | prim id), (v2 - v0 | 64-B record index, bit 31 set when
 //     the leaf's exact box must come from its parent's 64-B record).
 // Why the answers are the 64-B walk's (RR intersect_bvh2_lds.cl:107-178):
@@ -595,8 +598,8 @@ MCRT_DEV void qwalk(const TraceCtx& c, const TraceRay& r, f3 inv, uint32_t* stk,
                 b0 = fmaxf(fmaxf(fmaxf(fminf(bx0, bx1), fminf(by0, by1)), fminf(bz0, bz1)), 0.0f);
                 b1 = minFar(fmaxf(bx0, bx1), fmaxf(by0, by1), fmaxf(bz0, bz1), tc);
             }
-            const uint32_t cl = ref + 4u + ((b.w >> 27) & 1u);   // the next record (+32 B), its leaf bit
-            const uint32_t cr = __float_as_uint(a.w);            // the right child's reference
+            const uint32_t cl = __float_as_uint(a.w);   // the left child's reference
+            const uint32_t cr = cl + (b.w >> 27);       // the right child's: its sibling, at most a line on
             const bool h0 = a0 <= a1, h1 = b0 <= b1;
             const bool c1first = h1 && (a0 > b0);   // intersect_bvh2_lds.cl:128-141
             if (h0 && h1) {   // defer the far child

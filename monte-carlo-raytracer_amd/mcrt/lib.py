@@ -67,6 +67,8 @@ SIGNATURES = {
     "mcrt_obj_warnings": (_c.c_char_p, [_vp]),
     "mcrt_obj_free": (None, [_vp]),
     "mcrt_accel_read_records": (_c.c_int, [_vp, _vp, _c.c_uint64, _vp]),
+    "mcrt_accel_read_compact": (_c.c_int, [_vp, _vp, _c.c_uint64, _vp, _vp]),
+    "mcrt_accel_compact_order": (_c.c_int, [_vp, _c.c_uint32, _c.c_int32, _vp, _vp]),
     "mcrt_accel_build_host_records": (_c.c_int, [_vp, _vp, _vp, _c.c_uint64, _c.POINTER(_c.c_uint64), _vp]),
     "mcrt_trace_closest": (_c.c_int, [_vp, _vp, _c.c_int32, _vp]),
     "mcrt_trace_any": (_c.c_int, [_vp, _vp, _c.c_int32, _vp]),
@@ -289,6 +291,16 @@ def build_host_records(scene, **opts):
                  "meshes": int(info[3])}
 
 
+def compact_order(kids, order):
+    """Host-only (no GPU): the compact records' offsets in 16-B units for a tree given as int32
+    (n, 2) child indices, (-1, -1) for a leaf (mcrt_accel_compact_order).  Returns (off, units)."""
+    kids = np.ascontiguousarray(kids, np.int32)
+    off = np.zeros(len(kids), np.uint32)
+    n = _c.c_uint64()
+    _check(lib().mcrt_accel_compact_order(_p(kids), len(kids), order, _p(off), _c.byref(n)))
+    return off, n.value
+
+
 def refit_host_records(scene, moved_shapes, world_to_local=None, **opts):
     """Host-only refit (no GPU): builds `scene`, then brings its structure up to date for
     moved_shapes (mcrt_accel_refit_host_records); world_to_local belongs to the moved shapes.
@@ -338,6 +350,15 @@ class DeviceScene:
         rec = np.zeros((n.value, 16), np.float32)
         _check(lib().mcrt_accel_read_records(self.h, _p(rec), n.value, _c.byref(n)), self.ctx.h)
         return rec
+
+    def compact_records(self):
+        """The compact records as uint32 (units, 4) and the root's reference (mcrt_accel_read_compact);
+        no rows where the structure has none."""
+        n, root = _c.c_uint64(), _c.c_uint32()
+        _check(lib().mcrt_accel_read_compact(self.h, None, 0, _c.byref(n), _c.byref(root)), self.ctx.h)
+        rec = np.zeros((n.value, 4), np.uint32)
+        _check(lib().mcrt_accel_read_compact(self.h, _p(rec), n.value, _c.byref(n), _c.byref(root)), self.ctx.h)
+        return rec, root.value
 
     def builder(self):
         """0 host build (or two-level), 1 device LBVH, 2 device SAH (mcrt_accel_builder)."""
