@@ -224,13 +224,14 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
     if (!s) return fail(nullptr, MCRT_ERROR_INVALID_ARG, "scene is NULL");
     mcrt_ctx ctx = s->ctx;
     AccelState& a = s->accel;
+    const mcrt::SceneGeometry g = mcrt::scene_geometry(s);
     mcrt::AccelPlan plan;
-    if (!mcrt::make_accel_plan(opts, s->shapes.data(), s->shapes.size(), plan))
+    if (!mcrt::make_accel_plan(opts, g.shapes, g.numShapes, plan))
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "num_bins out of range");
     const auto t0 = Clock::now();
-    std::vector<uint32_t> first(s->shapes.size());   // each shape's first triangle
+    std::vector<uint32_t> first(g.numShapes);   // each shape's first triangle
     size_t n = 0;
-    for (size_t si = 0; si < s->shapes.size(); ++si) { first[si] = (uint32_t)n; n += s->shapes[si].numTriangles; }
+    for (size_t si = 0; si < g.numShapes; ++si) { first[si] = (uint32_t)n; n += g.shapes[si].numTriangles; }
     if (n == 0) return fail(ctx, MCRT_ERROR_INVALID_ARG, "scene has no triangles (RR: Commit on empty scene throws)");
     if (n > (size_t)0x7fffffff) return fail(ctx, MCRT_ERROR_INVALID_ARG, "too many triangles");
     const int mode = plan.twoLevel ? -1 : plan.deviceBuild;
@@ -246,10 +247,9 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
         info.numTris = n;
         info.builder = mode == 1 ? 1 : 2;
         const hipError_t e =
-            mode == 1 ? mcrt::gpu_build_bvh(s->dShapes.get(), first, s->dIndices.get(), s->dPositions.get(), n, ctx->stream,
-                                            &built, &info.depth)
-                      : mcrt::gpu_build_sah(s->dShapes.get(), first, s->dIndices.get(), s->dPositions.get(), n, plan.cost,
-                                            plan.bins, plan.sah, ctx->stream, &built, &info.depth, &why);
+            mode == 1 ? mcrt::gpu_build_bvh(g.dShapes, first, g.dIndices, g.dPositions, n, ctx->stream, &built, &info.depth)
+                      : mcrt::gpu_build_sah(g.dShapes, first, g.dIndices, g.dPositions, n, plan.cost, plan.bins, plan.sah,
+                                            ctx->stream, &built, &info.depth, &why);
         if (e == hipSuccess) {
             nodes.adopt(built, 4 * info.numNodes);
             return commit(s, opts, nodes, info, nullptr, t0);
@@ -272,7 +272,7 @@ MCRT_API mcrt_status mcrt_accel_build(mcrt_scene s, const mcrt_accel_opts* opts)
     mcrt::HostTree t;
     const mcrt_float4* positions = mcrt::host_positions(s);   // downloaded after a device-side vertex update
     if (!positions) return fail(ctx, MCRT_ERROR_DEVICE, "download of the updated vertex positions failed");
-    if (mcrt::build_host_tree(plan, s->shapes.data(), s->shapes.size(), s->indices.data(), positions, t) != MCRT_OK)
+    if (mcrt::build_host_tree(plan, g.shapes, g.numShapes, g.indices, positions, t) != MCRT_OK)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, plan.twoLevel ? "two-level BVH build failed" : "BVH build failed");
     hipSetDevice(ctx->device);
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -289,12 +289,12 @@ static constexpr size_t MCRT_TOP_DEVICE_MIN_SHAPES = 10000;
 
 MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape* sh, uint32_t n,
                                                   const mcrt_mat4* world_to_local) {
-    if (!s || !sh || n != s->shapes.size())
+    if (!s || !sh || n != mcrt::scene_geometry(s).numShapes)
         return fail(s ? s->ctx : nullptr, MCRT_ERROR_INVALID_ARG, "shape count must not change");
     mcrt_ctx ctx = s->ctx;
     AccelState& a = s->accel;
     if (!a.dNodes) return fail(ctx, MCRT_ERROR_NOT_READY, "mcrt_accel_build has not been called");
-    if (!mcrt::same_topology(sh, s->shapes.data(), n, a.tree.twoLevel))
+    if (!mcrt::same_topology(sh, mcrt::scene_geometry(s).shapes, n, a.tree.twoLevel))
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "shape topology must not change");
     if (const mcrt_status st = mcrt::check_updated_shapes(s, sh, n)) return st;   // before any state changes
     const auto t0 = Clock::now();
@@ -319,8 +319,8 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
         return done(3);
     }
     // the mesh keys are unchanged, so the surface records and their bases are too
-    HIPCHK(ctx, hipMemcpy(s->dShapes.get(), sh, sizeof(mcrt_shape) * n, hipMemcpyHostToDevice));
-    s->shapes.assign(sh, sh + n);
+    if (const mcrt_status st = mcrt::store_shapes(s, sh, n)) return st;
+    const mcrt::SceneGeometry g = mcrt::scene_geometry(s);
     const mcrt::Bvh2lTop& top = a.top2l;
     const char* env = std::getenv("MCRT_TOP_BUILD");
     const bool forceHost = env && std::strcmp(env, "host") == 0;
@@ -340,7 +340,7 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
         if (!a.topDev) e = mcrt::top_build_create(top, &a.topDev);
         if (e == hipSuccess && world_to_local) e = mcrt::upload(dW2l, world_to_local, (size_t)n, ctx->stream);
         if (e == hipSuccess)
-            e = mcrt::top_build_run(a.topDev, s->dShapes.get(), dW2l.get(), a.dNodes.get(), ctx->stream, &depth, box, &why);
+            e = mcrt::top_build_run(a.topDev, g.dShapes, dW2l.get(), a.dNodes.get(), ctx->stream, &depth, box, &why);
         if (dW2l) {
             (void)hipStreamSynchronize(ctx->stream);
             dW2l.reset();
@@ -356,7 +356,7 @@ MCRT_API mcrt_status mcrt_accel_update_transforms(mcrt_scene s, const mcrt_shape
     }
     if (path == 2) {
         std::vector<float> rec(16 * a.tree.topNodes);
-        mcrt::build_bvh2l_top(top, s->shapes.data(), world_to_local, rec.data(), &depth, box);
+        mcrt::build_bvh2l_top(top, g.shapes, world_to_local, rec.data(), &depth, box);
         HIPCHK(ctx, hipMemcpy(a.dNodes.get(), rec.data(), 64 * a.tree.topNodes, hipMemcpyHostToDevice));
     }
     a.tree.depth = depth;
@@ -412,8 +412,9 @@ MCRT_API mcrt_status mcrt_accel_refit(mcrt_scene s) {
     }
     {
         Timed t(ctx, K_REFIT, nullptr, (int64_t)n);
-        HIPCHK(ctx, mcrt::launch_refit(a.dNodes.get(), n, s->dShapes.get(), (uint32_t)s->shapes.size(), s->dIndices.get(),
-                                       s->dPositions.get(), a.refitParent.get(), a.refitArrive.get(), st));
+        const mcrt::SceneGeometry g = mcrt::scene_geometry(s);
+        HIPCHK(ctx, mcrt::launch_refit(a.dNodes.get(), n, g.dShapes, (uint32_t)g.numShapes, g.dIndices, g.dPositions,
+                                       a.refitParent.get(), a.refitArrive.get(), st));
     }
     int unbounded = 0;
     if (a.dQNodes) {

@@ -1,10 +1,13 @@
 // mcrt_accel_host.cpp -- the acceleration structure's host layer: the parsed build options, the
-// input checks, the world-space triangles and the one host build that mcrt_accel_build
-// (mcrt_accel.cpp) uploads and mcrt_accel_build_host_records returns.  No device, no context: it
-// links into host-only programs (tests/asan) with mcrt_bvh.cpp and mcrt_bvh2l.cpp.
+// input checks (the scene tables' among them, and the surface records' mesh ranges), the world-space
+// triangles and the one host build that mcrt_accel_build (mcrt_accel.cpp) uploads and
+// mcrt_accel_build_host_records returns.  No device, no context: it links into host-only programs
+// (tests/asan) with mcrt_bvh.cpp and mcrt_bvh2l.cpp.
 #include <algorithm>
 #include <cstring>
+#include <map>
 #include <thread>
+#include <tuple>
 
 #include "mcrt_internal.h"
 
@@ -90,6 +93,33 @@ std::string scene_tables_message(int rule, uint32_t entry, uint32_t slot) {
     case TABLE_MESH_LIGHT: return "mesh light " + e + " has an invalid shape";
     }
     return "invalid scene tables";
+}
+
+uint32_t surface_meshes(const mcrt_shape* shapes, std::size_t n, std::vector<uint32_t>& meshes,
+                        std::vector<uint32_t>& shapeBase) {
+    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, uint32_t> meshOf;
+    std::vector<uint32_t> mStart, mVert, mBase;
+    shapeBase.resize(n);
+    uint32_t total = 0;
+    for (std::size_t i = 0; i < n; ++i) {
+        const mcrt_shape& sh = shapes[i];
+        auto key = std::make_tuple((uint32_t)sh.startIdx, (uint32_t)sh.startVertex, (uint32_t)sh.numTriangles);
+        auto it = meshOf.find(key);
+        if (it == meshOf.end()) {
+            it = meshOf.emplace(key, total).first;
+            if (sh.numTriangles > 0) {
+                mStart.push_back(sh.startIdx);
+                mVert.push_back(sh.startVertex);
+                mBase.push_back(total);
+            }
+            total += sh.numTriangles;
+        }
+        shapeBase[i] = it->second;
+    }
+    meshes = mStart;
+    meshes.insert(meshes.end(), mVert.begin(), mVert.end());
+    meshes.insert(meshes.end(), mBase.begin(), mBase.end());
+    return total;
 }
 
 bool same_topology(const mcrt_shape* a, const mcrt_shape* b, std::size_t n, bool twoLevel) {

@@ -220,7 +220,7 @@ mcrt_status mcrt::bdpt_render(mcrt_scene s, mcrt_framebuffer fb, const mcrt_came
     mcrt_camera* dCam = slot.block.get()->cam;
     HIPCHK(ctx, hipMemcpyAsync(dCam, cam, sizeof(mcrt_camera) * B, hipMemcpyHostToDevice, st));
     HIPCHK(ctx, hipMemsetAsync(bs.bdptCounters.get(), 0, 64 * sizeof(int), st));
-    if (s->numLights == 0) {   // RTBDPTPass.cpp:69: no lights -> pass skipped
+    if (mcrt::scene_num_lights(s) == 0) {   // RTBDPTPass.cpp:69: no lights -> pass skipped
         HIPCHK(ctx, hipMemsetAsync(slot.radiance.get(), 0, 16 * fb->N * (size_t)B, st));
         return MCRT_OK;
     }

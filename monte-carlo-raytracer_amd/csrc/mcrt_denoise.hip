@@ -591,7 +591,7 @@ static mcrt_status render_guides(mcrt_scene s, mcrt_framebuffer fb, const mcrt_c
     if (motion) {
         Timed t(ctx, K_GUIDES_MOTION, nullptr, (int64_t)f.numTiles * 64);
         mcrt::launch_guides_motion(mcrt::scene_args(s), f, dCam, hits, d.guideNormal.get(), d.guideAlbedo.get(),
-                                   s->dPrevPose.get(), d.motion.get(), d.motionNormal.get(), st);
+                                   mcrt::scene_prev_poses(s), d.motion.get(), d.motionNormal.get(), st);
     } else {
         Timed t(ctx, K_GUIDES, nullptr, (int64_t)f.numTiles * 64);
         mcrt::launch_guides(mcrt::scene_args(s), f, dCam, hits, d.guideNormal.get(), d.guideAlbedo.get(), st);

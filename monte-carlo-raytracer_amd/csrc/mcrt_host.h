@@ -1,17 +1,19 @@
 // mcrt_host.h -- the host runtime's objects behind the opaque handles of include/mcrt_capi.h, and
 // the few helpers that host code in another file may call.  Not part of the ABI.
 //
-// This is the boundary between the host files.  mcrt_capi.cpp holds the context, the scene tables,
-// the ray queries and mcrt_render_aov.  A subsystem with entry points of its own
-// (mcrt_denoise.hip, mcrt_adaptive.hip, mcrt_accel.cpp, mcrt_bdpt_host.cpp, mcrt_pt_host.cpp,
-// mcrt_film.hip, mcrt_probe.hip) includes this header, reaches the rest of the runtime through what
-// is declared here and nothing else, and keeps its state in one struct that only it names the fields
-// of: DenoiseState, AdaptiveState, BdptState and the frame slots (FrameSlot, mcrt_pt_host.cpp) held
-// by the frame buffer, AccelState held by the scene.  Two have no such struct: the probes keep no
-// state, and the film's planes (wsum, wts, image, denoised, display, bands) are plain fields of the
-// frame buffer, which the integrators' hosts and the denoiser read; mcrt_film.hip creates,
-// zero-fills, reads back, packs and post-processes them.  It compiles
-// as plain C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip translation unit.
+// This is the boundary between the host files.  mcrt_capi.cpp holds the context and the helpers
+// declared below.  A subsystem with entry points of its own (mcrt_denoise.hip, mcrt_adaptive.hip,
+// mcrt_accel.cpp, mcrt_bdpt_host.cpp, mcrt_pt_host.cpp, mcrt_film.hip, mcrt_probe.hip,
+// mcrt_scene.hip, mcrt_query.hip, mcrt_aov.hip) includes this header, reaches the rest of the
+// runtime through what is declared here and nothing else, and keeps its state in one struct that
+// only it names the fields of: DenoiseState, AdaptiveState, BdptState and the frame slots (FrameSlot,
+// mcrt_pt_host.cpp) held by the frame buffer, AccelState held by the scene, and the scene itself
+// (mcrt_scene_s, mcrt_scene.hip; its `ctx` is everyone's, `accel` mcrt_accel.cpp's).  Four have none:
+// the probes, the ray queries and the AOV pass keep no state, and the film's planes (wsum, wts,
+// image, denoised, display, bands) are plain fields of the frame buffer, which the integrators'
+// hosts and the denoiser read; mcrt_film.hip creates, zero-fills, reads back, packs and
+// post-processes them.  It compiles as plain C++ (-x c++ -D__HIP_PLATFORM_AMD__) and inside a .hip
+// translation unit.
 #pragma once
 #include <climits>
 #include <cstddef>
@@ -97,6 +99,8 @@ struct AccelState {
     ~AccelState() { mcrt::top_build_destroy(topDev); }   // the buffers free themselves
 };
 
+// The scene tables (mcrt_scene.hip).  Only mcrt_scene.hip names the fields, apart from `ctx` and
+// `accel`; the rest of the runtime goes through the views and readers declared below.
 struct mcrt_scene_s {
     mcrt_ctx ctx = nullptr;
     // host copies needed for the BVH build and dynamic updates
@@ -167,7 +171,7 @@ static_assert(sizeof(SlotBlock) == 512 + 176 * MCRT_MAX_BATCH_FRAMES + sizeof(mc
 // the current slot through borrow_camera_hits and release_slot below.
 struct FrameSlot {
     DevBuf<float4> radiance;
-    DevBuf<float4> hitsP;        // primary hits (mcrt_kernels.hip hitSlot)
+    DevBuf<float4> hitsP;        // primary hits (mcrt_shading.h hitSlot)
     DevBuf<float4> hitsE;        // extension hits by queue slot
     DevBuf<float4> eO[2], eD[2], eT[2];
     DevBuf<float4> sO, sD, sL;
@@ -323,20 +327,13 @@ struct mcrt_framebuffer_s {
 // regrow its buffers are empty, never stale.
 inline FrameSlot& cur_slot(mcrt_framebuffer fb) { return fb->slot[fb->cur]; }
 
-// mcrt_capi.cpp's helpers that host code in other files may call
+// What host code in another file may call.  First mcrt_capi.cpp's helpers
 namespace mcrt {
 // records msg as the thread's and the context's (may be NULL) last error; returns code
 mcrt_status fail(mcrt_ctx ctx, mcrt_status code, const std::string& msg);
 // Reports and clears the device-side error flags kernels raised since the last check (a traversal
 // stack overflow); call after a synchronisation
 mcrt_status check_device_flags(mcrt_ctx ctx);
-// The shapes of an update (same count and topology as the scene's, checked by the caller) against
-// the scene's current table counts (check_scene_tables), and a moved startVertex against the host
-// copies of the indices and the vertex count.  Changes nothing; MCRT_ERROR_INVALID_ARG names the shape.
-mcrt_status check_updated_shapes(mcrt_scene s, const mcrt_shape* shapes, uint32_t n);
-// The host copy of the positions, for a host builder: downloaded first when a device-side vertex
-// update left it stale (the caller has finished the context stream).  NULL after a failed download.
-const mcrt_float4* host_positions(mcrt_scene s);
 // An integer environment variable clamped to lo .. hi, or `def` when it is not set.
 int env_int(const char* name, int def, int lo = INT_MIN, int hi = INT_MAX);
 // Host reads and context-stream work that touch the slots: all slot streams first.
@@ -355,6 +352,32 @@ inline size_t tile_lanes(mcrt_framebuffer fb) { return (size_t)((fb->W + 7) / 8)
 // and for which launches, is the caller's.
 hipError_t walk_rule(TraceCtx& c, int64_t paths, DevBuf<float4>& suspend, DevBuf<int>& suspended, int counts,
                      size_t entries, hipStream_t st);
+// mcrt_scene.hip: the scene tables, as the rest of the runtime reads them
+// The geometry the builders and the refit read (mcrt_accel.cpp): the host shapes and indices, the
+// device shapes, indices and positions.  The host pointers hold until the next call that replaces shapes.
+struct SceneGeometry {
+    const mcrt_shape* shapes;
+    size_t numShapes;
+    const uint32_t* indices;
+    const mcrt_shape* dShapes;
+    const uint32_t* dIndices;
+    const float4* dPositions;
+};
+SceneGeometry scene_geometry(mcrt_scene s);
+// A new shape table (same count, same mesh keys: checked by the caller) on the device, with a
+// blocking copy, and on the host; the surface records and their bases stay as they are
+mcrt_status store_shapes(mcrt_scene s, const mcrt_shape* shapes, uint32_t n);
+int scene_num_lights(mcrt_scene s);
+bool scene_has_sobol(mcrt_scene s);                // a Sobol matrix table of the full size was uploaded
+const PrevPose* scene_prev_poses(mcrt_scene s);    // mcrt_scene_motion_snapshot's table, NULL before the first
+SceneArgs scene_args(mcrt_scene s);                // the kernels' view
+// The shapes of an update (same count and topology as the scene's, checked by the caller) against
+// the scene's current table counts (check_scene_tables), and a moved startVertex against the host
+// copies of the indices and the vertex count.  Changes nothing; MCRT_ERROR_INVALID_ARG names the shape.
+mcrt_status check_updated_shapes(mcrt_scene s, const mcrt_shape* shapes, uint32_t n);
+// The host copy of the positions, for a host builder: downloaded first when a device-side vertex
+// update left it stale (the caller has finished the context stream).  NULL after a failed download.
+const mcrt_float4* host_positions(mcrt_scene s);
 // mcrt_pt_host.cpp: the frame slots and the path tracer
 // A slot's buffers, stream and events: planes for `frames` frames of N pixels (T: the lanes of the
 // frame's tiles) and ray queues of Q entries (at least N).  After a failure the slot is empty.
@@ -422,7 +445,6 @@ hipError_t upload(DevBuf<T>& dst, const S* src, size_t count, hipStream_t st) {
     if (e != hipSuccess) return e;
     return hipMemcpyAsync(dst.get(), src, sizeof(T) * count, hipMemcpyHostToDevice, st);
 }
-SceneArgs scene_args(mcrt_scene s);
 // Allocates the plane (one T per pixel, zero-filled on the context stream) when it does not exist yet.
 template <class T>
 hipError_t ensure_plane(mcrt_framebuffer fb, DevBuf<T>& p) {

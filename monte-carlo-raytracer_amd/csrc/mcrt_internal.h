@@ -1,6 +1,7 @@
 // mcrt_internal.h -- structures shared by the host runtime (mcrt_capi.cpp and the subsystems' host
 // files) and the HIP translation units (mcrt_kernels.hip, mcrt_bdpt.hip, mcrt_film.hip,
-// mcrt_qnodes.hip, ...), and the launchers one file offers another.  Not part of the public ABI.
+// mcrt_qnodes.hip, ...), and the launchers one file offers another: a kernel that only its own
+// file launches (the scene's, the ray queries', k_aov) has none here.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,7 +23,7 @@ struct SceneArgs {
     const mcrt_light* lights;
     const mcrt_material* materials;
     const float4* nodes;  // unified BVH (mcrt_bvh.cpp): leaf k = (v0, shape), (e1, prim), (e2, -), marker
-    // Surface records (built at scene upload, mcrt_build_surface_records): one 128-B record per
+    // Surface records (built at scene upload, mcrt_scene.hip build_surface_records): one 128-B record per
     // triangle of each distinct (startIdx, startVertex) mesh with the object-space p0..p2,
     // uv0..uv2 and n0..n2 computeSurfaceInteraction reads (geometry.cl:180-191), so a hit costs
     // one cache line instead of an index line + 9 scattered vertex lines.  Shape k's triangle p
@@ -161,12 +162,6 @@ struct TraceCtx {
 #endif
 
 namespace mcrt {
-// n rays, or with countDev (device memory) min(*countDev, n) of them
-void launch_trace_rays(bool any, const TraceCtx& c, const mcrt_ray* rays, int n, const int* countDev,
-                       mcrt_intersection* hits, int* occl, hipStream_t st);
-void launch_surface_records(const uint32_t* meshStartIdx, const uint32_t* meshStartVertex, const uint32_t* meshBase,
-                            int numMeshes, uint32_t numRecords, const uint32_t* indices, const float4* positions,
-                            const float2* uvs, const float4* normals, float4* surf, hipStream_t st);
 // tileSlots >= 0: the wave-packet launch covers that many tile slots of f.tileOrder instead of all
 // f.numTiles (adaptive sampling); the per-ray camera kernels take no table and cover every tile
 void launch_primary(const TraceCtx& c, const FrameArgs& f, const mcrt_camera* cam, float4* hits, hipStream_t st,
@@ -195,13 +190,10 @@ void launch_shade0(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* ca
 void launch_shadeN(const SceneArgs& s, const FrameArgs& f, int bounce, const int* countIn, const float4* qO,
                    const float4* qD, const float4* qT, const float4* hits, float4* radiance, const QueueArgs& q,
                    int maxCount, hipStream_t st);
-void launch_aov(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits, int which,
-                float4* out, hipStream_t st);
-// denoiser guides at the camera-ray hits (k_guides): the band's rows of the two W*H planes
+// mcrt_aov.hip for mcrt_denoise.hip: denoiser guides at the camera-ray hits (k_guides): the band's rows
+// of the two W*H planes
 void launch_guides(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
                    float4* normalPlane, float4* albedoDepth, hipStream_t st);
-// the previous-pose table of n shapes, copied out of the scene's shape array (k_pose_snapshot)
-void launch_pose_snapshot(const mcrt_shape* shapes, PrevPose* out, int n, hipStream_t st);
 // k_guides_motion: k_guides' two planes and, from the previous poses (NULL: none), the motion and
 // previous-normal planes
 void launch_guides_motion(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
@@ -407,6 +399,13 @@ enum TableRule {
 int check_scene_tables(const SceneTables& t, uint32_t* entry, uint32_t* slot);
 // The message of a broken rule, naming the entry
 std::string scene_tables_message(int rule, uint32_t entry, uint32_t slot);
+// The surface records' ranges (SceneArgs::surf, mcrt_scene.hip): shapes with the same (startIdx,
+// startVertex, numTriangles) -- RTScene's instances of one mesh -- share one.  shapeBase[i] = the
+// first record of shape i; meshes = the startIdx of every distinct mesh with triangles in order of
+// first use, then their startVertex, then their first records (3 x their count).  Returns the
+// records of all.
+uint32_t surface_meshes(const mcrt_shape* shapes, std::size_t n, std::vector<uint32_t>& meshes,
+                        std::vector<uint32_t>& shapeBase);
 // same shapes but for transforms and surface data; two-level: the mesh key must not move
 bool same_topology(const mcrt_shape* a, const mcrt_shape* b, std::size_t n, bool twoLevel);
 // box (lo xyz, hi xyz) of a flat tree from its root record: the two child boxes, or the lone triangle

@@ -8,9 +8,9 @@
 //     k_shadow           any-hit over the shadow queue; radiance += L * V (ShadowPass)
 //     k_extend           closest hit over the extension queue (if b + 1 < D)
 //   (k_accumulate, the ReconstructionPass, is the film's: mcrt_film.hip)
-// Also here: the RadeonRays-style ray queries, the AOV and denoiser-guide passes over the camera
-// hits, the scene's small kernels (k_surface_records, k_pose_snapshot) and k_tile_order; at the end
-// the launchers the host files call (mcrt_internal.h).
+// Also here: k_tile_order; at the end the launchers mcrt_pt_host.cpp and mcrt_bdpt_host.cpp call
+// (mcrt_internal.h).  The ray queries are mcrt_query.hip's, the AOV and denoiser-guide passes over
+// the camera hits mcrt_aov.hip's, the scene's kernels mcrt_scene.hip's.
 // Traversal: the RadeonRays Bvh2 as one array of 64-B records (internal nodes hold both child
 // boxes, leaves their triangle), one flat loop per ray with a per-lane LDS short stack
 // (16 entries, [entry][lane] layout -> conflict free) spilling to a per-ray global column;
@@ -36,79 +36,6 @@
 // one LDS atomic per record (profiles/r03/ab items 18-19)
 #define MCRT_EXT_GROUPS 24
 
-// ---------------------------------------------------------------------------
-// RadeonRays-compatible queries on AoS rays (mcrt_trace_closest / mcrt_trace_any).
-// One ray per lane, one wave per workgroup (LDS stack 4 KB): the hardware dispatcher keeps
-// 8 waves per SIMD resident and refills them as they finish -- measured faster on MI355X
-// than a persistent grid pulling work from an atomic queue.
-// ---------------------------------------------------------------------------
-template <bool ANY, int LAY>
-__global__ __launch_bounds__(64) void k_trace_rays(TraceCtx c, const mcrt_ray* __restrict__ rays, int n,
-                                                   const int* __restrict__ countDev,
-                                                   mcrt_intersection* __restrict__ hits, int* __restrict__ occl) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[STACK_LDS * 64];
-    if (countDev) n = min(n, *countDev);   // RR's numrays in remote memory (radeon_rays.h:272-277)
-    const int lane = threadIdx.x;
-    const int i = blockIdx.x * 64 + lane;
-    if (i >= n) return;
-    const mcrt_ray rr = rays[i];
-    if (rr.extra[1] == 0) return;   // inactive: output untouched (intersect_bvh2_lds.cl:88)
-    TraceRay r;
-    r.o = ld3(rr.o);
-    r.d = ld3(rr.d);
-    r.tmax = rr.o.w;
-    r.mask = rr.extra[0];
-    if (ANY) {
-        occl[i] = traceAny<LAY>(c, r, lds + lane, raySpill(c, blockIdx.x, lane)) ? 1 : -1;
-        return;
-    }
-    float t;
-    const float4 h4 = traceClosest<LAY>(c, r, lds + lane, raySpill(c, blockIdx.x, lane), t);
-    if (__float_as_int(h4.z) >= 0) {
-        mcrt_intersection h;
-        h.shapeid = __float_as_int(h4.z);
-        h.primid = __float_as_int(h4.w);
-        h.padding[0] = h.padding[1] = 0;
-        h.uvwt.x = h4.x; h.uvwt.y = h4.y; h.uvwt.z = 0.0f; h.uvwt.w = t;
-        hits[i] = h;
-    } else {
-        hits[i].shapeid = -1;
-        hits[i].primid = -1;
-    }
-}
-
-// Surface records (SceneArgs::surf): record r of mesh m (meshBase[m] <= r < meshBase[m+1]) is
-// triangle p = r - meshBase[m] of the (startIdx, startVertex) range, packed as
-// (p0 p1.x | p1.yz p2.xy | p2.z uv0 uv1.x | uv1.y uv2 n0.x | n0.yz n1.xy | n1.z n2) + 2 pad float4.
-__global__ void k_surface_records(const uint32_t* __restrict__ meshStartIdx, const uint32_t* __restrict__ meshStartVertex,
-                                  const uint32_t* __restrict__ meshBase, int numMeshes, uint32_t numRecords,
-                                  const uint32_t* __restrict__ indices, const float4* __restrict__ positions,
-                                  const float2* __restrict__ uvs, const float4* __restrict__ normals,
-                                  float4* __restrict__ surf) {
-    const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= numRecords) return;
-    int lo = 0, hi = numMeshes - 1;   // last mesh with meshBase <= r
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (meshBase[mid] <= r) lo = mid; else hi = mid - 1;
-    }
-    const uint32_t p = r - meshBase[lo];
-    const uint32_t* ix = indices + meshStartIdx[lo] + 3 * p;
-    const uint32_t sv = meshStartVertex[lo];
-    const float4 a = positions[sv + ix[0]], b = positions[sv + ix[1]], c = positions[sv + ix[2]];
-    const float2 ta = uvs[sv + ix[0]], tb = uvs[sv + ix[1]], tc = uvs[sv + ix[2]];
-    const float4 na = normals[sv + ix[0]], nb = normals[sv + ix[1]], nc = normals[sv + ix[2]];
-    float4* R = surf + 8 * (size_t)r;
-    R[0] = make_float4(a.x, a.y, a.z, b.x);
-    R[1] = make_float4(b.y, b.z, c.x, c.y);
-    R[2] = make_float4(c.z, ta.x, ta.y, tb.x);
-    R[3] = make_float4(tb.y, tc.x, tc.y, na.x);
-    R[4] = make_float4(na.y, na.z, nb.x, nb.y);
-    R[5] = make_float4(nb.z, nc.x, nc.y, nc.z);
-    R[6] = make_float4(0.f, 0.f, 0.f, 0.f);
-    R[7] = make_float4(0.f, 0.f, 0.f, 0.f);
-}
-
 // Packed waves of a batch of n frames: the n waves of tile t (tileAll = t*n .. t*n + n-1) hold the
 // tile's 64 x n paths (pixel pi, frame k) in pixel-major order, q = 64 * (tileAll - t*n) + lane =
 // pi * n + k.  Each (pi, k) is covered once for any n; for n | 64 a wave is 64/n whole pixels.
@@ -117,15 +44,6 @@ MCRT_DEV void packedPath(const FrameArgs& f, int tileAll, int lane, int& k, int&
     const int q = (tileAll - tile * f.batch) * 64 + lane;
     pi = q / f.batch;
     k = q - pi * f.batch;
-}
-
-// Slot of a camera-ray hit record (k_primary* write it, k_shade0 / k_aov read it).  Packed waves:
-// (tile, pixel-in-tile, frame) with the frames fastest, the packed launches' own order, so a wave's
-// 64 records are one contiguous 1-KB run for its writes and reads (frame-plane order,
-// k * W*H + pixel, put each lane of a packed wave in another plane).  Else the frame plane's pixel.
-MCRT_DEV size_t hitSlot(const FrameArgs& f, int tile, int pi, int k, int x, int y) {
-    if (f.primaryPack && f.batch > 1) return ((size_t)tile * 64 + (size_t)pi) * (size_t)f.batch + (size_t)k;
-    return (size_t)k * f.W * f.H + (size_t)y * f.W + x;
 }
 
 // Camera ray generation fused with the first closest-hit query (RTPrimaryRaysPass):
@@ -675,172 +593,6 @@ __global__ __launch_bounds__(SHADEN_BLOCK) void k_shadeN(SceneArgs s, FrameArgs 
     if (o.pushE) { q.eOout[es] = o.eO; q.eDout[es] = o.eD; q.eTout[es] = o.eT; }
 }
 
-// ---------------------------------------------------------------------------
-// Per-pixel outputs of the camera-ray hits (mcrt_render_aov), tile order as k_shade0.
-//   MCRT_AOV_ALBEDO:     1 float4 = (uber Kd incl. texture, opacity.x); LOD per f.textureLod
-//   MCRT_AOV_TEXTURE_LOD: 3 float4 = (duvdx, duvdy), (diffuse-texture LOD, shape, uv),
-//                         the diffuse texture read mip-mapped (zeros where untextured)
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_aov(SceneArgs s, FrameArgs f, const mcrt_camera* __restrict__ camp,
-                                             const float4* __restrict__ hits, int which, float4* __restrict__ out) {
-    const int lane = threadIdx.x & 63;
-    const int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    int x, y;
-    if (tile >= f.numTiles || !tilePixel(f, tile, lane, x, y)) return;
-    const int pix = y * (int)f.W + x;
-    const int stride = which == MCRT_AOV_TEXTURE_LOD ? 3 : 1;
-    float4* o = out + (size_t)pix * stride;
-    for (int k = 0; k < stride; ++k) o[k] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    const float4 hit = hits[hitSlot(f, tile, lane, 0, x, y)];
-    const int shapeIdx = __float_as_int(hit.z), primIdx = __float_as_int(hit.w);
-    if (shapeIdx < 0) return;
-    const mcrt_camera& cam = *camp;
-    f3 dpdu, dpdv, dx, dy;
-    const Frame si = computeSurfaceInteraction(s, shapeIdx, primIdx, f2{hit.x, hit.y}, &dpdu, &dpdv);
-    cameraDiffDirs(cam, x, y, dx, dy);
-    TexLod L = surfaceUVDifferentials(si, dpdu, dpdv, ld3(cam.pos), dx, dy);
-    const int materialId = s.shapes[shapeIdx].materialId;
-    if (which == MCRT_AOV_TEXTURE_LOD) {
-        float lod = 0.0f;
-        f4 c = f4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (materialId != -1 && s.materials[materialId].uber_diffuseTexId != -1) {
-            const int t = s.materials[materialId].uber_diffuseTexId;
-            const mcrt_texture_desc tex = s.textures[t];
-            lod = mipLod(tex, L.duvdx, L.duvdy);
-            c = readTexLodDesc(s, tex, si.uv, lod);
-        }
-        o[0] = make_float4(L.duvdx.x, L.duvdx.y, L.duvdy.x, L.duvdy.y);
-        o[1] = make_float4(lod, __int_as_float(shapeIdx), si.uv.x, si.uv.y);
-        o[2] = make_float4(c.x, c.y, c.z, c.w);
-    } else {
-        L.on = f.textureLod != 0;
-        if (materialId != -1 && s.materials[materialId].type == 0) {
-            const Uber u = uberProps(s, s.materials[materialId], si.uv, L);
-            o[0] = make_float4(u.Kd.x, u.Kd.y, u.Kd.z, u.opacity.x);
-        }
-    }
-}
-
-// Denoiser guides of the camera-ray hits (mcrt_render_guides), tile order and albedo as k_aov:
-//   normalPlane = (n, n . (P - cam.pos)), n = the interpolated shading normal before normal
-//                 mapping, flipped to face the camera; the plane offset is camera-relative so a
-//                 scene far from the origin keeps its precision
-//   albedoDepth = (MCRT_AOV_ALBEDO's Kd, |P - cam.pos|)
-// A miss writes (0, 0, 0, 0) and (0, 0, 0, -1).  Band rows only.
-//
-// MOTION (k_guides_motion, mcrt_render_guides_motion) writes the same two records and, from the
-// shape's previous pose `prev` (mcrt_scene_motion_snapshot; NULL: none yet), two more:
-//   motion     = (P_prev - P, flag).  flag 0: no table, or the table's 32 matrix words and mesh key
-//                equal the shape's -- (0, 0, 0, 0) without evaluating anything.  flag 1: P_prev is
-//                si.p's expression over the table's toWorldTransform (three transformPoint3 of the
-//                same surface-record vertices, the same blend), d = P_prev - si.p per component.
-//                flag -1: the mesh key differs, (0, 0, 0, -1).  A miss is (0, 0, 0, 0).
-//   prevNormal = (n_prev, 0) where flag is 1, zeros otherwise: si.sn's expression over the table's
-//                toWorldInverseTranspose, flipped when n was (the same physical side).
-template <bool MOTION>
-__device__ __forceinline__ void guidesPixel(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* __restrict__ camp,
-                                            const float4* __restrict__ hits, float4* __restrict__ normalPlane,
-                                            float4* __restrict__ albedoDepth, const PrevPose* __restrict__ prev,
-                                            float4* __restrict__ motion, float4* __restrict__ prevNormal) {
-    const int lane = threadIdx.x & 63;
-    const int tile = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    int x, y;
-    if (tile >= f.numTiles || !tilePixel(f, tile, lane, x, y)) return;
-    const int pix = y * (int)f.W + x;
-    const float4 hit = hits[hitSlot(f, tile, lane, 0, x, y)];
-    const int shapeIdx = __float_as_int(hit.z), primIdx = __float_as_int(hit.w);
-    if (shapeIdx < 0) {
-        normalPlane[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        albedoDepth[pix] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
-        if (MOTION) {
-            motion[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            prevNormal[pix] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        }
-        return;
-    }
-    const mcrt_camera& cam = *camp;
-    f3 dpdu, dpdv, dx, dy;
-    const Frame si = computeSurfaceInteraction(s, shapeIdx, primIdx, f2{hit.x, hit.y}, &dpdu, &dpdv);
-    cameraDiffDirs(cam, x, y, dx, dy);
-    TexLod L = surfaceUVDifferentials(si, dpdu, dpdv, ld3(cam.pos), dx, dy);
-    L.on = f.textureLod != 0;
-    f3 kd = f3{0.0f, 0.0f, 0.0f};
-    const int materialId = s.shapes[shapeIdx].materialId;
-    if (materialId != -1 && s.materials[materialId].type == 0) kd = uberProps(s, s.materials[materialId], si.uv, L).Kd;
-    const f3 v = si.p - ld3(cam.pos);
-    f3 n = si.sn;
-    float off = cl_dot(n, v);
-    const bool flipped = off > 0.0f;
-    if (flipped) {
-        n = f3{-n.x, -n.y, -n.z};
-        off = -off;
-    }
-    normalPlane[pix] = make_float4(n.x, n.y, n.z, off);
-    albedoDepth[pix] = make_float4(kd.x, kd.y, kd.z, cl_length(v));
-    if (MOTION) {
-        float4 mv = make_float4(0.0f, 0.0f, 0.0f, 0.0f), pn = mv;
-        if (prev) {
-            const mcrt_shape shape = tableEntry(s.shapes, shapeIdx);
-            const PrevPose pp = tableEntry(prev, shapeIdx);
-            if (pp.startIdx != shape.startIdx || pp.startVertex != shape.startVertex ||
-                pp.numTriangles != shape.numTriangles) {
-                mv.w = -1.0f;
-            } else {
-                const uint32_t* a = reinterpret_cast<const uint32_t*>(&shape);
-                const uint32_t* b = reinterpret_cast<const uint32_t*>(&pp);
-                uint32_t diff = 0;
-#pragma unroll
-                for (int w = 0; w < 32; ++w) diff |= a[w] ^ b[w];
-                if (diff) {
-                    const float4* R = s.surf + 8 * ((size_t)tableEntry(s.surfBase, shapeIdx) + (uint32_t)primIdx);
-                    const float4 r0 = R[0], r1 = R[1], r2 = R[2], r3 = R[3], r4 = R[4], r5 = R[5];
-                    const f2 barycentrics = f2{hit.x, hit.y};
-                    const f3 p0 = transformPoint3(pp.toWorldTransform, mk3(r0.x, r0.y, r0.z));
-                    const f3 p1 = transformPoint3(pp.toWorldTransform, mk3(r0.w, r1.x, r1.y));
-                    const f3 p2 = transformPoint3(pp.toWorldTransform, mk3(r1.z, r1.w, r2.x));
-                    const f3 n0 = transformVector3(pp.toWorldInverseTranspose, mk3(r3.w, r4.x, r4.y));
-                    const f3 n1 = transformVector3(pp.toWorldInverseTranspose, mk3(r4.z, r4.w, r5.x));
-                    const f3 n2 = transformVector3(pp.toWorldInverseTranspose, mk3(r5.y, r5.z, r5.w));
-                    const f3 pPrev = p0 * (1.0f - barycentrics.x - barycentrics.y) + p1 * barycentrics.x + p2 * barycentrics.y;
-                    f3 nPrev = cl_normalize(n0 * (1.0f - barycentrics.x - barycentrics.y) + n1 * barycentrics.x + n2 * barycentrics.y);
-                    if (flipped) nPrev = f3{-nPrev.x, -nPrev.y, -nPrev.z};
-                    mv = make_float4(pPrev.x - si.p.x, pPrev.y - si.p.y, pPrev.z - si.p.z, 1.0f);
-                    pn = make_float4(nPrev.x, nPrev.y, nPrev.z, 0.0f);
-                }
-            }
-        }
-        motion[pix] = mv;
-        prevNormal[pix] = pn;
-    }
-}
-
-__global__ __launch_bounds__(256) void k_guides(SceneArgs s, FrameArgs f, const mcrt_camera* __restrict__ camp,
-                                                const float4* __restrict__ hits, float4* __restrict__ normalPlane,
-                                                float4* __restrict__ albedoDepth) {
-    guidesPixel<false>(s, f, camp, hits, normalPlane, albedoDepth, nullptr, nullptr, nullptr);
-}
-
-__global__ __launch_bounds__(256) void k_guides_motion(SceneArgs s, FrameArgs f, const mcrt_camera* __restrict__ camp,
-                                                       const float4* __restrict__ hits,
-                                                       float4* __restrict__ normalPlane,
-                                                       float4* __restrict__ albedoDepth,
-                                                       const PrevPose* __restrict__ prev, float4* __restrict__ motion,
-                                                       float4* __restrict__ prevNormal) {
-    guidesPixel<true>(s, f, camp, hits, normalPlane, albedoDepth, prev, motion, prevNormal);
-}
-
-// The previous-pose table (mcrt_scene_motion_snapshot): the first 35 words of every mcrt_shape --
-// both matrices and the mesh key -- and a zero, one word per thread.
-__global__ __launch_bounds__(256) void k_pose_snapshot(const mcrt_shape* __restrict__ shapes, PrevPose* __restrict__ out,
-                                                       int n) {
-    constexpr int WORDS = (int)(sizeof(PrevPose) / 4), SHAPE_WORDS = (int)(sizeof(mcrt_shape) / 4);
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n * WORDS) return;
-    const int k = i / WORDS, w = i - k * WORDS;
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(shapes);
-    reinterpret_cast<uint32_t*>(out)[i] = w < WORDS - 1 ? src[(size_t)k * SHAPE_WORDS + w] : 0u;
-}
-
 // Longest-first order of the camera / first-shading tiles from the previous call's camera-wave
 // times (FrameArgs::tileCost): tiles bucketed by log2 cost in 1/8 steps, buckets in descending
 // order (one workgroup; a tile's place inside its bucket is arbitrary -- any order gives the same
@@ -871,28 +623,6 @@ __global__ __launch_bounds__(1024) void k_tile_order(const uint32_t* __restrict_
 // ---------------------------------------------------------------------------
 
 namespace mcrt {
-
-void launch_trace_rays(bool any, const TraceCtx& c, const mcrt_ray* rays, int n, const int* countDev,
-                       mcrt_intersection* hits, int* occl, hipStream_t st) {
-    const dim3 g((n + 63) / 64), b(64);
-    {
-        if (any)
-            hipLaunchKernelGGL(pickLayout(c, k_trace_rays<true, LAY_TWO_LEVEL>, k_trace_rays<true, LAY_QUANT>,
-                                          k_trace_rays<true, LAY_PLAIN>),
-                               g, b, 0, st, c, rays, n, countDev, hits, occl);
-        else
-            hipLaunchKernelGGL(pickLayout(c, k_trace_rays<false, LAY_TWO_LEVEL>, k_trace_rays<false, LAY_QUANT>,
-                                          k_trace_rays<false, LAY_PLAIN>),
-                               g, b, 0, st, c, rays, n, countDev, hits, occl);
-    }
-}
-void launch_surface_records(const uint32_t* meshStartIdx, const uint32_t* meshStartVertex, const uint32_t* meshBase,
-                            int numMeshes, uint32_t numRecords, const uint32_t* indices, const float4* positions,
-                            const float2* uvs, const float4* normals, float4* surf, hipStream_t st) {
-    if (numRecords == 0) return;
-    k_surface_records<<<(numRecords + 255) / 256, 256, 0, st>>>(meshStartIdx, meshStartVertex, meshBase, numMeshes,
-                                                                numRecords, indices, positions, uvs, normals, surf);
-}
 
 void launch_primary(const TraceCtx& c, const FrameArgs& f, const mcrt_camera* cam, float4* hits, hipStream_t st,
                     int tileSlots) {
@@ -961,28 +691,6 @@ void launch_shadeN(const SceneArgs& s, const FrameArgs& f, int bounce, const int
                                : (last ? k_shadeN<true, false> : k_shadeN<false, false>);
     hipLaunchKernelGGL(k, dim3(blocks > 0 ? blocks : 1), dim3(SHADEN_BLOCK), 0, st, s, f, bounce, countIn, qO, qD, qT,
                        hits, radiance, q);
-}
-void launch_aov(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits, int which,
-                float4* out, hipStream_t st) {
-    const int blocks = (f.numTiles * 64 + 255) / 256;
-    hipLaunchKernelGGL(k_aov, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, s, f, cam, hits, which, out);
-}
-void launch_guides(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
-                   float4* normalPlane, float4* albedoDepth, hipStream_t st) {
-    const int blocks = (f.numTiles * 64 + 255) / 256;
-    hipLaunchKernelGGL(k_guides, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, s, f, cam, hits, normalPlane,
-                       albedoDepth);
-}
-void launch_guides_motion(const SceneArgs& s, const FrameArgs& f, const mcrt_camera* cam, const float4* hits,
-                          float4* normalPlane, float4* albedoDepth, const PrevPose* prev, float4* motion,
-                          float4* prevNormal, hipStream_t st) {
-    const int blocks = (f.numTiles * 64 + 255) / 256;
-    hipLaunchKernelGGL(k_guides_motion, dim3(blocks > 0 ? blocks : 1), dim3(256), 0, st, s, f, cam, hits, normalPlane,
-                       albedoDepth, prev, motion, prevNormal);
-}
-void launch_pose_snapshot(const mcrt_shape* shapes, PrevPose* out, int n, hipStream_t st) {
-    const int words = n * (int)(sizeof(PrevPose) / 4);
-    hipLaunchKernelGGL(k_pose_snapshot, dim3((words + 255) / 256), dim3(256), 0, st, shapes, out, n);
 }
 void launch_tile_order(const uint32_t* cost, int n, uint32_t* order, hipStream_t st) {
     hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, st, cost, n, order);

@@ -113,7 +113,7 @@ mcrt_status pt_render(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* cam,
     int* const extCnt = blk->n.ext;         // [b]
     const SceneArgs sa = scene_args(s);
     fb->lastIntegrator = MCRT_INTEGRATOR_PT;
-    if (s->numLights == 0) {   // RTPathTracingPass.cpp:42: no lights -> pass skipped; radiance = 0 here
+    if (mcrt::scene_num_lights(s) == 0) {   // RTPathTracingPass.cpp:42: no lights -> pass skipped; radiance = 0 here
         // every frame plane of the batch: accumulate reads `count` of them
         HIPCHK(ctx, hipMemsetAsync(radiance, 0, 16 * fb->N * (size_t)count, st));
         HIPCHK(ctx, hipEventRecord(slot.done, st));
@@ -244,7 +244,7 @@ mcrt_status render_frames(mcrt_scene s, mcrt_framebuffer fb, const mcrt_camera* 
     if (p->max_depth < 1 || p->max_depth > MCRT_MAX_BOUNCES) return fail(ctx, MCRT_ERROR_INVALID_ARG, "max_depth out of range");
     if (p->sampler != MCRT_SAMPLER_RANDOM && p->sampler != MCRT_SAMPLER_SOBOL)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "unknown sampler");
-    if (p->sampler == MCRT_SAMPLER_SOBOL && !s->hasSobol)
+    if (p->sampler == MCRT_SAMPLER_SOBOL && !mcrt::scene_has_sobol(s))
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "Sobol sampler requires the 1024x52 Sobol matrices in the scene");
     if (p->integrator != MCRT_INTEGRATOR_PT && p->integrator != MCRT_INTEGRATOR_BDPT)
         return fail(ctx, MCRT_ERROR_INVALID_ARG, "unknown integrator");
@@ -370,7 +370,7 @@ int pt_bounces(mcrt_framebuffer fb) {
 }  // namespace
 
 // Per-frame planes (radiance, primary hits) for `frames` frames of N pixels; ray queues of Q entries.
-// N: pixels; T: the frame's 8x8 tiles x 64 (the packed hit slots, mcrt_kernels.hip hitSlot)
+// N: pixels; T: the frame's 8x8 tiles x 64 (the packed hit slots, mcrt_shading.h hitSlot)
 hipError_t mcrt::slot_alloc(FrameSlot& k, size_t N, size_t T, int frames, size_t Q) {
     hipError_t e = hipSuccess;
     if (Q < N) Q = N;

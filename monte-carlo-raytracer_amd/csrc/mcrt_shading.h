@@ -16,6 +16,15 @@ MCRT_DEV bool tilePixel(const FrameArgs& f, int tile, int lane, int& x, int& y) 
     return x < (int)f.W && y < (int)f.H;
 }
 
+// Slot of a camera-ray hit record (k_primary* write it, k_shade0 / k_aov read it).  Packed waves:
+// (tile, pixel-in-tile, frame) with the frames fastest, the packed launches' own order, so a wave's
+// 64 records are one contiguous 1-KB run for its writes and reads (frame-plane order,
+// k * W*H + pixel, put each lane of a packed wave in another plane).  Else the frame plane's pixel.
+MCRT_DEV size_t hitSlot(const FrameArgs& f, int tile, int pi, int k, int x, int y) {
+    if (f.primaryPack && f.batch > 1) return ((size_t)tile * 64 + (size_t)pi) * (size_t)f.batch + (size_t)k;
+    return (size_t)k * f.W * f.H + (size_t)y * f.W + x;
+}
+
 // Longest-first order (FrameArgs::tileOrder): the launch's tile slot j runs tile tileOrder[j], the
 // batch frames of a tile staying adjacent.  Any order gives the same paths (keyed by pixel, frame).
 MCRT_DEV int orderedTileAll(const FrameArgs& f, int tileAll) {

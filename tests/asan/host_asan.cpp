@@ -2,7 +2,7 @@
 // (mcrt_camera.cpp), the host Bvh2 restatement (mcrt_bvh.cpp), the acceleration structure's host layer
 // (mcrt_accel_host.cpp over mcrt_bvh.cpp and mcrt_bvh2l.cpp) and the oracle (oracle/mcrt_oracle.c:
 // BVH build, closest / any-hit traversal against brute force, one PT and one BDPT frame, accumulate,
-// denoise, tone map), the scene-table check (check_scene_tables), the band split's arithmetic (mcrt_bands.h) and the runtime's owning device-buffer type (mcrt_devbuf.h, over malloc / free), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
+// denoise, tone map), the scene-table check (check_scene_tables), the surface records' mesh ranges (surface_meshes), the band split's arithmetic (mcrt_bands.h) and the runtime's owning device-buffer type (mcrt_devbuf.h, over malloc / free), all built with -fsanitize=address,undefined (tests/asan/Makefile).  Exit 0 =
 // every check held and the sanitizers reported nothing (they abort on the first finding).
 #include <unistd.h>
 
@@ -389,6 +389,35 @@ static int table_checks() {
     return 0;
 }
 
+// The surface records' mesh ranges (surface_meshes, mcrt_accel_host.cpp) called directly: shapes of
+// one mesh share a range, a shape without triangles takes none wherever it stands.  `meshes` is
+// startIdx | startVertex | first record per distinct mesh with triangles, sized exactly.
+static int surface_mesh_checks() {
+    using V = std::vector<uint32_t>;
+    V meshes, base;
+    const mcrt_shape quad = shape_at(0.0f, 0, 0, 2), fan = shape_at(1.0f, 6, 4, 3), none = shape_at(2.0f, 15, 9, 0);
+    auto run = [&](std::vector<mcrt_shape> sh) { return mcrt::surface_meshes(sh.data(), sh.size(), meshes, base); };
+    // one shape
+    CHECK(run({fan}) == 3 && meshes == V({6, 4, 0}) && base == V({0}));
+    // two shapes sharing a mesh with a third between them
+    CHECK(run({fan, quad, shape_at(5.0f, 6, 4, 3)}) == 5 && meshes == V({6, 0, 4, 0, 0, 3}) && base == V({0, 3, 0}));
+    // the same index range from another first vertex, or with another count, is another mesh
+    CHECK(run({fan, shape_at(0.0f, 6, 3, 3), shape_at(0.0f, 6, 4, 2)}) == 8 && meshes == V({6, 6, 6, 4, 3, 4, 0, 3, 6}) &&
+          base == V({0, 3, 6}));
+    // a shape with zero triangles first, in the middle and last: no mesh, the next record as its base
+    CHECK(run({none, quad, fan}) == 5 && meshes == V({0, 6, 0, 4, 0, 2}) && base == V({0, 0, 2}));
+    CHECK(run({quad, none, fan}) == 5 && meshes == V({0, 6, 0, 4, 0, 2}) && base == V({0, 2, 2}));
+    CHECK(run({quad, fan, none}) == 5 && meshes == V({0, 6, 0, 4, 0, 2}) && base == V({0, 2, 5}));
+    CHECK(run({none}) == 0 && meshes.empty() && base == V({0}));
+    CHECK(run({none, none, quad}) == 2 && meshes == V({0, 0, 0}) && base == V({0, 0, 0}));
+    // all shapes sharing one mesh
+    CHECK(run({quad, shape_at(1.0f, 0, 0, 2), shape_at(2.0f, 0, 0, 2), quad}) == 2 && meshes == V({0, 0, 0}) &&
+          base == V({0, 0, 0, 0}));
+    // no shapes: the outputs are emptied, not left over
+    CHECK(mcrt::surface_meshes(nullptr, 0, meshes, base) == 0 && meshes.empty() && base.empty());
+    return 0;
+}
+
 // host_asan --tables FILE: the check over tables written by tests/test_table_zoo_cpu.py (seven
 // uint32 counts -- shapes, materials, lights, textures, indices, vertices, the expected rule --
 // then the shape, material, light and index arrays); exit 0 when the check gives the expected rule
@@ -464,6 +493,7 @@ int main(int argc, char** argv) {
     if (devbuf_checks() != 0) return 1;
     if (band_checks() != 0) return 1;
     if (table_checks() != 0) return 1;
+    if (surface_mesh_checks() != 0) return 1;
     // a room (floor, back wall), a box, an emissive quad and a quad fan, with an MTL
     char tmpl[] = "/tmp/mcrt_asan_XXXXXX";
     const char* dir = mkdtemp(tmpl);

@@ -1,4 +1,4 @@
-"""Float64 truth and forward bounds for the motion planes of k_guides_motion (csrc/mcrt_kernels.hip).
+"""Float64 truth and forward bounds for the motion planes of k_guides_motion (csrc/mcrt_aov.hip).
 
 Truth, per pixel of a moved shape with poses M_prev, M_cur (toWorldTransform) and IT_prev, IT_cur
 (toWorldInverseTranspose), from the guide planes alone:
